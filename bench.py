@@ -1,8 +1,14 @@
 """Denoising steps/s of the VideoPainter hot path on MI355X (BASELINE.json config 2, data-parallel clips for N>1).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|4|5] [--mode dp|cfgpair|ulysses|stages]
-                    [--no-cpu-baseline] [--cpu-baseline-only [--cpu-full-step]]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
+                    [--config 2|4|5] [--mode dp|cfgpair|ulysses|stages] [--cpu-baseline-only [--cpu-full-step]]
     (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N)
+
+A plain run sets up, runs W untimed and K timed steps and prints the result line (value = K / the timed seconds,
+ms_per_step = the timed milliseconds / K).  --dump-outputs DIR also writes what the last timed step computed as
+DIR/<name>.npy (float32); seeds are fixed, so two builds run with the same arguments see the same inputs.  --full adds
+everything that takes runs of its own: the instrumented per-kernel roofline pass, the CPU baseline (config 2) and
+config 5's fp8-vs-bf16 drift check.
 
 One step = one iteration of the any-length pipeline's denoising loop (anyl.py:933-1034): 2-layer branch forward +
 42-layer CogVideoX-5b-I2V transformer forward at B=2 (CFG) with return_hidden_states / resample mask as the pipeline
@@ -11,9 +17,9 @@ requests them, then the fused CFG + DPM-Solver + replace-gt kernel.  Random-init
 N GPUs, --mode dp (default): each rank runs its own clip (weak scaling, no per-step collective); weights are
 initialised on rank 0 and broadcast over RCCL (config 3).  --mode cfgpair: one clip per rank PAIR, each rank runs one
 CFG half at B=1 and the pair exchanges the noise prediction with one all-gather per step (SURVEY.md §8e latency
-mode); value = clips' denoising steps/s summed over pairs.  The timed steps run without instrumentation; a separate
-pass afterwards records HIP events around every GEMM / attention launch for the per-kernel roofline.  Rank 0 prints
-ONE JSON line.
+mode); value = clips' denoising steps/s summed over pairs.  The timed steps run without instrumentation; with --full a
+separate pass afterwards records HIP events around every GEMM / attention launch for the per-kernel roofline.  Rank 0
+prints ONE JSON line.
 """
 from __future__ import annotations
 
@@ -77,6 +83,15 @@ def profiled_traffic(kind: str):
 def log(*a):
     if int(os.environ.get("RANK", "0")) == 0:
         print(*a, file=sys.stderr, flush=True)
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: each array of the last timed step as path/<name>.npy in float32 (whole arrays: the config-2
+    step's outputs are 18 MB, config 5's 48 MB)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 def _cpu_model() -> str:
@@ -405,9 +420,14 @@ def run_config4(args, world: int, rank: int, local: int) -> None:
         if stages is not None:
             from videopainter_amd.distributed import max_over_ranks
             elapsed = max_over_ranks(elapsed, device)
-        with K.timed_launches("attention", "gemm") as tl:  # instrumented pass (not timed): per-kernel breakdown
-            run(1, 1)
-            torch.cuda.synchronize()
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"latents": out[0]})
+        attn_ms = None
+        if args.full:
+            with K.timed_launches("attention", "gemm") as tl:  # instrumented pass (not timed): per-kernel breakdown
+                run(1, 1)
+                torch.cuda.synchronize()
+            attn_ms = tl.mean_ms("attention")
     n_steps = n_clips * n_windows * args.steps
     steps_per_s = n_steps / elapsed
     fl = sum(config4_step_flops(w) for w in range(n_windows)) * args.steps * n_clips
@@ -416,7 +436,6 @@ def run_config4(args, world: int, rank: int, local: int) -> None:
                 for w in range(n_windows)]
     fl_exec = sum(config4_step_flops_executed(w, n_masked[w - 1 if w > 0 else 0])
                   for w in range(n_windows)) * args.steps * n_clips
-    attn_ms = tl.mean_ms("attention")
     if rank == 0:
         line = {
             "metric": METRIC, "value": steps_per_s, "unit": "steps/s", "n_gpus": world, "steps": n_steps,
@@ -524,7 +543,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the instrumented per-kernel roofline pass, "
+                         "the CPU baseline (config 2, 1 GPU) and config 5's fp8-vs-bf16 drift check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0's clip) as DIR/<name>.npy, float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--fp8-out-bf16", action="store_true",
                     help="config 5 A/B: keep the attention output projection in bf16 (the round-6 form before)")
     ap.add_argument("--cpu-baseline-only", action="store_true")
@@ -642,7 +666,10 @@ def main():
     rope = harness.rope_for(F, HL, WL)
     gen = torch.Generator().manual_seed(42 + clip)
     fp8_drift = None
-    if args.config == 5:
+    if args.config == 5 and not args.full:
+        tr.enable_fp8(out=not args.fp8_out_bf16)
+        br.enable_fp8(out=not args.fp8_out_bf16)
+    elif args.config == 5:
         # the fp8 path's drift from this same model in bf16, one full forward on the step's inputs
         # (re-stated tolerance of config 5; block level vs the reference: tests/test_model_gpu.py)
         with torch.no_grad():
@@ -681,19 +708,27 @@ def main():
 
     with torch.no_grad():
         elapsed = timed_steps(one, sync_all, args.warmup, args.steps)  # uninstrumented
-        # separate instrumented pass (HIP events around every GEMM / attention launch on its stream), NOT timed
-        n_prof = min(2, args.steps)
-        with K.timed_launches("attention", "attention_fp8", "gemm", "gemm_mx") as tl:
-            for i in range(args.warmup + args.steps, args.warmup + args.steps + n_prof):
-                one(i)
-            torch.cuda.synchronize()
+        if args.dump_outputs and rank == 0 and args.steps + args.warmup > 0:
+            # what the step hands its caller: the transformer's noise prediction (uncond, text), the scheduler's
+            # x0 prediction and the window's next latents
+            dump_outputs(args.dump_outputs, {"noise_pred": st.extra["keep"][0], "pred_original_sample": st.old_pred,
+                                             "latents": st.latents})
+        if args.full:
+            # separate instrumented pass (HIP events around every GEMM / attention launch on its stream), NOT timed
+            n_prof = min(2, args.steps)
+            with K.timed_launches("attention", "attention_fp8", "gemm", "gemm_mx") as tl:
+                for i in range(args.warmup + args.steps, args.warmup + args.steps + n_prof):
+                    one(i)
+                torch.cuda.synchronize()
     if dist is not None:
         from videopainter_amd.distributed import max_over_ranks
         elapsed = max_over_ranks(elapsed, device)
     clips, steps_per_s = job_value(elapsed, args.steps, world, args.mode)
     ms_per_step = elapsed / args.steps * 1e3
-    classes, dominant = kernel_classes(tl, n_prof, args.config == 5, 1.0 / world if args.mode == "ulysses" else 1.0,
-                                       fp8_out=not args.fp8_out_bf16)
+    if args.full:
+        classes, dominant = kernel_classes(tl, n_prof, args.config == 5,
+                                           1.0 / world if args.mode == "ulysses" else 1.0,
+                                           fp8_out=not args.fp8_out_bf16)
     total_fl, ffn_fl = step_flops(split=True)
     if args.config == 5:  # time the step would take at the dense peaks of the dtypes its MFMAs use
         f8_fl = ffn_fl + (L + LB) * attn_flops_per_launch() + fp8_proj_flops(not args.fp8_out_bf16)
@@ -705,13 +740,21 @@ def main():
     if not math.isfinite(steps_per_s):
         raise RuntimeError("non-finite timing")
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == 2:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and args.config == 2:
         del st
         cpu = cpu_baseline()
     if rank == 0:
-        rf = dict(classes[dominant])
-        rf["kernel"] = f"{rf['kernel']} ({dominant}: dominant by time in this run)"
-        par = (f"cfgpair x{clips} (CFG halves on rank pairs, one noise-prediction all-gather per step)" if pair
+        full = {}
+        if args.full:
+            rf = dict(classes[dominant])
+            rf["kernel"] = f"{rf['kernel']} ({dominant}: dominant by time in this run)"
+            full = {"roofline": rf, "roofline_kernels": classes, "fp8_rel_l2_vs_bf16": fp8_drift,
+                    "gemm_ms_per_step": classes["gemm"]["ms_per_step"],
+                    "attention_ms_per_step": classes["attention"]["ms_per_step"],
+                    "timing": "timed steps uninstrumented; per-kernel numbers from a separate instrumented pass of "
+                              f"{n_prof} steps (HIP events on the launch stream)",
+                    "cpu_baseline": cpu}
+        par =(f"cfgpair x{clips} (CFG halves on rank pairs, one noise-prediction all-gather per step)" if pair
                else f"ulysses{world} (one clip, head-parallel: 2 all-to-alls per block)" if args.mode == "ulysses"
                else f"dp{world} (independent clips, weights replicated over RCCL: {args.bcast})")
         out = {
@@ -736,18 +779,12 @@ def main():
                           if args.qk_gamma > 0 else {}),
                        **({"lora_rank": args.lora_rank, "lora": "unfused (PEFT's forward), not in step_flop"}
                           if args.lora_rank > 0 else {})},
-            "roofline": rf,
-            "roofline_kernels": classes,
             "step_mfma_frac": step_frac,
-            "fp8_rel_l2_vs_bf16": fp8_drift,
             "step_flop": step_flops(),
-            "gemm_ms_per_step": classes["gemm"]["ms_per_step"],
-            "attention_ms_per_step": classes["attention"]["ms_per_step"],
             "weight_broadcast_s": t_bcast["seconds"] if t_bcast else None,
             "weight_replication": t_bcast,
-            "timing": "timed steps uninstrumented; per-kernel numbers from a separate instrumented pass of "
-                      f"{n_prof} steps (HIP events on the launch stream)",
-            "cpu_baseline": cpu,
+            "timing": "timed steps uninstrumented",
+            **full,  # --full: roofline, per-kernel times, fp8 drift (config 5), CPU baseline
         }
         print(json.dumps(out), flush=True)
     if dist is not None:

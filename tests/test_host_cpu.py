@@ -146,3 +146,19 @@ def test_branch_wo_text_construction():
     with pytest.raises(ValueError):
         b2(hidden_states=x, encoder_hidden_states=torch.zeros(1, 8, 32), branch_cond=torch.zeros(1, 3, 17, 16, 24),
            timestep=torch.tensor([10]), image_rotary_emb=None, wo_text=True)
+
+
+def test_bench_dump_outputs_writes_float32_npy(tmp_path):
+    """bench.py --dump-outputs: every array lands as DIR/<name>.npy in float32 with the tensor's values (bf16 widens
+    exactly), and a second dump into the same directory replaces the first."""
+    import bench
+    g = torch.Generator().manual_seed(3)
+    a = torch.randn(2, 3, 5, generator=g).to(torch.bfloat16)
+    b = torch.randn(7, generator=g)
+    out = tmp_path / "dump" / "nested"
+    bench.dump_outputs(str(out), {"latents": torch.zeros(2, 3, 5), "pred": b})
+    bench.dump_outputs(str(out), {"latents": a, "pred": b})
+    assert sorted(os.listdir(out)) == ["latents.npy", "pred.npy"]
+    la, pb = np.load(out / "latents.npy"), np.load(out / "pred.npy")
+    assert la.dtype == np.float32 and pb.dtype == np.float32
+    assert np.array_equal(la, a.float().numpy()) and np.array_equal(pb, b.numpy())

@@ -7,7 +7,8 @@
 # code and last line.  The session stops at the first failing step (a fault, abort, time-limit kill or test failure
 # ends it: nothing more runs on the GPU after it).  Shortcuts for the usual steps:
 #   gtests   the whole -m gpu suite          smoke   __graft_entry__.smoke()
-#   bench    bench.py --steps 5 --warmup 2   prof    bench.py under rocprofv3 --kernel-trace --stats
+#   bench    bench.py --full --steps 5 --warmup 2 (roofline + CPU baseline in the line)
+#   prof     bench.py under rocprofv3 --kernel-trace --stats
 set -u
 export TMPDIR=/tmp
 TAG=$1
@@ -23,7 +24,7 @@ for spec in "$@"; do
     case "$name" in
       gtests) cmd="python -u -m pytest tests -v -m gpu --timeout 300 --timeout-method thread -rA" ;;
       smoke) cmd="python -c 'import __graft_entry__ as g; g.smoke()'" ;;
-      bench) cmd="python bench.py --steps 5 --warmup 2" ;;
+      bench) cmd="python bench.py --full --steps 5 --warmup 2" ;;
       prof) cmd="rocprofv3 --kernel-trace --stats -d $OUT/prof -o bench --output-format csv -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline" ;;
       *) echo "unknown step $name"; exit 2 ;;
     esac
