@@ -26,7 +26,7 @@ extern "C" {
 #define VP_ERR_UNSUPPORTED 1001
 
 /* ABI version: bump when any struct layout or signature below changes. */
-#define VP_ABI_VERSION 20
+#define VP_ABI_VERSION 21
 int vp_abi_version(void);
 /* "<sha256 of sources + flags>:<sha256 of the compiler version>" of the build (no reference counterpart) */
 const char* vp_build_digest(void);
@@ -38,8 +38,8 @@ const char* vp_build_digest(void);
  * runs two variants on the same operands.  Returns VP_ERR_ARG for an unknown name or a value over 31 bytes.  Host
  * only; not thread-safe against launches in flight on other host threads.  (ABI 14.) */
 int vp_set_knob(const char* name, const char* value);
-/* sizeof of the descriptor structs as compiled into the library: out[0..6] = gemm, attn, dpm, gemm_mx, attn_fp8,
- * conv3d, attn_bwd (ABI check) */
+/* sizeof of the descriptor structs as compiled into the library: out[0..9] = gemm, attn, dpm, gemm_mx, attn_fp8,
+ * conv3d, attn_bwd, mt_tensor, mt_chunk, optim_scalars (ABI check) */
 void vp_struct_sizes(int64_t* out);
 
 /* ---------------------------------------------------------------------------------------------------------------
@@ -615,6 +615,84 @@ int vp_head_norm_rope_bwd_bf16(const void* x_in, int64_t ld_in, int64_t bs_in, c
                                int64_t bs_dy, void* dx, int64_t ld_dx, int64_t bs_dx, int32_t B, int32_t Ntok,
                                int32_t H, int32_t text_len, const void* ln_w, const void* ln_b, float eps,
                                const float* cos, const float* sin, float* dln_w, float* dln_b, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Training tail (ABI 21; csrc/optim.hip): the loss, the gradient norm / clip and the AdamW update of the reference's
+ * training step (train/train_cogvideox_inpainting_i2v_video.py:1879-1902 under accelerate + DeepSpeed bf16: bf16
+ * model weights, fp32 master weights and moments).  Multi-tensor kernels over a list of contiguous bf16 tensors of
+ * any sizes, described by two DEVICE tables the caller builds and uploads (asynchronously on `stream`):
+ *   tensors[t]: the gradient / parameter pointers, the element offset of the tensor's fp32 state in the flat state
+ *               buffers, and its element count;
+ *   chunks[c]:  one workgroup's work: elements [chunk * VP_MT_CHUNK, min(numel, (chunk + 1) * VP_MT_CHUNK)) of
+ *               tensors[tensor] — a chunk never crosses a tensor, an empty tensor has no chunk.
+ * 16-byte loads / stores in the body of a chunk, scalar head and tail (a chunk whose pointers do not share one
+ * 16-byte phase runs scalar as a whole); 64-bit element offsets.  No float atomics: every reduction writes one fp32
+ * partial per chunk into its own slot and a single-workgroup finaliser sums the slots in a fixed order, so results
+ * are bit-identical run to run.  No entry point reads device memory on the host or synchronises. */
+#define VP_MT_CHUNK 16384
+typedef struct {
+  void* grad;        /* bf16 [numel], contiguous */
+  void* param;       /* bf16 [numel], contiguous (vp_mt_adamw_bf16 only; NULL otherwise) */
+  int64_t state_off; /* element offset of this tensor in master / exp_avg / exp_avg_sq (vp_mt_adamw_bf16 only) */
+  int64_t numel;
+} vp_mt_tensor;
+typedef struct {
+  int32_t tensor; /* index into the tensor table */
+  int32_t chunk;  /* chunk index inside that tensor */
+} vp_mt_chunk;
+/* the device "scalars" block of one optimizer / one norm call (written by vp_optim_finalize with ordinary vector
+ * stores, read by the scale and update kernels) */
+typedef struct {
+  float grad_norm;   /* total L2 norm of the gradients (before any clip) */
+  float clip_coef;   /* min(1, max_norm / (grad_norm + 1e-6)) (torch clip_grad_norm_); 1 when max_norm <= 0 */
+  int32_t nonfinite; /* 1 when any gradient element is inf or NaN */
+  int32_t step;      /* optimizer step counter (kept across calls; incremented by the finaliser) */
+  float bias_c1;     /* 1 - beta1^step */
+  float bias_c2;     /* 1 - beta2^step */
+  int32_t skipped;   /* 1 when this step is skipped (nonfinite && skip_nonfinite): step not incremented */
+  int32_t pad;
+} vp_optim_scalars;
+/* stage 1 of the gradient norm: partials[c] = sum of squares (fp32) of chunk c, flags[c] = 1 when the chunk holds an
+ * inf / NaN (the bf16 bit pattern is tested: a finite value whose square overflows does not set it).
+ * n_chunks = 0: no launch. */
+int vp_mt_grad_sqnorm_bf16(const vp_mt_tensor* tensors, const vp_mt_chunk* chunks, int32_t n_chunks, float* partials,
+                           int32_t* flags, void* stream);
+/* stage 2 (one workgroup): grad_norm = sqrt(sum of partials[0 .. n_chunks) in a fixed order), nonfinite, clip_coef
+ * (max_norm <= 0: no clip, 1).  advance_step != 0: the optimizer's finaliser — skipped = nonfinite &&
+ * skip_nonfinite; unless skipped, ++step and bias_c1 / bias_c2 = 1 - beta^step (evaluated in double).
+ * advance_step == 0: step / bias_c* / skipped are left as they are.  n_chunks = 0 gives norm 0. */
+int vp_optim_finalize(const float* partials, const int32_t* flags, int32_t n_chunks, float max_norm, double beta1,
+                      double beta2, int32_t skip_nonfinite, int32_t advance_step, vp_optim_scalars* scalars,
+                      void* stream);
+/* grad = bf16(grad * scalars->clip_coef) in place over the tensor list (torch.nn.utils.clip_grad_norm_'s multiply);
+ * nothing is written when the coefficient is exactly 1 */
+int vp_mt_scale_bf16(const vp_mt_tensor* tensors, const vp_mt_chunk* chunks, int32_t n_chunks,
+                     const vp_optim_scalars* scalars, void* stream);
+/* torch.optim.AdamW (amsgrad = False, maximize = False) with fp32 master weights, over chunks [chunk_begin,
+ * chunk_begin + n_chunks) of the table (one call per parameter group).  Per element, in fp32: g = grad (* clip_coef
+ * when use_clip); p = master * (1 - lr * weight_decay); m += (1 - beta1) (g - m); v = beta2 v + (1 - beta2) g^2;
+ * p -= (lr / bias_c1) * m / (sqrt(v) / sqrt(bias_c2) + eps); master, exp_avg, exp_avg_sq are stored and
+ * param = bf16(p) (round to nearest even).  zero_grads: the gradient is zeroed in the same pass.  A skipped step
+ * (scalars->skipped) writes no state and no parameter (it still zeroes the gradients when asked to). */
+int vp_mt_adamw_bf16(const vp_mt_tensor* tensors, const vp_mt_chunk* chunks, int32_t chunk_begin, int32_t n_chunks,
+                     float* master, float* exp_avg, float* exp_avg_sq, const vp_optim_scalars* scalars, double lr,
+                     double beta1, double beta2, double eps, double weight_decay, int32_t use_clip,
+                     int32_t zero_grads, void* stream);
+/* y = bf16(x * *s) with the fp32 factor read on the device (the loss's backward: the incoming scalar gradient) */
+int vp_scale_dev_bf16(const void* x, void* y, int64_t n, const float* s, void* stream);
+/* The v-prediction training loss (:1879-1891), forward and gradient in one pass.  model_output, noisy, target:
+ * bf16 [B, F, C, H*W] contiguous; mask [B, F, 1, H*W] bf16 or fp32, or NULL (no inpainting term then,
+ * whatever lambda is).  Per sample b, in fp32, t = timesteps[b] (int64 on the device, clamped to [0, n_alphas)),
+ * ac = alphas_cumprod[t]: sa = sqrt(ac), sb = sqrt(1 - ac), w = 1 / (1 - ac), d = sa noisy - sb model_output - target;
+ *   *loss = mean_b mean(w d^2) + lambda mean_b mean(w (d mask)^2)
+ *   dout  = bf16(-sb w 2 d (1 + lambda mask^2) / (B numel_per_sample))
+ * partials: fp32 workspace of vp_v_loss_partials(...) slots (-1: invalid sizes); the sum runs through the same
+ * two-stage reduction (bit-identical run to run). */
+int64_t vp_v_loss_partials(int32_t B, int32_t F, int32_t C, int32_t HW);
+int vp_v_loss_bf16(const void* model_output, const void* noisy, const void* target, const void* mask,
+                   int32_t mask_is_f32, const int64_t* timesteps, const float* alphas_cumprod, int32_t n_alphas,
+                   int32_t B, int32_t F, int32_t C, int32_t HW, float lambda, float* partials, float* loss,
+                   void* dout, void* stream);
 
 
 #ifdef __cplusplus

@@ -1,0 +1,126 @@
+"""Optimizer-step time at the real branch parameter set on one MI355X: FusedAdamW against the torch equivalents.
+
+    python tools/bench_optim.py [--rounds R] [--iters N]
+
+Parameters: the trainable VideoPainter branch (5b-I2V config, num_layers=2, init_synthetic_weights_), bf16, with
+random bf16 gradients N(0, 1e-3^2); the training script's hyper-parameters (lr 1e-5, betas (0.9, 0.95), weight decay
+1e-4, max_grad_norm 1.0).  Three variants, interleaved round by round in one process:
+
+    fused      videopainter_amd.FusedAdamW(max_grad_norm=1.0).step(): norm + clip + AdamW on fp32 masters + bf16
+               write-back, on the HIP kernels (csrc/optim.hip)
+    torch_fp32 the honest torch equivalent: fp32 copies of the parameters; per step the bf16 gradients cast to the
+               fp32 copies' .grad, torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW(foreach=True) on them, and the
+               bf16 copy-back
+    torch_bf16 torch.optim.AdamW(foreach=True) directly on the bf16 parameters (no master weights: the
+               wrong-but-cheap baseline)
+
+Prints ms per step per round (HIP events around N back-to-back steps), and for `fused` the effective bandwidth
+30 B x n_params / t (norm pass: 2 B read; update pass: 14 B read + 14 B written per parameter) as a fraction of
+6.3 TB/s, with the per-kernel split (norm pass / update pass).  One JSON line at the end.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+HBM = 6.3e12
+HYP = dict(lr=1e-5, betas=(0.9, 0.95), eps=1e-8, weight_decay=1e-4)
+
+
+def timed(fn, iters):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--iters", type=int, default=10)
+    args = ap.parse_args()
+    from videopainter_amd import CogvideoXBranchModel, FusedAdamW, device_scope
+    from videopainter_amd import kernels as K
+    from videopainter_amd.config import COGVIDEOX_5B_I2V
+
+    dev = "cuda"
+    with device_scope(dev):
+        br = CogvideoXBranchModel(**dict(COGVIDEOX_5B_I2V, num_layers=2))
+    br.init_synthetic_weights_(1235)
+    br.requires_grad_(True)
+    base = [p for p in br.parameters() if p.requires_grad]
+    n_params = sum(p.numel() for p in base)
+    for i, p in enumerate(base):
+        p.grad = torch.empty_like(p)
+        K.fill_normal_(p.grad, 77 + i, 0.0, 1e-3)
+    clone = lambda: [torch.nn.Parameter(p.detach().clone()) for p in base]  # noqa: E731
+
+    def with_grads(ps):
+        for p, b in zip(ps, base):
+            p.grad = b.grad  # shared, read-only for every variant
+        return ps
+
+    pf = with_grads(clone())
+    fused = FusedAdamW(pf, **HYP, max_grad_norm=1.0)
+
+    pb = clone()  # the bf16 model of the fp32 variant
+    p32 = [torch.nn.Parameter(p.detach().float()) for p in pb]
+    opt32 = torch.optim.AdamW(p32, **HYP, foreach=True)
+
+    def torch_fp32():
+        for m, b in zip(p32, base):
+            m.grad = b.grad.float()
+        torch.nn.utils.clip_grad_norm_(p32, 1.0, foreach=True)
+        opt32.step()
+        with torch.no_grad():
+            torch._foreach_copy_(pb, p32)
+
+    p16 = with_grads(clone())
+    opt16 = torch.optim.AdamW(p16, **HYP, foreach=True)
+
+    variants = dict(fused=fused.step, torch_fp32=torch_fp32, torch_bf16=opt16.step)
+    for fn in variants.values():  # warm-up (allocations, table upload)
+        fn()
+        fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in variants}
+    for r in range(args.rounds):
+        for k, fn in variants.items():
+            ms[k].append(timed(fn, args.iters))
+        print("round %d: " % r + "  ".join(f"{k} {ms[k][-1]:.3f} ms" for k in variants), flush=True)
+
+    # the fused step's kernels one by one
+    t = fused._tables
+    norm_ms = timed(lambda: K.mt_grad_sqnorm(t.tensors, t.chunks, t.n_chunks, t.partials, t.flags), args.iters)
+    upd_ms = timed(lambda: K.mt_adamw(t.tensors, t.chunks, 0, t.n_chunks, fused._master, fused._exp_avg,
+                                      fused._exp_avg_sq, fused._scalars, lr=HYP["lr"], betas=HYP["betas"],
+                                      eps=HYP["eps"], weight_decay=HYP["weight_decay"], use_clip=True,
+                                      zero_grads=False), args.iters)
+    med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+    bw = 30.0 * n_params / (med["fused"] * 1e-3)
+    res = dict(metric="optimizer step, VideoPainter branch (5b-I2V, 2 layers), bf16 params + fp32 masters",
+               n_params=n_params, n_tensors=len(base), n_chunks=t.n_chunks, rounds=args.rounds, iters=args.iters,
+               ms=ms, median_ms=med, min_ms={k: min(v) for k, v in ms.items()},
+               max_ms={k: max(v) for k, v in ms.items()},
+               fused_gb_per_s=bw / 1e9, fused_fraction_of_6p3_tb_s=bw / HBM,
+               norm_pass_ms=norm_ms, norm_pass_gb_per_s=2.0 * n_params / (norm_ms * 1e-3) / 1e9,
+               update_pass_ms=upd_ms, update_pass_gb_per_s=28.0 * n_params / (upd_ms * 1e-3) / 1e9,
+               speedup_vs_torch_fp32=med["torch_fp32"] / med["fused"])
+    print(f"fused: {med['fused']:.3f} ms = {bw / 1e9:.0f} GB/s = {bw / HBM:.2f} of 6.3 TB/s "
+          f"(norm pass {norm_ms:.3f} ms, update pass {upd_ms:.3f} ms); torch fp32 equivalent "
+          f"{med['torch_fp32']:.3f} ms, torch on bf16 {med['torch_bf16']:.3f} ms")
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

@@ -1,13 +1,18 @@
 """Training-step throughput of the VideoPainter training path on one MI355X.
 
-    python tools/bench_train.py [--steps K] [--warmup W] [--height 60 --width 90] [--optimizer]
+    python tools/bench_train.py [--steps K] [--warmup W] [--height 60 --width 90] [--optimizer none|torch|fused]
+                                [--loss]
 
 One step = the reference's training iteration (train/train_cogvideox_inpainting_i2v_video.py:1856-1892 with the
 launch script train/VideoPainter.sh: 49 frames 480x720 -> latent 13x60x90, batch 1, bf16, branch_layer_num 2,
 --mask_add, --gradient_checkpointing): 2-layer branch forward (trainable) -> 42-layer 5b-I2V transformer forward
 (frozen) with the samples injected under the mask -> backward of a synthetic loss gradient into every branch
-parameter.  --optimizer adds torch's AdamW (foreach) on the branch parameters (PyTorch's kernels, not ours; off by
-default).  Random-init weights, synthetic latents.  Prints one JSON line.
+parameter.  --optimizer torch adds torch's AdamW (foreach) stepped directly on the bf16 branch parameters (PyTorch's
+kernels, and no master weights: most of an lr = 1e-5 update is lost below the bf16 ulp); --optimizer fused adds
+videopainter_amd.FusedAdamW(max_grad_norm=1.0): gradient norm + clip + AdamW with fp32 master weights on the HIP
+kernels (csrc/optim.hip).  --loss replaces the synthetic loss gradient with inpainting_v_loss(...).backward()
+(:1879-1892).  Default: neither.  Random-init weights, synthetic latents.  Prints one JSON line; optimizer_ms = HIP
+events around optimizer.step().
 """
 from __future__ import annotations
 
@@ -43,7 +48,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--height", type=int, default=60)
     ap.add_argument("--width", type=int, default=90)
-    ap.add_argument("--optimizer", action="store_true")
+    ap.add_argument("--optimizer", choices=("none", "torch", "fused"), default="none")
+    ap.add_argument("--loss", action="store_true",
+                    help="inpainting_v_loss(...).backward() instead of out.backward(dout)")
     ap.add_argument("--classes", action="store_true", help="per-class HIP-event timing pass afterwards")
     args = ap.parse_args()
     from videopainter_amd import CogVideoXTransformer3DModel, CogvideoXBranchModel, device_scope
@@ -61,7 +68,12 @@ def main():
     br.init_synthetic_weights_(1235)
     br.requires_grad_(True)
     params = [p for p in br.parameters() if p.requires_grad]
-    opt = torch.optim.AdamW(params, lr=1e-5, betas=(0.9, 0.95), foreach=True) if args.optimizer else None
+    opt = None
+    if args.optimizer == "torch":
+        opt = torch.optim.AdamW(params, lr=1e-5, betas=(0.9, 0.95), foreach=True)
+    elif args.optimizer == "fused":
+        from videopainter_amd import FusedAdamW
+        opt = FusedAdamW(params, lr=1e-5, betas=(0.9, 0.95), weight_decay=1e-4, max_grad_norm=1.0)
 
     g = torch.Generator().manual_seed(7)
     lat = torch.randn(1, F, 16, HL, WL, generator=g).to(dev, torch.bfloat16)
@@ -79,21 +91,34 @@ def main():
     dout = torch.randn(1, F, 16, HL, WL, generator=g).to(dev, torch.bfloat16)
     nv = F * (HL // 2) * (WL // 2)
     ntok = T + nv
+    if args.loss:
+        from videopainter_amd import CogVideoXDPMScheduler, inpainting_v_loss
+        alphas_cumprod = CogVideoXDPMScheduler().alphas_cumprod.to(dev, torch.float32)
+        target = torch.randn(1, F, 16, HL, WL, generator=g).to(dev, torch.bfloat16)
+    opt_events = []
 
     def step():
         samples = br(hidden_states=lat, encoder_hidden_states=enc, branch_cond=cond, timestep=ts,
                      image_rotary_emb=rope, return_dict=False)[0]
         out = tr(hidden_states=hidden, encoder_hidden_states=enc, timestep=ts, image_rotary_emb=rope,
                  branch_block_samples=samples, branch_block_masks=mask, return_dict=False)[0]
-        out.backward(dout)
+        if args.loss:
+            inpainting_v_loss(out, lat, target, ts, alphas_cumprod, mask, 1.0).backward()
+        else:
+            out.backward(dout)
         if opt is not None:
+            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            ev[0].record()
             opt.step()
+            ev[1].record()
+            opt_events.append(ev)
         for p in params:
             p.grad = None
 
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
+    opt_events.clear()
     t0 = time.perf_counter()
     for i in range(args.steps):
         step()
@@ -103,7 +128,10 @@ def main():
     fl = flops(ntok, nv)
     res = dict(metric="training steps/sec (VideoPainter branch, 5b-I2V frozen, 49f 480x720, B=1)",
                value=1.0 / el, unit="steps/s", ms_per_step=el * 1e3, steps=args.steps, warmup=args.warmup,
-               optimizer="torch AdamW foreach" if opt is not None else None,
+               optimizer={"none": None, "torch": "torch AdamW foreach",
+                          "fused": "FusedAdamW(max_grad_norm=1.0)"}[args.optimizer],
+               optimizer_ms=(sum(a.elapsed_time(b) for a, b in opt_events) / len(opt_events)) if opt_events else None,
+               loss="inpainting_v_loss" if args.loss else None,
                tflops_per_s=fl["total"] / el / 1e12, flop_per_step=fl, ntok=ntok,
                peak_mem_gib=torch.cuda.max_memory_allocated() / 2 ** 30)
     if args.classes:

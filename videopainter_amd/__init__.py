@@ -31,4 +31,10 @@ def __getattr__(name):
     if name in ("CogVideoXI2VDualInpaintAnyLHarness",):
         from . import pipeline
         return getattr(pipeline, name)
+    if name in ("FusedAdamW", "clip_grad_norm_", "get_gradient_norm"):
+        from . import optim
+        return getattr(optim, name)
+    if name in ("inpainting_v_loss",):
+        from . import training
+        return getattr(training, name)
     raise AttributeError(name)

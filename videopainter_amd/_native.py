@@ -11,7 +11,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VP_HIP_LIB", os.path.join(_HERE, "_lib", "libvp_hip.so"))
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 vp = C.c_void_p
 i32 = C.c_int32
@@ -85,6 +85,22 @@ class AttnBwdDesc(C.Structure):
                 ("dO", vp), ("do_sb", i64), ("do_sn", i64), ("lse", vp), ("delta", vp),
                 ("dQ", vp), ("dq_sb", i64), ("dq_sn", i64), ("dK", vp), ("dk_sb", i64), ("dk_sn", i64),
                 ("dV", vp), ("dv_sb", i64), ("dv_sn", i64), ("scale", f32), ("pad1", i32)]
+
+
+MT_CHUNK = 16384  # VP_MT_CHUNK: elements of one multi-tensor chunk (one workgroup's work)
+
+
+class MtTensor(C.Structure):
+    _fields_ = [("grad", vp), ("param", vp), ("state_off", i64), ("numel", i64)]
+
+
+class MtChunk(C.Structure):
+    _fields_ = [("tensor", i32), ("chunk", i32)]
+
+
+class OptimScalars(C.Structure):
+    _fields_ = [("grad_norm", f32), ("clip_coef", f32), ("nonfinite", i32), ("step", i32), ("bias_c1", f32),
+                ("bias_c2", f32), ("skipped", i32), ("pad", i32)]
 
 
 (EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_SCALE, EPI_GATED, EPI_BIAS_ADDROWS, EPI_BIAS_GELU_MXFP8, EPI_BIAS_QKNORM_ROPE,
@@ -165,6 +181,14 @@ _SIGS = {
     "vp_silu_bwd_bf16": (i32, [vp, vp, vp, i64, vp]),
     "vp_head_norm_rope_bwd_bf16": (i32, [vp, i64, i64, vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, vp, vp, f32, vp,
                                          vp, vp, vp, vp]),
+    "vp_mt_grad_sqnorm_bf16": (i32, [vp, vp, i32, vp, vp, vp]),
+    "vp_optim_finalize": (i32, [vp, vp, i32, f32, C.c_double, C.c_double, i32, i32, vp, vp]),
+    "vp_mt_scale_bf16": (i32, [vp, vp, i32, vp, vp]),
+    "vp_mt_adamw_bf16": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double,
+                               C.c_double, i32, i32, vp]),
+    "vp_scale_dev_bf16": (i32, [vp, vp, i64, vp, vp]),
+    "vp_v_loss_partials": (i64, [i32, i32, i32, i32]),
+    "vp_v_loss_bf16": (i32, [vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp]),
 }
 
 EXPORTS = tuple(_SIGS)
@@ -216,10 +240,11 @@ def lib():
         if src is not None and built.split(":")[0] != src:
             raise HipLibraryError(f"{LIB_PATH} was built from other sources (digest {built[:12]}.. != "
                                   f"{src[:12]}..); rebuild with `python -m videopainter_amd.build`")
-        sizes = (i64 * 7)()
+        sizes = (i64 * 10)()
         L.vp_struct_sizes(sizes)
         want = (C.sizeof(GemmDesc), C.sizeof(AttnDesc), C.sizeof(DpmDesc), C.sizeof(GemmMxDesc),
-                C.sizeof(AttnFp8Desc), C.sizeof(Conv3dDesc), C.sizeof(AttnBwdDesc))
+                C.sizeof(AttnFp8Desc), C.sizeof(Conv3dDesc), C.sizeof(AttnBwdDesc), C.sizeof(MtTensor),
+                C.sizeof(MtChunk), C.sizeof(OptimScalars))
         if tuple(sizes) != want:
             raise HipLibraryError(f"descriptor size mismatch lib={tuple(sizes)} python={want}; rebuild")
         knob_values.update({k: os.environ.get(k) for k in KNOBS})  # what the library read at load

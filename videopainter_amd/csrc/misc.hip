@@ -294,6 +294,9 @@ extern "C" void vp_struct_sizes(int64_t* out) {
   out[4] = (int64_t)sizeof(vp_attn_fp8_desc);
   out[5] = (int64_t)sizeof(vp_conv3d_desc);
   out[6] = (int64_t)sizeof(vp_attn_bwd_desc);
+  out[7] = (int64_t)sizeof(vp_mt_tensor);
+  out[8] = (int64_t)sizeof(vp_mt_chunk);
+  out[9] = (int64_t)sizeof(vp_optim_scalars);
 }
 
 // M <= 2 rows (the CFG pair's AdaLN / time-embedding vectors), K <= 512: a weight-streaming kernel.  Each wave owns

@@ -1,0 +1,464 @@
+// The tail of the training step (gfx950): the fused v-prediction loss + its gradient, the multi-tensor gradient norm /
+// clip, and AdamW with fp32 master weights behind the bf16 parameters (include/vp_hip.h "Training tail").  All of it
+// is memory-bound streaming: one workgroup per VP_MT_CHUNK elements of one tensor, 16-byte loads / stores in the
+// body, scalar head / tail.  Reductions are two-stage (a partial per chunk in its own slot, then one workgroup that
+// sums the slots in a fixed order): no float atomics, bit-identical run to run.
+#include "vp_common.h"
+
+namespace {
+
+constexpr int OT = 256;  // threads per workgroup; VP_MT_CHUNK = OT * 8 elements * 8 rounds
+static_assert(VP_MT_CHUNK % (OT * 8) == 0, "a chunk is whole rounds of 8 elements per thread");
+
+// fixed-order sum over the workgroup (xor butterfly inside a wave, then the waves in order); valid in thread 0
+VP_DEV float block_sum(float v, float* red) {
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float s = 0.f;
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int w = 0; w < OT / 64; ++w) s += red[w];
+  }
+  __syncthreads();
+  return s;
+}
+
+VP_DEV bool bf16_nonfinite(bf16 x) { return (__builtin_bit_cast(uint16_t, x) & 0x7f80u) == 0x7f80u; }
+
+// the element range of chunk c: tensor entry, first element, count
+struct ChunkRange {
+  vp_mt_tensor t;
+  int64_t start;
+  int n;
+};
+VP_DEV ChunkRange chunk_range(const vp_mt_tensor* __restrict__ tensors, const vp_mt_chunk* __restrict__ chunks,
+                              int c) {
+  const vp_mt_chunk ch = chunks[c];
+  ChunkRange r;
+  r.t = tensors[ch.tensor];
+  r.start = (int64_t)ch.chunk * VP_MT_CHUNK;
+  const int64_t left = r.t.numel - r.start;
+  r.n = left < VP_MT_CHUNK ? (left > 0 ? (int)left : 0) : VP_MT_CHUNK;
+  return r;
+}
+
+// scalar elements before p reaches a 16-byte boundary (all n when p is not even 2-byte aligned)
+VP_DEV int head_of(const void* p, int n) {
+  const uintptr_t a = (uintptr_t)p;
+  if (a & 1) return n;
+  const int h = (int)(((16 - (a & 15)) & 15) >> 1);
+  return h < n ? h : n;
+}
+
+// ---- a. squared gradient norm, stage 1 ----
+__global__ __launch_bounds__(OT) void mt_sqnorm_kernel(const vp_mt_tensor* __restrict__ tensors,
+                                                       const vp_mt_chunk* __restrict__ chunks,
+                                                       float* __restrict__ partials, int* __restrict__ flags) {
+#pragma clang fp contract(off)
+  __shared__ float red[OT / 64];
+  __shared__ int bad_any;
+  const ChunkRange r = chunk_range(tensors, chunks, blockIdx.x);
+  const bf16* g = (const bf16*)r.t.grad + r.start;
+  const int head = head_of(g, r.n);
+  const int nvec = (r.n - head) / 8;
+  float acc = 0.f;
+  bool bad = false;
+  if (threadIdx.x == 0) bad_any = 0;
+  for (int i = threadIdx.x; i < head; i += OT) {
+    const bf16 x = g[i];
+    bad |= bf16_nonfinite(x);
+    acc = __builtin_fmaf(bf2f(x), bf2f(x), acc);
+  }
+  const bf16x8* gv = (const bf16x8*)(g + head);
+  for (int i = threadIdx.x; i < nvec; i += OT) {
+    const bf16x8 v = gv[i];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      bad |= bf16_nonfinite(v[e]);
+      acc = __builtin_fmaf(bf2f(v[e]), bf2f(v[e]), acc);
+    }
+  }
+  for (int i = head + nvec * 8 + threadIdx.x; i < r.n; i += OT) {
+    const bf16 x = g[i];
+    bad |= bf16_nonfinite(x);
+    acc = __builtin_fmaf(bf2f(x), bf2f(x), acc);
+  }
+  __syncthreads();
+  if (bad) bad_any = 1;  // (every writer stores the same value)
+  const float s = block_sum(acc, red);
+  if (threadIdx.x == 0) {
+    partials[blockIdx.x] = s;
+    flags[blockIdx.x] = bad_any;
+  }
+}
+
+// ---- a. stage 2: one workgroup; thread t sums slots t, t + OT, ... in order, then the fixed block sum ----
+__global__ __launch_bounds__(OT) void optim_finalize_kernel(const float* __restrict__ partials,
+                                                            const int* __restrict__ flags, int n, float max_norm,
+                                                            double beta1, double beta2, int skip_nonfinite,
+                                                            int advance_step, vp_optim_scalars* __restrict__ sc) {
+#pragma clang fp contract(off)
+  __shared__ float red[OT / 64];
+  __shared__ int bad_any;
+  if (threadIdx.x == 0) bad_any = 0;
+  float acc = 0.f;
+  bool bad = false;
+  for (int i = threadIdx.x; i < n; i += OT) {
+    acc += partials[i];
+    bad |= flags[i] != 0;
+  }
+  __syncthreads();
+  if (bad) bad_any = 1;
+  const float s = block_sum(acc, red);
+  if (threadIdx.x != 0) return;
+  const float norm = sqrtf(s);
+  const int nonfinite = bad_any;
+  sc->grad_norm = norm;
+  sc->nonfinite = nonfinite;
+  float coef = 1.f;
+  if (max_norm > 0.f) {
+    coef = max_norm / (norm + 1e-6f);
+    coef = coef > 1.f ? 1.f : coef;  // (a NaN coefficient stays NaN, as torch.clamp keeps it)
+  }
+  sc->clip_coef = coef;
+  if (!advance_step) return;
+  const int skipped = (nonfinite && skip_nonfinite) ? 1 : 0;
+  sc->skipped = skipped;
+  if (skipped) return;
+  const int step = sc->step + 1;
+  sc->step = step;
+  sc->bias_c1 = (float)(1.0 - pow(beta1, (double)step));
+  sc->bias_c2 = (float)(1.0 - pow(beta2, (double)step));
+}
+
+// ---- b. in-place scale by the device clip coefficient ----
+__global__ __launch_bounds__(OT) void mt_scale_kernel(const vp_mt_tensor* __restrict__ tensors,
+                                                      const vp_mt_chunk* __restrict__ chunks,
+                                                      const vp_optim_scalars* __restrict__ sc) {
+  const float coef = sc->clip_coef;
+  if (coef == 1.f) return;
+  const ChunkRange r = chunk_range(tensors, chunks, blockIdx.x);
+  bf16* g = (bf16*)r.t.grad + r.start;
+  const int head = head_of(g, r.n);
+  const int nvec = (r.n - head) / 8;
+  for (int i = threadIdx.x; i < head; i += OT) g[i] = f2bf(bf2f(g[i]) * coef);
+  bf16x8* gv = (bf16x8*)(g + head);
+  for (int i = threadIdx.x; i < nvec; i += OT) {
+    bf16x8 v = gv[i];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = f2bf(bf2f(v[e]) * coef);
+    gv[i] = v;
+  }
+  for (int i = head + nvec * 8 + threadIdx.x; i < r.n; i += OT) g[i] = f2bf(bf2f(g[i]) * coef);
+}
+
+// ---- c. AdamW with fp32 master weights ----
+struct AdamArgs {
+  float lr, decay, omb1, beta2, omb2, eps;  // decay = 1 - lr * weight_decay, omb = 1 - beta
+  int use_clip, zero_grads;
+};
+
+struct AdamCoef {
+  float clip, step_size, bc2_sqrt;
+};
+
+VP_DEV void adam_element(float g, float& p, float& m, float& v, const AdamArgs& a, const AdamCoef& k) {
+  // torch.optim.adamw._single_tensor_adamw, one rounded operation per torch op (no contraction across them)
+#pragma clang fp contract(off)
+  g *= k.clip;
+  p *= a.decay;                               // param.mul_(1 - lr * weight_decay)
+  m = __builtin_fmaf(a.omb1, g - m, m);       // exp_avg.lerp_(grad, 1 - beta1)
+  v = v * a.beta2 + a.omb2 * g * g;           // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
+  const float denom = sqrtf(v) / k.bc2_sqrt + a.eps;
+  p = p - k.step_size * (m / denom);          // param.addcdiv_(exp_avg, denom, value=-step_size)
+}
+
+__global__ __launch_bounds__(OT) void mt_adamw_kernel(const vp_mt_tensor* __restrict__ tensors,
+                                                      const vp_mt_chunk* __restrict__ chunks, int chunk_begin,
+                                                      float* __restrict__ master, float* __restrict__ exp_avg,
+                                                      float* __restrict__ exp_avg_sq,
+                                                      const vp_optim_scalars* __restrict__ sc, const AdamArgs a) {
+  const ChunkRange r = chunk_range(tensors, chunks, chunk_begin + blockIdx.x);
+  bf16* g = (bf16*)r.t.grad + r.start;
+  bf16* w = (bf16*)r.t.param + r.start;
+  const int64_t so = r.t.state_off + r.start;
+  float* pm = master + so;
+  float* mm = exp_avg + so;
+  float* vm = exp_avg_sq + so;
+  // one 16-byte phase for every stream of the chunk, else the whole chunk runs scalar
+  int head = head_of(g, r.n);
+  if (head_of(w, r.n) != head || (((uintptr_t)(pm + head) | (uintptr_t)(mm + head) | (uintptr_t)(vm + head)) & 15))
+    head = r.n;
+  const int nvec = (r.n - head) / 8;
+  const int tail0 = head + nvec * 8;
+  const bf16 zero = f2bf(0.f);
+  if (sc->skipped) {  // a skipped step writes no state and no parameter
+    if (!a.zero_grads) return;
+    for (int i = threadIdx.x; i < head; i += OT) g[i] = zero;
+    bf16x8* gz = (bf16x8*)(g + head);
+    for (int i = threadIdx.x; i < nvec; i += OT) gz[i] = bf16x8{};
+    for (int i = tail0 + threadIdx.x; i < r.n; i += OT) g[i] = zero;
+    return;
+  }
+  AdamCoef k;
+  k.clip = a.use_clip ? sc->clip_coef : 1.f;
+  k.step_size = a.lr / sc->bias_c1;
+  k.bc2_sqrt = sqrtf(sc->bias_c2);
+
+  auto scalar = [&](int i) {
+    float p = pm[i], m = mm[i], v = vm[i];
+    adam_element(bf2f(g[i]), p, m, v, a, k);
+    pm[i] = p;
+    mm[i] = m;
+    vm[i] = v;
+    w[i] = f2bf(p);
+    if (a.zero_grads) g[i] = zero;
+  };
+  for (int i = threadIdx.x; i < head; i += OT) scalar(i);
+  for (int i = threadIdx.x; i < nvec; i += OT) {
+    const int o = head + i * 8;
+    const bf16x8 g8 = *(const bf16x8*)(g + o);
+    f32x4 p[2], m[2], v[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      p[h] = *(const f32x4*)(pm + o + 4 * h);
+      m[h] = *(const f32x4*)(mm + o + 4 * h);
+      v[h] = *(const f32x4*)(vm + o + 4 * h);
+    }
+    bf16x8 w8;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float pe = p[e >> 2][e & 3], me = m[e >> 2][e & 3], ve = v[e >> 2][e & 3];
+      adam_element(bf2f(g8[e]), pe, me, ve, a, k);
+      p[e >> 2][e & 3] = pe;
+      m[e >> 2][e & 3] = me;
+      v[e >> 2][e & 3] = ve;
+      w8[e] = f2bf(pe);
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      *(f32x4*)(pm + o + 4 * h) = p[h];
+      *(f32x4*)(mm + o + 4 * h) = m[h];
+      *(f32x4*)(vm + o + 4 * h) = v[h];
+    }
+    *(bf16x8*)(w + o) = w8;
+    if (a.zero_grads) *(bf16x8*)(g + o) = bf16x8{};
+  }
+  for (int i = tail0 + threadIdx.x; i < r.n; i += OT) scalar(i);
+}
+
+// ---- y = bf16(x * *s) ----
+__global__ __launch_bounds__(OT) void scale_dev_kernel(const bf16* __restrict__ x, bf16* __restrict__ y, int64_t n,
+                                                       const float* __restrict__ s) {
+  const float c = *s;
+  const bool vec = (((uintptr_t)x | (uintptr_t)y) & 15) == 0;
+  const int64_t nvec = vec ? n / 8 : 0;
+  const int64_t stride = (int64_t)gridDim.x * OT;
+  const int64_t tid = (int64_t)blockIdx.x * OT + threadIdx.x;
+  for (int64_t i = tid; i < nvec; i += stride) {
+    bf16x8 v = ((const bf16x8*)x)[i];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = f2bf(bf2f(v[e]) * c);
+    ((bf16x8*)y)[i] = v;
+  }
+  for (int64_t i = nvec * 8 + tid; i < n; i += stride) y[i] = f2bf(bf2f(x[i]) * c);
+}
+
+// ---- d. the v-prediction loss and its gradient ----
+struct LossArgs {
+  const bf16* out;
+  const bf16* noisy;
+  const bf16* target;
+  const void* mask;
+  int mask_is_f32;
+  const int64_t* timesteps;
+  const float* ac;
+  int n_alphas, F, C, HW;
+  int64_t n_sample;  // F * C * HW < 2^31
+  int chunks_per_sample;
+  float lambda, inv_total;  // 1 / (B * n_sample)
+  float* partials;
+  bf16* dout;
+};
+
+VP_DEV float loss_element(float o, float x, float t, float mk, float sa, float sb, float lambda, float gc, float& q,
+                          float& qm) {
+#pragma clang fp contract(off)
+  const float d = (sa * x - sb * o) - t;
+  const float dm = d * mk;
+  q += d * d;
+  qm += dm * dm;
+  return gc * d * (1.f + lambda * (mk * mk));
+}
+
+__global__ __launch_bounds__(OT) void v_loss_kernel(const LossArgs a) {
+#pragma clang fp contract(off)
+  __shared__ float red[OT / 64];
+  const int b = blockIdx.y;
+  int64_t t = a.timesteps[b];
+  t = t < 0 ? 0 : (t >= a.n_alphas ? a.n_alphas - 1 : t);
+  const float ac = a.ac[t];
+  const float sa = sqrtf(ac), sb = sqrtf(1.f - ac), w = 1.f / (1.f - ac);
+  const float gc = -2.f * sb * w * a.inv_total;
+  const bool masked = a.mask != nullptr;
+  const float lambda = masked ? a.lambda : 0.f;
+  const int start = blockIdx.x * VP_MT_CHUNK;  // inside the sample (n_sample < 2^31)
+  const int64_t left = a.n_sample - start;
+  const int n = left < VP_MT_CHUNK ? (int)left : VP_MT_CHUNK;
+  const int64_t base = (int64_t)b * a.n_sample + start;
+  const bf16* po = a.out + base;
+  const bf16* px = a.noisy + base;
+  const bf16* pt = a.target + base;
+  bf16* pd = a.dout + base;
+  int head = head_of(po, n);
+  if (head_of(px, n) != head || head_of(pt, n) != head || head_of(pd, n) != head) head = n;
+  const int nvec = (n - head) / 8;
+  const int CHW = a.C * a.HW;
+  const int64_t mbase = (int64_t)b * a.F * a.HW;
+  auto mask_at = [&](int i) -> float {  // i: element inside the sample
+    if (!masked) return 0.f;
+    const int64_t mi = mbase + (int64_t)(i / CHW) * a.HW + (i % a.HW);
+    return a.mask_is_f32 ? ((const float*)a.mask)[mi] : bf2f(((const bf16*)a.mask)[mi]);
+  };
+  float q = 0.f, qm = 0.f;
+  auto scalar = [&](int i) {
+    pd[i] = f2bf(loss_element(bf2f(po[i]), bf2f(px[i]), bf2f(pt[i]), mask_at(start + i), sa, sb, lambda, gc, q, qm));
+  };
+  for (int i = threadIdx.x; i < head; i += OT) scalar(i);
+  for (int i = threadIdx.x; i < nvec; i += OT) {
+    const int o = head + i * 8;
+    const bf16x8 o8 = *(const bf16x8*)(po + o);
+    const bf16x8 x8 = *(const bf16x8*)(px + o);
+    const bf16x8 t8 = *(const bf16x8*)(pt + o);
+    bf16x8 d8;
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      d8[e] = f2bf(loss_element(bf2f(o8[e]), bf2f(x8[e]), bf2f(t8[e]), mask_at(start + o + e), sa, sb, lambda, gc, q,
+                                qm));
+    *(bf16x8*)(pd + o) = d8;
+  }
+  for (int i = head + nvec * 8 + threadIdx.x; i < n; i += OT) scalar(i);
+  const float s = block_sum(w * (q + lambda * qm), red);
+  if (threadIdx.x == 0) a.partials[(int64_t)b * a.chunks_per_sample + blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(OT) void sum_partials_kernel(const float* __restrict__ partials, int64_t n, float scale,
+                                                          float* __restrict__ out) {
+#pragma clang fp contract(off)
+  __shared__ float red[OT / 64];
+  float acc = 0.f;
+  for (int64_t i = threadIdx.x; i < n; i += OT) acc += partials[i];
+  const float s = block_sum(acc, red);
+  if (threadIdx.x == 0) out[0] = s * scale;
+}
+
+}  // namespace
+
+extern "C" int vp_mt_grad_sqnorm_bf16(const vp_mt_tensor* tensors, const vp_mt_chunk* chunks, int32_t n_chunks,
+                                      float* partials, int32_t* flags, void* stream) {
+  if (n_chunks < 0) return VP_ERR_ARG;
+  if (n_chunks == 0) return VP_OK;
+  if (!tensors || !chunks || !partials || !flags) return VP_ERR_ARG;
+  hipLaunchKernelGGL(mt_sqnorm_kernel, dim3(n_chunks), dim3(OT), 0, (hipStream_t)stream, tensors, chunks, partials,
+                     flags);
+  VP_CHECK_LAUNCH();
+  return VP_OK;
+}
+
+extern "C" int vp_optim_finalize(const float* partials, const int32_t* flags, int32_t n_chunks, float max_norm,
+                                 double beta1, double beta2, int32_t skip_nonfinite, int32_t advance_step,
+                                 vp_optim_scalars* scalars, void* stream) {
+  if (!scalars || n_chunks < 0 || (n_chunks > 0 && (!partials || !flags))) return VP_ERR_ARG;
+  if (max_norm != max_norm) return VP_ERR_ARG;
+  if (advance_step && !(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0)) return VP_ERR_ARG;
+  hipLaunchKernelGGL(optim_finalize_kernel, dim3(1), dim3(OT), 0, (hipStream_t)stream, partials, flags, n_chunks,
+                     max_norm, beta1, beta2, skip_nonfinite, advance_step, scalars);
+  VP_CHECK_LAUNCH();
+  return VP_OK;
+}
+
+extern "C" int vp_mt_scale_bf16(const vp_mt_tensor* tensors, const vp_mt_chunk* chunks, int32_t n_chunks,
+                                const vp_optim_scalars* scalars, void* stream) {
+  if (n_chunks < 0 || !scalars) return VP_ERR_ARG;
+  if (n_chunks == 0) return VP_OK;
+  if (!tensors || !chunks) return VP_ERR_ARG;
+  hipLaunchKernelGGL(mt_scale_kernel, dim3(n_chunks), dim3(OT), 0, (hipStream_t)stream, tensors, chunks, scalars);
+  VP_CHECK_LAUNCH();
+  return VP_OK;
+}
+
+extern "C" int vp_mt_adamw_bf16(const vp_mt_tensor* tensors, const vp_mt_chunk* chunks, int32_t chunk_begin,
+                                int32_t n_chunks, float* master, float* exp_avg, float* exp_avg_sq,
+                                const vp_optim_scalars* scalars, double lr, double beta1, double beta2, double eps,
+                                double weight_decay, int32_t use_clip, int32_t zero_grads, void* stream) {
+  if (n_chunks < 0 || chunk_begin < 0 || !scalars || !master || !exp_avg || !exp_avg_sq) return VP_ERR_ARG;
+  if (!(lr >= 0.0) || !(eps >= 0.0) || !(weight_decay >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) ||
+      !(beta2 >= 0.0 && beta2 < 1.0))
+    return VP_ERR_ARG;
+  if (n_chunks == 0) return VP_OK;
+  if (!tensors || !chunks) return VP_ERR_ARG;
+  AdamArgs a;
+  a.lr = (float)lr;
+  a.decay = (float)(1.0 - lr * weight_decay);
+  a.omb1 = (float)(1.0 - beta1);
+  a.beta2 = (float)beta2;
+  a.omb2 = (float)(1.0 - beta2);
+  a.eps = (float)eps;
+  a.use_clip = use_clip;
+  a.zero_grads = zero_grads;
+  hipLaunchKernelGGL(mt_adamw_kernel, dim3(n_chunks), dim3(OT), 0, (hipStream_t)stream, tensors, chunks, chunk_begin,
+                     master, exp_avg, exp_avg_sq, scalars, a);
+  VP_CHECK_LAUNCH();
+  return VP_OK;
+}
+
+extern "C" int vp_scale_dev_bf16(const void* x, void* y, int64_t n, const float* s, void* stream) {
+  if (!x || !y || !s || n <= 0) return VP_ERR_ARG;
+  const int64_t want = (n / 8 + OT - 1) / OT + 1;
+  hipLaunchKernelGGL(scale_dev_kernel, dim3((unsigned)(want < 2048 ? want : 2048)), dim3(OT), 0, (hipStream_t)stream,
+                     (const bf16*)x, (bf16*)y, n, s);
+  VP_CHECK_LAUNCH();
+  return VP_OK;
+}
+
+extern "C" int64_t vp_v_loss_partials(int32_t B, int32_t F, int32_t C, int32_t HW) {
+  if (B <= 0 || F <= 0 || C <= 0 || HW <= 0 || B > 65535) return -1;
+  const int64_t n = (int64_t)F * C * HW;
+  if (n > 0x7fffffffll - VP_MT_CHUNK) return -1;
+  return (int64_t)B * ((n + VP_MT_CHUNK - 1) / VP_MT_CHUNK);
+}
+
+extern "C" int vp_v_loss_bf16(const void* model_output, const void* noisy, const void* target, const void* mask,
+                              int32_t mask_is_f32, const int64_t* timesteps, const float* alphas_cumprod,
+                              int32_t n_alphas, int32_t B, int32_t F, int32_t C, int32_t HW, float lambda,
+                              float* partials, float* loss, void* dout, void* stream) {
+  const int64_t slots = vp_v_loss_partials(B, F, C, HW);
+  if (slots < 0 || !model_output || !noisy || !target || !timesteps || !alphas_cumprod || n_alphas <= 0 ||
+      !partials || !loss || !dout || lambda != lambda)
+    return VP_ERR_ARG;
+  LossArgs a;
+  a.out = (const bf16*)model_output;
+  a.noisy = (const bf16*)noisy;
+  a.target = (const bf16*)target;
+  a.mask = mask;
+  a.mask_is_f32 = mask_is_f32;
+  a.timesteps = timesteps;
+  a.ac = alphas_cumprod;
+  a.n_alphas = n_alphas;
+  a.F = F;
+  a.C = C;
+  a.HW = HW;
+  a.n_sample = (int64_t)F * C * HW;
+  a.chunks_per_sample = (int)(slots / B);
+  a.lambda = lambda;
+  a.inv_total = (float)(1.0 / ((double)B * (double)a.n_sample));
+  a.partials = partials;
+  a.dout = (bf16*)dout;
+  hipLaunchKernelGGL(v_loss_kernel, dim3(a.chunks_per_sample, B), dim3(OT), 0, (hipStream_t)stream, a);
+  VP_CHECK_LAUNCH();
+  hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(OT), 0, (hipStream_t)stream, (const float*)partials, slots,
+                     a.inv_total, loss);
+  VP_CHECK_LAUNCH();
+  return VP_OK;
+}

@@ -1317,3 +1317,103 @@ def wgrad(dy: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
     out = torch.empty(dyt.shape[0], xt.shape[0], device=dy.device, dtype=BF16)
     gemm(dyt, [xt], [None], out)
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# training tail: loss, gradient norm / clip, AdamW with fp32 master weights (csrc/optim.hip; videopainter_amd/optim.py
+# builds the device tables these take)
+# ------------------------------------------------------------------------------------------------------------------
+
+MT_CHUNK = N.MT_CHUNK
+
+
+def mt_grad_sqnorm(tensors: torch.Tensor, chunks: torch.Tensor, n_chunks: int, partials: torch.Tensor,
+                   flags: torch.Tensor) -> None:
+    """Stage 1 of the gradient norm over the device tables `tensors` / `chunks` (optim.MultiTensorTables): one fp32
+    sum of squares and one non-finite flag per chunk."""
+    _chk(partials, "partials", torch.float32)
+    _chk(flags, "flags", torch.int32)
+    if partials.numel() < n_chunks or flags.numel() < n_chunks:
+        raise ValueError("mt_grad_sqnorm: partials / flags hold fewer than n_chunks slots")
+    N.check(N.lib().vp_mt_grad_sqnorm_bf16(_p(tensors), _p(chunks), n_chunks, _p(partials), _p(flags), _stream()),
+            "vp_mt_grad_sqnorm_bf16")
+
+
+def optim_finalize(partials: torch.Tensor, flags: torch.Tensor, n_chunks: int, scalars: torch.Tensor, *,
+                   max_norm: float = 0.0, betas=(0.0, 0.0), skip_nonfinite: bool = False,
+                   advance_step: bool = False) -> None:
+    """Stage 2: the norm, the non-finite flag, the clip coefficient and (advance_step) the step counter and bias
+    corrections into the int32[8] `scalars` block (N.OptimScalars)."""
+    _chk(scalars, "scalars", torch.int32)
+    if scalars.numel() * 4 < C.sizeof(N.OptimScalars):
+        raise ValueError("optim_finalize: scalars block too small")
+    N.check(N.lib().vp_optim_finalize(_p(partials), _p(flags), n_chunks, max_norm, betas[0], betas[1],
+                                      int(skip_nonfinite), int(advance_step), _p(scalars), _stream()),
+            "vp_optim_finalize")
+
+
+def mt_scale(tensors: torch.Tensor, chunks: torch.Tensor, n_chunks: int, scalars: torch.Tensor) -> None:
+    """grad = bf16(grad * clip_coef) in place over the tables' gradients (clip_coef on the device, in `scalars`)."""
+    _chk(scalars, "scalars", torch.int32)
+    N.check(N.lib().vp_mt_scale_bf16(_p(tensors), _p(chunks), n_chunks, _p(scalars), _stream()), "vp_mt_scale_bf16")
+
+
+def mt_adamw(tensors: torch.Tensor, chunks: torch.Tensor, chunk_begin: int, n_chunks: int, master: torch.Tensor,
+             exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, scalars: torch.Tensor, *, lr: float, betas, eps: float,
+             weight_decay: float, use_clip: bool, zero_grads: bool) -> None:
+    """The AdamW update of chunks [chunk_begin, chunk_begin + n_chunks) (one parameter group)."""
+    for t, n in ((master, "master"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+        _chk(t, n, torch.float32)
+    _chk(scalars, "scalars", torch.int32)
+    N.check(N.lib().vp_mt_adamw_bf16(_p(tensors), _p(chunks), chunk_begin, n_chunks, _p(master), _p(exp_avg),
+                                     _p(exp_avg_sq), _p(scalars), lr, betas[0], betas[1], eps, weight_decay,
+                                     int(use_clip), int(zero_grads), _stream()), "vp_mt_adamw_bf16")
+
+
+def scale(x: torch.Tensor, s: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """bf16(x * s) with s a one-element fp32 DEVICE tensor (no host read)."""
+    _flat(x, "x")
+    _chk(s, "s", torch.float32)
+    if s.numel() != 1:
+        raise ValueError("scale: s must hold one element")
+    out = torch.empty_like(x) if out is None else out
+    _flat(out, "out")
+    if out.numel() != x.numel():
+        raise ValueError("scale: size mismatch")
+    if x.numel():
+        N.check(N.lib().vp_scale_dev_bf16(_p(x), _p(out), x.numel(), _p(s), _stream()), "vp_scale_dev_bf16")
+    return out
+
+
+def v_loss(model_output: torch.Tensor, noisy: torch.Tensor, target: torch.Tensor, timesteps: torch.Tensor,
+           alphas_cumprod: torch.Tensor, mask: Optional[torch.Tensor], lam: float):
+    """The v-prediction training loss and its gradient w.r.t. model_output in one pass: (fp32 0-dim loss, bf16 dout).
+    model_output / noisy / target bf16 [B, F, C, H, W] contiguous, mask [B, F, 1, H, W] bf16 / fp32 or None,
+    timesteps int64 [B] and alphas_cumprod fp32 [T] on the device."""
+    for t, n in ((model_output, "model_output"), (noisy, "noisy_latents"), (target, "target")):
+        _flat(t, n)
+        if t.dim() != 5 or t.shape != model_output.shape:
+            raise ValueError(f"{n} must be [B, F, C, H, W] like model_output")
+    B, F, Cc, H, W = model_output.shape
+    _chk(timesteps, "timesteps", torch.int64)
+    _chk(alphas_cumprod, "alphas_cumprod", torch.float32)
+    if timesteps.shape != (B,) or not timesteps.is_contiguous():
+        raise ValueError("timesteps must be a contiguous [B] tensor")
+    if alphas_cumprod.dim() != 1 or not alphas_cumprod.is_contiguous():
+        raise ValueError("alphas_cumprod must be a contiguous 1-D table")
+    if mask is not None:
+        if not mask.is_cuda or mask.dtype not in (torch.float32, BF16):
+            raise TypeError("mask must be a float32 / bfloat16 device tensor")
+        if mask.shape != (B, F, 1, H, W) or not mask.is_contiguous():
+            raise ValueError("mask must be contiguous [B, F, 1, H, W]")
+    slots = N.lib().vp_v_loss_partials(B, F, Cc, H * W)
+    if slots < 0:
+        raise ValueError("v_loss: unsupported sizes")
+    partials = torch.empty(slots, device=model_output.device, dtype=torch.float32)
+    loss = torch.empty((), device=model_output.device, dtype=torch.float32)
+    dout = torch.empty_like(model_output)
+    N.check(N.lib().vp_v_loss_bf16(_p(model_output), _p(noisy), _p(target), _p(mask),
+                                   int(mask is not None and mask.dtype == torch.float32), _p(timesteps),
+                                   _p(alphas_cumprod), alphas_cumprod.numel(), B, F, Cc, H * W, float(lam),
+                                   _p(partials), _p(loss), _p(dout), _stream()), "vp_v_loss_bf16")
+    return loss, dout

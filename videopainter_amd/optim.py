@@ -1,0 +1,355 @@
+"""The optimizer tail of the training step on the HIP kernels (csrc/optim.hip): gradient norm, clip, and AdamW with
+fp32 master weights behind the bf16 parameters.
+
+The reference trains under accelerate + DeepSpeed bf16 (train/VideoPainter.sh: --mixed_precision bf16 --optimizer
+AdamW --learning_rate 1e-5 --max_grad_norm 1.0), which keeps fp32 master weights and fp32 moments behind the bf16
+model.  This package's branch parameters are bf16 device tensors with bf16 gradients; stepping a plain optimizer on
+them loses most of an lr = 1e-5 update below half a bf16 ulp.  `FusedAdamW` owns the fp32 masters and moments and
+writes the bf16 parameters back every step.
+
+    FusedAdamW(params, ..., max_grad_norm=1.0)   norm + clip + update in three launches (people who own their loop)
+    clip_grad_norm_(parameters, max_norm)        norm + in-place scale (accelerator.clip_grad_norm_'s job, :1897)
+    get_gradient_norm(parameters)                norm only (the script's helper, :80-90, without its host loop)
+
+Nothing here copies device memory to the host or synchronises: the norm, the clip coefficient, the non-finite flag,
+the step counter and the bias corrections live in a small device block the kernels read.
+"""
+from __future__ import annotations
+
+from typing import Iterable, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _native as N
+
+BF16 = torch.bfloat16
+CHUNK = N.MT_CHUNK
+_STATE_ALIGN = 8  # elements: every tensor's fp32 state starts on a 16-byte boundary of the flat buffers
+
+
+def build_chunk_table(numels: Sequence[int], chunk: int = CHUNK) -> np.ndarray:
+    """int32 [n_chunks, 2] rows (tensor index, chunk index inside the tensor) — N.MtChunk.  Chunk c of tensor t covers
+    elements [c * chunk, min(numel_t, (c + 1) * chunk)): every element exactly once, no chunk crosses a tensor, an
+    empty tensor has no chunk."""
+    rows = []
+    for t, n in enumerate(numels):
+        n = int(n)
+        if n < 0:
+            raise ValueError("negative tensor size")
+        k = (n + chunk - 1) // chunk
+        if k:
+            rows.append(np.stack((np.full(k, t, dtype=np.int32), np.arange(k, dtype=np.int32)), 1))
+    return np.concatenate(rows, 0) if rows else np.zeros((0, 2), dtype=np.int32)
+
+
+def build_tensor_table(grad_ptrs: Sequence[int], param_ptrs: Sequence[int], state_offs: Sequence[int],
+                       numels: Sequence[int]) -> np.ndarray:
+    """int64 [n, 4] rows (grad pointer, param pointer, state offset, numel) — N.MtTensor."""
+    return np.array([grad_ptrs, param_ptrs, state_offs, numels], dtype=np.int64).T.reshape(len(numels), 4).copy()
+
+
+def _check_grad(g: torch.Tensor, what: str) -> None:
+    if g.is_sparse:
+        raise ValueError(f"{what}: sparse gradients are not supported")
+    if g.dtype != BF16:
+        raise TypeError(f"{what} must be torch.bfloat16, got {g.dtype}")
+    if not g.is_cuda:
+        raise ValueError(f"{what} must be a device tensor")
+    if not g.is_contiguous():
+        raise ValueError(f"{what} must be contiguous")
+
+
+class MultiTensorTables:
+    """The device tables (tensor table + chunk table) of a list of gradients, and the reduction workspace.
+
+    The tables are rebuilt on the host and uploaded (one asynchronous copy from pinned memory, on the current stream)
+    only when a pointer, a size or the set of tensors changed since the last call — so persistent `.grad` tensors
+    cost nothing per step, and gradients reallocated every step (`p.grad = None`, `zero_grad(set_to_none=True)`)
+    cost one small copy."""
+
+    def __init__(self, device: torch.device):
+        self.device = device
+        self.key = None
+        self.buf = None  # uint8 device buffer: tensor table, then chunk table
+        self.n_tensors = 0
+        self.n_chunks = 0
+        self.partials = None
+        self.flags = None
+        self.numels: List[int] = []
+
+    def update(self, grads: Sequence[torch.Tensor], params: Optional[Sequence[torch.Tensor]] = None,
+               state_offs: Optional[Sequence[int]] = None) -> None:
+        gp = [g.data_ptr() for g in grads]
+        pp = [p.data_ptr() for p in params] if params is not None else [0] * len(gp)
+        so = list(state_offs) if state_offs is not None else [0] * len(gp)
+        ne = [g.numel() for g in grads]
+        key = (tuple(gp), tuple(pp), tuple(so), tuple(ne))
+        if key == self.key:
+            return
+        tt = build_tensor_table(gp, pp, so, ne)
+        ct = build_chunk_table(ne)
+        if len(ne) >= 2 ** 31 or ct.shape[0] >= 2 ** 31:
+            raise ValueError("too many tensors / chunks")
+        host = np.concatenate((tt.view(np.uint8).reshape(-1), ct.view(np.uint8).reshape(-1)))
+        nbytes = host.size
+        if nbytes:
+            if self.buf is None or self.buf.numel() < nbytes:
+                self.buf = torch.empty(max(nbytes, 4096), device=self.device, dtype=torch.uint8)
+            pinned = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+            pinned.copy_(torch.from_numpy(host))
+            self.buf[:nbytes].copy_(pinned, non_blocking=True)
+        self.n_tensors, self.n_chunks, self.numels = len(ne), int(ct.shape[0]), ne
+        if self.partials is None or self.partials.numel() < self.n_chunks:
+            self.partials = torch.empty(max(self.n_chunks, 1024), device=self.device, dtype=torch.float32)
+            self.flags = torch.empty(max(self.n_chunks, 1024), device=self.device, dtype=torch.int32)
+        self.key = key
+
+    @property
+    def tensors(self) -> Optional[torch.Tensor]:
+        return self.buf
+
+    @property
+    def chunks(self) -> Optional[torch.Tensor]:
+        return None if self.buf is None else self.buf[self.n_tensors * 32:]
+
+    def chunks_of(self, first_tensor: int, n: int):
+        """(first chunk, chunk count) of tensors [first_tensor, first_tensor + n) of the list."""
+        per = [(x + CHUNK - 1) // CHUNK for x in self.numels]
+        return sum(per[:first_tensor]), sum(per[first_tensor:first_tensor + n])
+
+
+_TABLES: dict = {}  # device -> MultiTensorTables of the functional API
+
+
+def _grads_of(parameters) -> List[torch.Tensor]:
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    grads = [p.grad for p in parameters if p.grad is not None]
+    for g in grads:
+        _check_grad(g, "gradient")
+    if len({g.device for g in grads}) > 1:
+        raise ValueError("gradients on more than one device")
+    return grads
+
+
+def _norm_into(tables: MultiTensorTables, scalars: torch.Tensor, max_norm: float) -> None:
+    from . import kernels as K
+    K.mt_grad_sqnorm(tables.tensors, tables.chunks, tables.n_chunks, tables.partials, tables.flags)
+    K.optim_finalize(tables.partials, tables.flags, tables.n_chunks, scalars, max_norm=max_norm)
+
+
+def _functional(parameters, max_norm: float, scale: bool) -> torch.Tensor:
+    grads = _grads_of(parameters)
+    if not grads:
+        return torch.zeros(())
+    dev = grads[0].device
+    tables = _TABLES.get(dev)
+    if tables is None:
+        tables = _TABLES[dev] = MultiTensorTables(dev)
+    with torch.cuda.device(dev):
+        tables.update(grads)
+        scalars = torch.zeros(8, device=dev, dtype=torch.int32)
+        _norm_into(tables, scalars, max_norm)
+        if scale:
+            from . import kernels as K
+            K.mt_scale(tables.tensors, tables.chunks, tables.n_chunks, scalars)
+    return scalars.view(torch.float32)[0]
+
+
+def get_gradient_norm(parameters) -> torch.Tensor:
+    """Total L2 norm of the bf16 gradients of `parameters` as a 0-dim fp32 DEVICE tensor (no host read; the
+    reference's helper, train_cogvideox_inpainting_i2v_video.py:80-90, reads one .item() per parameter)."""
+    return _functional(parameters, 0.0, False)
+
+
+def clip_grad_norm_(parameters, max_norm: float, norm_type: float = 2.0) -> torch.Tensor:
+    """torch.nn.utils.clip_grad_norm_ on the HIP kernels: grads *= min(1, max_norm / (norm + 1e-6)) in place (bf16
+    rounding of each product), the total norm returned as a 0-dim fp32 device tensor.  Gradients are not touched at
+    all when the coefficient is 1."""
+    if float(norm_type) != 2.0:
+        raise ValueError("clip_grad_norm_: only the L2 norm is implemented")
+    max_norm = float(max_norm)
+    if not max_norm > 0.0:
+        raise ValueError("clip_grad_norm_: max_norm must be positive")
+    return _functional(parameters, max_norm, True)
+
+
+class FusedAdamW(torch.optim.Optimizer):
+    """torch.optim.AdamW (amsgrad=False, maximize=False) for bf16 device parameters with fp32 master weights.
+
+    State lives in three flat fp32 device buffers (master, exp_avg, exp_avg_sq); `state[p]` exposes per-parameter
+    views of them plus the shared device step counter.  Masters start as the fp32 value of the bf16 parameters.
+    `step()` is three kinds of launches — gradient norm, its finaliser, one update per parameter group — with no
+    device-to-host copy and no synchronisation; `grad_norm` (before the clip), `clip_coef` and `last_step_skipped`
+    are device tensors.
+
+      max_grad_norm   fold clip_grad_norm_(max_grad_norm) into the update.  The gradients themselves are left
+                      UNSCALED (the update multiplies by the coefficient in fp32, without the bf16 rounding a separate
+                      clip pass would add).
+      skip_nonfinite  when any gradient element is inf / NaN the step changes no parameter, no state and not the
+                      step counter, and `last_step_skipped` is 1.
+      zero_grads      zero the gradients (in place, same storage) in the update pass — also in a skipped step.
+
+    Differences from torch's: one step counter for the whole optimizer (a parameter whose grad was None in some
+    step shares the others' bias correction); betas must be the same in every parameter group (lr, weight_decay and
+    eps may differ); parameters must be bf16, contiguous, on one device; amsgrad / maximize / foreach / capturable do
+    not exist.  `load_state_dict` restores masters, moments and the step counter and leaves the bf16 parameters as
+    they are (a checkpoint's model weights are bf16(master) already)."""
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
+                 *, max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, zero_grads: bool = False):
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError(f"Invalid betas: {betas}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError(f"Invalid max_grad_norm: {max_grad_norm}")
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay))
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.zero_grads = bool(zero_grads)
+        # validate everything before the first device allocation
+        self._params = [p for g in self.param_groups for p in g["params"] if p.requires_grad]
+        if not self._params:
+            raise ValueError("FusedAdamW: no parameter requires a gradient")
+        for p in self._params:
+            if p.dtype != BF16:
+                raise TypeError(f"FusedAdamW parameters must be torch.bfloat16, got {p.dtype}")
+            if p.layout != torch.strided or not p.is_contiguous():
+                raise ValueError("FusedAdamW parameters must be dense and contiguous")
+            if p.grad is not None and p.grad.is_sparse:
+                raise ValueError("FusedAdamW does not support sparse gradients")
+        if not all(p.is_cuda for p in self._params):
+            raise ValueError("FusedAdamW parameters must be device tensors")
+        if len({p.device for p in self._params}) > 1:
+            raise ValueError("FusedAdamW parameters must be on one device")
+        dev = self._params[0].device
+        self._offs, total = {}, 0
+        for p in self._params:
+            self._offs[p] = total
+            total += (p.numel() + _STATE_ALIGN - 1) // _STATE_ALIGN * _STATE_ALIGN
+        self._master = torch.zeros(max(total, 1), device=dev, dtype=torch.float32)
+        self._exp_avg = torch.zeros_like(self._master)
+        self._exp_avg_sq = torch.zeros_like(self._master)
+        self._scalars = torch.zeros(8, device=dev, dtype=torch.int32)  # N.OptimScalars
+        self._scalars_f = self._scalars.view(torch.float32)
+        self._tables = MultiTensorTables(dev)
+        with torch.no_grad():
+            for p in self._params:
+                o, n = self._offs[p], p.numel()
+                self._master[o:o + n].copy_(p.detach().reshape(-1))
+                self.state[p] = dict(step=self._scalars[3], master=self._master[o:o + n].view(p.shape),
+                                     exp_avg=self._exp_avg[o:o + n].view(p.shape),
+                                     exp_avg_sq=self._exp_avg_sq[o:o + n].view(p.shape))
+
+    # the device scalars of the last step
+    @property
+    def grad_norm(self) -> torch.Tensor:
+        return self._scalars_f[0]
+
+    @property
+    def clip_coef(self) -> torch.Tensor:
+        return self._scalars_f[1]
+
+    @property
+    def nonfinite(self) -> torch.Tensor:
+        return self._scalars[2]
+
+    @property
+    def step_count(self) -> torch.Tensor:
+        return self._scalars[3]
+
+    @property
+    def last_step_skipped(self) -> torch.Tensor:
+        return self._scalars[6]
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        from . import kernels as K
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        betas = self.param_groups[0]["betas"]
+        grads, params, offs, counts = [], [], [], []
+        for group in self.param_groups:
+            if tuple(group["betas"]) != tuple(betas):
+                raise ValueError("FusedAdamW: betas must be the same in every parameter group")
+            n = 0
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                if p not in self._offs:
+                    raise ValueError("FusedAdamW: a parameter that did not require a gradient at construction has one")
+                _check_grad(p.grad, "gradient")
+                grads.append(p.grad)
+                params.append(p)
+                offs.append(self._offs[p])
+                n += 1
+            counts.append(n)
+        t = self._tables
+        with torch.cuda.device(self._master.device):
+            t.update(grads, params, offs)
+            K.mt_grad_sqnorm(t.tensors, t.chunks, t.n_chunks, t.partials, t.flags)
+            K.optim_finalize(t.partials, t.flags, t.n_chunks, self._scalars, max_norm=self.max_grad_norm or 0.0,
+                             betas=betas, skip_nonfinite=self.skip_nonfinite, advance_step=True)
+            first = 0
+            for group, n in zip(self.param_groups, counts):
+                c0, nc = t.chunks_of(first, n)
+                first += n
+                K.mt_adamw(t.tensors, t.chunks, c0, nc, self._master, self._exp_avg, self._exp_avg_sq, self._scalars,
+                           lr=float(group["lr"]), betas=betas, eps=float(group["eps"]),
+                           weight_decay=float(group["weight_decay"]), use_clip=self.max_grad_norm is not None,
+                           zero_grads=self.zero_grads)
+        return loss
+
+    def _indexed(self):
+        i = 0
+        for g in self.param_groups:
+            for p in g["params"]:
+                yield i, p
+                i += 1
+
+    def state_dict(self):
+        """{"state": {index: {master, exp_avg, exp_avg_sq}}, "param_groups": [...], "step": int} — clones; reading
+        the step counter is the one device-to-host copy of this class (not on the step path)."""
+        groups, i = [], 0
+        for g in self.param_groups:
+            d = {k: v for k, v in g.items() if k != "params"}
+            d["params"] = list(range(i, i + len(g["params"])))
+            i += len(g["params"])
+            groups.append(d)
+        state = {i: {k: self.state[p][k].detach().clone() for k in ("master", "exp_avg", "exp_avg_sq")}
+                 for i, p in self._indexed() if p in self._offs}
+        return {"state": state, "param_groups": groups, "step": int(self._scalars[3].item())}
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict):
+        groups = state_dict["param_groups"]
+        if len(groups) != len(self.param_groups) or any(len(a["params"]) != len(b["params"])
+                                                        for a, b in zip(groups, self.param_groups)):
+            raise ValueError("loaded state dict has different parameter groups")
+        state = state_dict["state"]
+        for i, p in self._indexed():
+            if p not in self._offs:
+                continue
+            s = state.get(i, state.get(str(i)))
+            if s is None:
+                raise ValueError(f"loaded state dict has no state for parameter {i}")
+            for k in ("master", "exp_avg", "exp_avg_sq"):
+                if tuple(s[k].shape) != tuple(p.shape):
+                    raise ValueError(f"loaded {k} of parameter {i} has shape {tuple(s[k].shape)}")
+        for i, p in self._indexed():
+            if p in self._offs:
+                s = state.get(i, state.get(str(i)))
+                for k in ("master", "exp_avg", "exp_avg_sq"):
+                    self.state[p][k].copy_(s[k])
+        for mine, theirs in zip(self.param_groups, groups):
+            mine.update({k: v for k, v in theirs.items() if k != "params"})
+        self._scalars[3:4].fill_(int(state_dict.get("step", 0)))
+        self._scalars[6:7].zero_()
