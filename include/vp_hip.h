@@ -26,7 +26,7 @@ extern "C" {
 #define VP_ERR_UNSUPPORTED 1001
 
 /* ABI version: bump when any struct layout or signature below changes. */
-#define VP_ABI_VERSION 21
+#define VP_ABI_VERSION 22
 int vp_abi_version(void);
 /* "<sha256 of sources + flags>:<sha256 of the compiler version>" of the build (no reference counterpart) */
 const char* vp_build_digest(void);
@@ -38,8 +38,8 @@ const char* vp_build_digest(void);
  * runs two variants on the same operands.  Returns VP_ERR_ARG for an unknown name or a value over 31 bytes.  Host
  * only; not thread-safe against launches in flight on other host threads.  (ABI 14.) */
 int vp_set_knob(const char* name, const char* value);
-/* sizeof of the descriptor structs as compiled into the library: out[0..9] = gemm, attn, dpm, gemm_mx, attn_fp8,
- * conv3d, attn_bwd, mt_tensor, mt_chunk, optim_scalars (ABI check) */
+/* sizeof of the descriptor structs as compiled into the library: out[0..11] = gemm, attn, dpm, gemm_mx, attn_fp8,
+ * conv3d, attn_bwd, mt_tensor, mt_chunk, optim_scalars, zero_range, zero_record (ABI check) */
 void vp_struct_sizes(int64_t* out);
 
 /* ---------------------------------------------------------------------------------------------------------------
@@ -693,6 +693,61 @@ int vp_v_loss_bf16(const void* model_output, const void* noisy, const void* targ
                    int32_t mask_is_f32, const int64_t* timesteps, const float* alphas_cumprod, int32_t n_alphas,
                    int32_t B, int32_t F, int32_t C, int32_t HW, float lambda, float* partials, float* loss,
                    void* dout, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Sharded training tail (ABI 22; csrc/zero.hip): the kernels of a data-parallel optimizer step with the fp32 state
+ * sharded over the ranks (the reference trains under DeepSpeed ZeRO stage 2, accelerate_config_machine_single_ds.yaml).
+ * The element space is the flat state space of the training tail above: tensor t at elements [state_off, state_off +
+ * numel), state_off a multiple of 8, T elements in all.  per = ceil(T / world) rounded up to a multiple of 8; rank r
+ * owns elements [r per, (r + 1) per) and keeps master / exp_avg / exp_avg_sq for them only (fp32 [per] each).  One
+ * step is, with the three collectives left to the caller:
+ *   vp_zero_pack_bf16        bf16 gradients -> fp32 flat [world per], scaled by 1 / world
+ *   (reduce-scatter, sum)    -> this rank's fp32 gradient shard [per]: the average over the ranks
+ *   vp_zero_shard_sqnorm     -> this rank's (sum of squares, non-finite flag) record
+ *   (all-gather)             -> the records of all ranks, in rank order
+ *   vp_zero_finalize         -> vp_optim_scalars, bit-identical on every rank
+ *   vp_zero_shard_adamw      once per parameter group: the update of the shard, bf16(p) into a bf16 shard
+ *   (all-gather)             -> bf16 flat [world per]
+ *   vp_zero_unpack_bf16      bf16 flat -> the bf16 parameters
+ * The shard kernels run over a DEVICE table of ranges: pieces of the shard of at most VP_MT_CHUNK elements, none of
+ * which crosses a tensor (hence a parameter group) or the shard, and which cover only tensors that have a gradient
+ * this step (no padding).  Range starts are multiples of 8 elements.  Same rules as the training tail: 16-byte body,
+ * scalar head / tail, 64-bit offsets, no float atomics, fixed-order two-stage reductions, no host read.  A chunk or
+ * range that does not fit the buffer length passed with it is left out (nothing is read or written for it). */
+typedef struct {
+  int64_t start; /* first element, relative to the start of this rank's shard */
+  int32_t n;     /* 1 .. VP_MT_CHUNK elements; start + n <= per */
+  int32_t pad;
+} vp_zero_range;
+typedef struct {
+  float sqsum;       /* sum of squares of the averaged gradient over the rank's ranges */
+  int32_t nonfinite; /* 1 when one of them is inf / NaN */
+} vp_zero_record;
+/* pack, over the tensor / chunk tables of ALL trainable tensors: flat[state_off + i] = (float)grad[i] * inv_world
+ * (one fp32 product; inv_world in (0, 1]); a tensor whose grad pointer is NULL gets zeros.  zero_grads: the bf16
+ * gradient is zeroed in the same pass (whether or not the step is skipped later).  Padding is never written. */
+int vp_zero_pack_bf16(const vp_mt_tensor* tensors, const vp_mt_chunk* chunks, int32_t n_chunks, float* flat,
+                      int64_t flat_len, float inv_world, int32_t zero_grads, void* stream);
+/* unpack, over the same tables: param[i] = flat[state_off + i] (bf16) for the tensors whose grad pointer is not
+ * NULL; nothing at all in a skipped step (scalars->skipped) */
+int vp_zero_unpack_bf16(const vp_mt_tensor* tensors, const vp_mt_chunk* chunks, int32_t n_chunks, const void* flat,
+                        int64_t flat_len, const vp_optim_scalars* scalars, void* stream);
+/* shard norm: partials[c] / flags[c] = the fp32 sum of squares / non-finite flag of range c of grad_shard (fp32
+ * [per]; the fp32 bit pattern is tested, so an average that overflowed counts), then one workgroup sums the slots in
+ * a fixed order into *record.  n_ranges = 0 (a rank that owns only padding): record = (0, 0), still written. */
+int vp_zero_shard_sqnorm(const vp_zero_range* ranges, int32_t n_ranges, const float* grad_shard, int64_t per,
+                         float* partials, int32_t* flags, vp_zero_record* record, void* stream);
+/* vp_optim_finalize (advance_step = 1; the same device code) over records[0 .. world) in rank order: every rank that
+ * passes the same records and the same scalars block gets the same block, bit for bit */
+int vp_zero_finalize(const vp_zero_record* records, int32_t world, float max_norm, double beta1, double beta2,
+                     int32_t skip_nonfinite, vp_optim_scalars* scalars, void* stream);
+/* vp_mt_adamw_bf16's update (the same per-element device function) over ranges [range_begin, range_begin + n_ranges)
+ * of the shard: g = grad_shard (* clip_coef when use_clip), master / exp_avg / exp_avg_sq fp32 [per] updated in place,
+ * param_shard[i] = bf16(p) (bf16 [per]).  A skipped step writes nothing. */
+int vp_zero_shard_adamw(const vp_zero_range* ranges, int32_t range_begin, int32_t n_ranges, const float* grad_shard,
+                        float* master, float* exp_avg, float* exp_avg_sq, void* param_shard, int64_t per,
+                        const vp_optim_scalars* scalars, double lr, double beta1, double beta2, double eps,
+                        double weight_decay, int32_t use_clip, void* stream);
 
 
 #ifdef __cplusplus

@@ -1,6 +1,6 @@
 """Optimizer-step time at the real branch parameter set on one MI355X: FusedAdamW against the torch equivalents.
 
-    python tools/bench_optim.py [--rounds R] [--iters N]
+    python tools/bench_optim.py [--rounds R] [--iters N] [--sharded]
 
 Parameters: the trainable VideoPainter branch (5b-I2V config, num_layers=2, init_synthetic_weights_), bf16, with
 random bf16 gradients N(0, 1e-3^2); the training script's hyper-parameters (lr 1e-5, betas (0.9, 0.95), weight decay
@@ -13,6 +13,13 @@ random bf16 gradients N(0, 1e-3^2); the training script's hyper-parameters (lr 1
                bf16 copy-back
     torch_bf16 torch.optim.AdamW(foreach=True) directly on the bf16 parameters (no master weights: the
                wrong-but-cheap baseline)
+
+--sharded adds a fourth variant, interleaved with the others: videopainter_amd.ShardedFusedAdamW(max_grad_norm=1.0) at
+world size 1 over RCCL (the process initialises a one-rank "nccl" group itself: the reduce-scatter and both all-gathers
+run in RCCL on the device buffers, as copies), and afterwards times its kernels one by one, each with its achieved
+bytes/s from its own byte count — pack 2 B read + 4 B written per parameter, shard AdamW 16 + 14 B, unpack 2 + 2 B —
+next to vp_mt_adamw_bf16's in the same run (the yardstick), and the three collectives.  No figure for world > 1 can be
+produced on one GPU.
 
 Prints ms per step per round (HIP events around N back-to-back steps), and for `fused` the effective bandwidth
 30 B x n_params / t (norm pass: 2 B read; update pass: 14 B read + 14 B written per parameter) as a fraction of
@@ -48,6 +55,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--sharded", action="store_true", help="add ShardedFusedAdamW at world 1 over RCCL")
     args = ap.parse_args()
     from videopainter_amd import CogvideoXBranchModel, FusedAdamW, device_scope
     from videopainter_amd import kernels as K
@@ -89,6 +97,21 @@ def main():
     opt16 = torch.optim.AdamW(p16, **HYP, foreach=True)
 
     variants = dict(fused=fused.step, torch_fp32=torch_fp32, torch_bf16=opt16.step)
+    sharded = None
+    if args.sharded:
+        import socket
+        from videopainter_amd import ShardedFusedAdamW
+        from videopainter_amd import distributed as VD
+        sock = socket.socket()
+        sock.bind(("127.0.0.1", 0))
+        port = sock.getsockname()[1]
+        sock.close()
+        for k, v in (("MASTER_ADDR", "127.0.0.1"), ("MASTER_PORT", str(port)), ("RANK", "0"), ("WORLD_SIZE", "1")):
+            os.environ.setdefault(k, v)
+        torch.cuda.set_device(0)
+        VD.init("nccl", torch.device("cuda", 0))
+        sharded = ShardedFusedAdamW(with_grads(clone()), **HYP, max_grad_norm=1.0)
+        variants["sharded"] = sharded.step
     for fn in variants.values():  # warm-up (allocations, table upload)
         fn()
         fn()
@@ -116,6 +139,36 @@ def main():
                norm_pass_ms=norm_ms, norm_pass_gb_per_s=2.0 * n_params / (norm_ms * 1e-3) / 1e9,
                update_pass_ms=upd_ms, update_pass_gb_per_s=28.0 * n_params / (upd_ms * 1e-3) / 1e9,
                speedup_vs_torch_fp32=med["torch_fp32"] / med["fused"])
+    if sharded is not None:
+        z, zt, c = sharded, sharded._tables, sharded._comm
+        mine = z._flat16[z._lo:z._hi]
+        ksteps = dict(
+            pack=(6.0, lambda: K.zero_pack(zt.tensors, zt.chunks, zt.n_chunks, z._flat32, inv_world=1.0,
+                                           zero_grads=False)),
+            shard_norm=(4.0, lambda: K.zero_shard_sqnorm(zt.ranges, zt.n_ranges, z._grad_shard, zt.partials, zt.flags,
+                                                         z._record)),
+            shard_adamw=(30.0, lambda: K.zero_shard_adamw(zt.ranges, 0, zt.n_ranges, z._grad_shard, z._master,
+                                                          z._exp_avg, z._exp_avg_sq, mine, z._scalars, lr=HYP["lr"],
+                                                          betas=HYP["betas"], eps=HYP["eps"],
+                                                          weight_decay=HYP["weight_decay"], use_clip=True)),
+            unpack=(4.0, lambda: K.zero_unpack(zt.tensors, zt.chunks, zt.n_chunks, z._flat16, z._scalars)),
+            reduce_scatter_f32=(8.0, lambda: c.reduce_scatter_sum(0, z._grad_shard, z._flat32)),
+            all_gather_bf16=(4.0, lambda: c.all_gather(0, z._flat16, mine)))
+        res["sharded_kernels"] = {}
+        yard = res["update_pass_gb_per_s"]
+        for name, (nbytes, fn) in ksteps.items():
+            t_ms = timed(fn, args.iters)
+            gbs = nbytes * n_params / (t_ms * 1e-3) / 1e9
+            res["sharded_kernels"][name] = dict(ms=t_ms, bytes_per_param=nbytes, gb_per_s=gbs,
+                                                fraction_of_6p3_tb_s=gbs * 1e9 / HBM, vs_mt_adamw=gbs / yard)
+            print(f"sharded {name}: {t_ms:.3f} ms = {gbs:.0f} GB/s = {gbs * 1e9 / HBM:.2f} of 6.3 TB/s "
+                  f"({gbs / yard:.2f} of vp_mt_adamw_bf16's {yard:.0f} GB/s in this run)")
+        res["sharded_n_ranges"] = zt.n_ranges
+        res["sharded_note"] = "world 1 over RCCL on one GPU: the collectives are device copies; world > 1 unmeasured"
+        print(f"sharded step: {med['sharded']:.3f} ms against fused {med['fused']:.3f} ms "
+              f"(about 50 B against 30 B of traffic per parameter)")
+        import torch.distributed as dist
+        dist.destroy_process_group()
     print(f"fused: {med['fused']:.3f} ms = {bw / 1e9:.0f} GB/s = {bw / HBM:.2f} of 6.3 TB/s "
           f"(norm pass {norm_ms:.3f} ms, update pass {upd_ms:.3f} ms); torch fp32 equivalent "
           f"{med['torch_fp32']:.3f} ms, torch on bf16 {med['torch_bf16']:.3f} ms")

@@ -1,6 +1,6 @@
 """Training-step throughput of the VideoPainter training path on one MI355X.
 
-    python tools/bench_train.py [--steps K] [--warmup W] [--height 60 --width 90] [--optimizer none|torch|fused]
+    python tools/bench_train.py [--steps K] [--warmup W] [--height 60 --width 90] [--optimizer none|torch|fused|sharded]
                                 [--loss]
 
 One step = the reference's training iteration (train/train_cogvideox_inpainting_i2v_video.py:1856-1892 with the
@@ -10,7 +10,11 @@ launch script train/VideoPainter.sh: 49 frames 480x720 -> latent 13x60x90, batch
 parameter.  --optimizer torch adds torch's AdamW (foreach) stepped directly on the bf16 branch parameters (PyTorch's
 kernels, and no master weights: most of an lr = 1e-5 update is lost below the bf16 ulp); --optimizer fused adds
 videopainter_amd.FusedAdamW(max_grad_norm=1.0): gradient norm + clip + AdamW with fp32 master weights on the HIP
-kernels (csrc/optim.hip).  --loss replaces the synthetic loss gradient with inpainting_v_loss(...).backward()
+kernels (csrc/optim.hip); --optimizer sharded runs videopainter_amd.ShardedFusedAdamW(max_grad_norm=1.0), the
+data-parallel step (csrc/zero.hip): alone it forms a one-rank group, under `torchrun --nproc_per_node N` one rank per
+GPU (the group is initialised as bench.py does, the branch replicated from rank 0 with broadcast_module, every rank
+draws its own latents, and verify_replicas runs after the last step: "replicas_identical" in the JSON line, which
+rank 0 prints).  --loss replaces the synthetic loss gradient with inpainting_v_loss(...).backward()
 (:1879-1892).  Default: neither.  Random-init weights, synthetic latents.  Prints one JSON line; optimizer_ms = HIP
 events around optimizer.step().
 """
@@ -48,7 +52,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--height", type=int, default=60)
     ap.add_argument("--width", type=int, default=90)
-    ap.add_argument("--optimizer", choices=("none", "torch", "fused"), default="none")
+    ap.add_argument("--optimizer", choices=("none", "torch", "fused", "sharded"), default="none")
     ap.add_argument("--loss", action="store_true",
                     help="inpainting_v_loss(...).backward() instead of out.backward(dout)")
     ap.add_argument("--classes", action="store_true", help="per-class HIP-event timing pass afterwards")
@@ -59,6 +63,26 @@ def main():
     from videopainter_amd.embeddings import prepare_rotary_positional_embeddings
 
     dev = "cuda"
+    rank, world = 0, 1
+    if args.optimizer == "sharded":
+        import torch.distributed as dist
+        from videopainter_amd import distributed as VD
+        rank, world, local = VD.env_rank_world()
+        if "MASTER_ADDR" not in os.environ:  # stand-alone: a one-rank group on this GPU
+            import socket
+            sock = socket.socket()
+            sock.bind(("127.0.0.1", 0))
+            os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(sock.getsockname()[1]), RANK="0",
+                              WORLD_SIZE="1")
+            sock.close()
+        # VP_BENCH_DIST_BACKEND=gloo: a functional rehearsal with several ranks on the GPUs there are (as bench.py:
+        # ranks share a device and the collectives go through host copies; the timing says nothing about scaling)
+        backend = os.environ.get("VP_BENCH_DIST_BACKEND", "nccl")
+        if backend != "nccl":
+            local = local % max(1, torch.cuda.device_count())
+        dev = torch.device("cuda", local)
+        torch.cuda.set_device(dev)
+        VD.init(backend, dev)
     HL, WL = args.height, args.width
     cfg = dict(COGVIDEOX_5B_I2V, sample_height=HL, sample_width=WL)
     with device_scope(dev):
@@ -74,8 +98,12 @@ def main():
     elif args.optimizer == "fused":
         from videopainter_amd import FusedAdamW
         opt = FusedAdamW(params, lr=1e-5, betas=(0.9, 0.95), weight_decay=1e-4, max_grad_norm=1.0)
+    elif args.optimizer == "sharded":
+        from videopainter_amd import ShardedFusedAdamW
+        VD.broadcast_module(br, src=0, always=True)  # the replicas start from rank 0's bytes
+        opt = ShardedFusedAdamW(params, lr=1e-5, betas=(0.9, 0.95), weight_decay=1e-4, max_grad_norm=1.0)
 
-    g = torch.Generator().manual_seed(7)
+    g = torch.Generator().manual_seed(7 + rank)  # (every rank its own data)
     lat = torch.randn(1, F, 16, HL, WL, generator=g).to(dev, torch.bfloat16)
     img = torch.zeros(1, F, 16, HL, WL)
     img[:, 0] = torch.randn(1, 16, HL, WL, generator=g)
@@ -125,22 +153,35 @@ def main():
         torch.cuda.synchronize()
         print(f"step {i}: {time.perf_counter() - t0:.2f}s", file=sys.stderr, flush=True)
     el = (time.perf_counter() - t0) / args.steps
+    replicas = None
+    if args.optimizer == "sharded":
+        el = VD.max_over_ranks(el, dev)
+        ok, n_buckets = VD.verify_replicas(br, always=True)
+        replicas = dict(identical=ok, buckets=n_buckets, world=world)
     fl = flops(ntok, nv)
     res = dict(metric="training steps/sec (VideoPainter branch, 5b-I2V frozen, 49f 480x720, B=1)",
                value=1.0 / el, unit="steps/s", ms_per_step=el * 1e3, steps=args.steps, warmup=args.warmup,
                optimizer={"none": None, "torch": "torch AdamW foreach",
-                          "fused": "FusedAdamW(max_grad_norm=1.0)"}[args.optimizer],
+                          "fused": "FusedAdamW(max_grad_norm=1.0)",
+                          "sharded": "ShardedFusedAdamW(max_grad_norm=1.0)"}[args.optimizer],
                optimizer_ms=(sum(a.elapsed_time(b) for a, b in opt_events) / len(opt_events)) if opt_events else None,
                loss="inpainting_v_loss" if args.loss else None,
                tflops_per_s=fl["total"] / el / 1e12, flop_per_step=fl, ntok=ntok,
                peak_mem_gib=torch.cuda.max_memory_allocated() / 2 ** 30)
+    if replicas is not None:
+        res["world"] = world
+        res["replicas_identical"] = replicas["identical"]
+        res["replica_buckets"] = replicas["buckets"]
     if args.classes:
         with K.timed_launches("gemm", "attention", "attention_bwd") as tl:
             step()
         torch.cuda.synchronize()
         res["classes_ms"] = {n: tl.mean_ms(n) * tl.count(n) for n in ("gemm", "attention", "attention_bwd")}
         res["counts"] = {n: tl.count(n) for n in ("gemm", "attention", "attention_bwd")}
-    print(json.dumps(res))
+    if rank == 0:
+        print(json.dumps(res))
+    if args.optimizer == "sharded":
+        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -34,6 +34,9 @@ def __getattr__(name):
     if name in ("FusedAdamW", "clip_grad_norm_", "get_gradient_norm"):
         from . import optim
         return getattr(optim, name)
+    if name in ("ShardedFusedAdamW",):
+        from . import zero
+        return getattr(zero, name)
     if name in ("inpainting_v_loss",):
         from . import training
         return getattr(training, name)

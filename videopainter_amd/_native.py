@@ -11,7 +11,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VP_HIP_LIB", os.path.join(_HERE, "_lib", "libvp_hip.so"))
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 vp = C.c_void_p
 i32 = C.c_int32
@@ -103,6 +103,14 @@ class OptimScalars(C.Structure):
                 ("bias_c2", f32), ("skipped", i32), ("pad", i32)]
 
 
+class ZeroRange(C.Structure):
+    _fields_ = [("start", i64), ("n", i32), ("pad", i32)]
+
+
+class ZeroRecord(C.Structure):
+    _fields_ = [("sqsum", f32), ("nonfinite", i32)]
+
+
 (EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_SCALE, EPI_GATED, EPI_BIAS_ADDROWS, EPI_BIAS_GELU_MXFP8, EPI_BIAS_QKNORM_ROPE,
  EPI_GELU_BWD) = range(8)
 
@@ -189,6 +197,12 @@ _SIGS = {
     "vp_scale_dev_bf16": (i32, [vp, vp, i64, vp, vp]),
     "vp_v_loss_partials": (i64, [i32, i32, i32, i32]),
     "vp_v_loss_bf16": (i32, [vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp]),
+    "vp_zero_pack_bf16": (i32, [vp, vp, i32, vp, i64, f32, i32, vp]),
+    "vp_zero_unpack_bf16": (i32, [vp, vp, i32, vp, i64, vp, vp]),
+    "vp_zero_shard_sqnorm": (i32, [vp, i32, vp, i64, vp, vp, vp, vp]),
+    "vp_zero_finalize": (i32, [vp, i32, f32, C.c_double, C.c_double, i32, vp, vp]),
+    "vp_zero_shard_adamw": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, i64, vp, C.c_double, C.c_double, C.c_double,
+                                  C.c_double, C.c_double, i32, vp]),
 }
 
 EXPORTS = tuple(_SIGS)
@@ -240,11 +254,11 @@ def lib():
         if src is not None and built.split(":")[0] != src:
             raise HipLibraryError(f"{LIB_PATH} was built from other sources (digest {built[:12]}.. != "
                                   f"{src[:12]}..); rebuild with `python -m videopainter_amd.build`")
-        sizes = (i64 * 10)()
+        sizes = (i64 * 12)()
         L.vp_struct_sizes(sizes)
         want = (C.sizeof(GemmDesc), C.sizeof(AttnDesc), C.sizeof(DpmDesc), C.sizeof(GemmMxDesc),
                 C.sizeof(AttnFp8Desc), C.sizeof(Conv3dDesc), C.sizeof(AttnBwdDesc), C.sizeof(MtTensor),
-                C.sizeof(MtChunk), C.sizeof(OptimScalars))
+                C.sizeof(MtChunk), C.sizeof(OptimScalars), C.sizeof(ZeroRange), C.sizeof(ZeroRecord))
         if tuple(sizes) != want:
             raise HipLibraryError(f"descriptor size mismatch lib={tuple(sizes)} python={want}; rebuild")
         knob_values.update({k: os.environ.get(k) for k in KNOBS})  # what the library read at load

@@ -297,6 +297,8 @@ extern "C" void vp_struct_sizes(int64_t* out) {
   out[7] = (int64_t)sizeof(vp_mt_tensor);
   out[8] = (int64_t)sizeof(vp_mt_chunk);
   out[9] = (int64_t)sizeof(vp_optim_scalars);
+  out[10] = (int64_t)sizeof(vp_zero_range);
+  out[11] = (int64_t)sizeof(vp_zero_record);
 }
 
 // M <= 2 rows (the CFG pair's AdaLN / time-embedding vectors), K <= 512: a weight-streaming kernel.  Each wave owns

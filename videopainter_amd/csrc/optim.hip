@@ -3,53 +3,11 @@
 // is memory-bound streaming: one workgroup per VP_MT_CHUNK elements of one tensor, 16-byte loads / stores in the
 // body, scalar head / tail.  Reductions are two-stage (a partial per chunk in its own slot, then one workgroup that
 // sums the slots in a fixed order): no float atomics, bit-identical run to run.
-#include "vp_common.h"
+#include "optim_common.h"  // shared with csrc/zero.hip: workgroup sum, chunk decoding, adam_element, the finaliser
 
 namespace {
 
-constexpr int OT = 256;  // threads per workgroup; VP_MT_CHUNK = OT * 8 elements * 8 rounds
-static_assert(VP_MT_CHUNK % (OT * 8) == 0, "a chunk is whole rounds of 8 elements per thread");
-
-// fixed-order sum over the workgroup (xor butterfly inside a wave, then the waves in order); valid in thread 0
-VP_DEV float block_sum(float v, float* red) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float s = 0.f;
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int w = 0; w < OT / 64; ++w) s += red[w];
-  }
-  __syncthreads();
-  return s;
-}
-
-VP_DEV bool bf16_nonfinite(bf16 x) { return (__builtin_bit_cast(uint16_t, x) & 0x7f80u) == 0x7f80u; }
-
-// the element range of chunk c: tensor entry, first element, count
-struct ChunkRange {
-  vp_mt_tensor t;
-  int64_t start;
-  int n;
-};
-VP_DEV ChunkRange chunk_range(const vp_mt_tensor* __restrict__ tensors, const vp_mt_chunk* __restrict__ chunks,
-                              int c) {
-  const vp_mt_chunk ch = chunks[c];
-  ChunkRange r;
-  r.t = tensors[ch.tensor];
-  r.start = (int64_t)ch.chunk * VP_MT_CHUNK;
-  const int64_t left = r.t.numel - r.start;
-  r.n = left < VP_MT_CHUNK ? (left > 0 ? (int)left : 0) : VP_MT_CHUNK;
-  return r;
-}
-
-// scalar elements before p reaches a 16-byte boundary (all n when p is not even 2-byte aligned)
-VP_DEV int head_of(const void* p, int n) {
-  const uintptr_t a = (uintptr_t)p;
-  if (a & 1) return n;
-  const int h = (int)(((16 - (a & 15)) & 15) >> 1);
-  return h < n ? h : n;
-}
+using namespace vp_optim;
 
 // ---- a. squared gradient norm, stage 1 ----
 __global__ __launch_bounds__(OT) void mt_sqnorm_kernel(const vp_mt_tensor* __restrict__ tensors,
@@ -98,38 +56,9 @@ __global__ __launch_bounds__(OT) void optim_finalize_kernel(const float* __restr
                                                             const int* __restrict__ flags, int n, float max_norm,
                                                             double beta1, double beta2, int skip_nonfinite,
                                                             int advance_step, vp_optim_scalars* __restrict__ sc) {
-#pragma clang fp contract(off)
   __shared__ float red[OT / 64];
   __shared__ int bad_any;
-  if (threadIdx.x == 0) bad_any = 0;
-  float acc = 0.f;
-  bool bad = false;
-  for (int i = threadIdx.x; i < n; i += OT) {
-    acc += partials[i];
-    bad |= flags[i] != 0;
-  }
-  __syncthreads();
-  if (bad) bad_any = 1;
-  const float s = block_sum(acc, red);
-  if (threadIdx.x != 0) return;
-  const float norm = sqrtf(s);
-  const int nonfinite = bad_any;
-  sc->grad_norm = norm;
-  sc->nonfinite = nonfinite;
-  float coef = 1.f;
-  if (max_norm > 0.f) {
-    coef = max_norm / (norm + 1e-6f);
-    coef = coef > 1.f ? 1.f : coef;  // (a NaN coefficient stays NaN, as torch.clamp keeps it)
-  }
-  sc->clip_coef = coef;
-  if (!advance_step) return;
-  const int skipped = (nonfinite && skip_nonfinite) ? 1 : 0;
-  sc->skipped = skipped;
-  if (skipped) return;
-  const int step = sc->step + 1;
-  sc->step = step;
-  sc->bias_c1 = (float)(1.0 - pow(beta1, (double)step));
-  sc->bias_c2 = (float)(1.0 - pow(beta2, (double)step));
+  optim_finalize_body(partials, flags, 1, n, max_norm, beta1, beta2, skip_nonfinite, advance_step, sc, red, &bad_any);
 }
 
 // ---- b. in-place scale by the device clip coefficient ----
@@ -154,26 +83,7 @@ __global__ __launch_bounds__(OT) void mt_scale_kernel(const vp_mt_tensor* __rest
 }
 
 // ---- c. AdamW with fp32 master weights ----
-struct AdamArgs {
-  float lr, decay, omb1, beta2, omb2, eps;  // decay = 1 - lr * weight_decay, omb = 1 - beta
-  int use_clip, zero_grads;
-};
-
-struct AdamCoef {
-  float clip, step_size, bc2_sqrt;
-};
-
-VP_DEV void adam_element(float g, float& p, float& m, float& v, const AdamArgs& a, const AdamCoef& k) {
-  // torch.optim.adamw._single_tensor_adamw, one rounded operation per torch op (no contraction across them)
-#pragma clang fp contract(off)
-  g *= k.clip;
-  p *= a.decay;                               // param.mul_(1 - lr * weight_decay)
-  m = __builtin_fmaf(a.omb1, g - m, m);       // exp_avg.lerp_(grad, 1 - beta1)
-  v = v * a.beta2 + a.omb2 * g * g;           // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
-  const float denom = sqrtf(v) / k.bc2_sqrt + a.eps;
-  p = p - k.step_size * (m / denom);          // param.addcdiv_(exp_avg, denom, value=-step_size)
-}
-
+// (AdamArgs / AdamCoef / adam_element: optim_common.h)
 __global__ __launch_bounds__(OT) void mt_adamw_kernel(const vp_mt_tensor* __restrict__ tensors,
                                                       const vp_mt_chunk* __restrict__ chunks, int chunk_begin,
                                                       float* __restrict__ master, float* __restrict__ exp_avg,
@@ -201,10 +111,7 @@ __global__ __launch_bounds__(OT) void mt_adamw_kernel(const vp_mt_tensor* __rest
     for (int i = tail0 + threadIdx.x; i < r.n; i += OT) g[i] = zero;
     return;
   }
-  AdamCoef k;
-  k.clip = a.use_clip ? sc->clip_coef : 1.f;
-  k.step_size = a.lr / sc->bias_c1;
-  k.bc2_sqrt = sqrtf(sc->bias_c2);
+  const AdamCoef k = adam_coef(a, sc);
 
   auto scalar = [&](int i) {
     float p = pm[i], m = mm[i], v = vm[i];
@@ -393,20 +300,10 @@ extern "C" int vp_mt_adamw_bf16(const vp_mt_tensor* tensors, const vp_mt_chunk* 
                                 const vp_optim_scalars* scalars, double lr, double beta1, double beta2, double eps,
                                 double weight_decay, int32_t use_clip, int32_t zero_grads, void* stream) {
   if (n_chunks < 0 || chunk_begin < 0 || !scalars || !master || !exp_avg || !exp_avg_sq) return VP_ERR_ARG;
-  if (!(lr >= 0.0) || !(eps >= 0.0) || !(weight_decay >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) ||
-      !(beta2 >= 0.0 && beta2 < 1.0))
-    return VP_ERR_ARG;
+  if (!adam_hyper_ok(lr, beta1, beta2, eps, weight_decay)) return VP_ERR_ARG;
   if (n_chunks == 0) return VP_OK;
   if (!tensors || !chunks) return VP_ERR_ARG;
-  AdamArgs a;
-  a.lr = (float)lr;
-  a.decay = (float)(1.0 - lr * weight_decay);
-  a.omb1 = (float)(1.0 - beta1);
-  a.beta2 = (float)beta2;
-  a.omb2 = (float)(1.0 - beta2);
-  a.eps = (float)eps;
-  a.use_clip = use_clip;
-  a.zero_grads = zero_grads;
+  const AdamArgs a = adam_args(lr, beta1, beta2, eps, weight_decay, use_clip, zero_grads);
   hipLaunchKernelGGL(mt_adamw_kernel, dim3(n_chunks), dim3(OT), 0, (hipStream_t)stream, tensors, chunks, chunk_begin,
                      master, exp_avg, exp_avg_sq, scalars, a);
   VP_CHECK_LAUNCH();

@@ -1,0 +1,283 @@
+// Data-parallel training tail (gfx950): the kernels around the three collectives of a sharded optimizer step
+// (include/vp_hip.h "Sharded training tail"; videopainter_amd/zero.py).  The element space is the flat fp32 state
+// space of csrc/optim.hip (every tensor at its state_off, 8-element aligned), cut into `world` shards of `per`
+// elements.  pack / unpack move between the bf16 tensors and the flat staging buffers over the multi-tensor tables;
+// the norm and the AdamW update run over this rank's shard, described by a table of ranges (pieces of at most
+// VP_MT_CHUNK elements that cross no tensor and leave out padding and tensors without a gradient).  All of it is
+// memory-bound streaming: one workgroup per chunk / range, 16-byte loads and stores in the body, scalar head / tail
+// (the whole piece scalar when its streams do not share one 16-byte phase), 64-bit offsets, no float atomics,
+// two-stage reductions with a fixed-order one-workgroup second stage.
+#include "optim_common.h"
+
+namespace {
+
+using namespace vp_optim;
+
+// ---- 1. pack: flat[state_off + i] = float(grad[i]) * inv_world (zeros for a tensor without a gradient) ----
+__global__ __launch_bounds__(OT) void zero_pack_kernel(const vp_mt_tensor* __restrict__ tensors,
+                                                       const vp_mt_chunk* __restrict__ chunks,
+                                                       float* __restrict__ flat, int64_t flat_len, float inv_world,
+                                                       int zero_grads) {
+#pragma clang fp contract(off)
+  const ChunkRange r = chunk_range(tensors, chunks, blockIdx.x);
+  const int64_t o = r.t.state_off + r.start;
+  if (r.t.state_off < 0 || o + r.n > flat_len) return;  // (a table that does not fit the buffer writes nothing)
+  float* out = flat + o;
+  bf16* g = (bf16*)r.t.grad;
+  if (g == nullptr) {
+    const int head = ((uintptr_t)out & 15) ? r.n : 0;
+    const int nvec = (r.n - head) / 4;
+    for (int i = threadIdx.x; i < head; i += OT) out[i] = 0.f;
+    for (int i = threadIdx.x; i < nvec; i += OT) *(f32x4*)(out + head + 4 * i) = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int i = head + nvec * 4 + threadIdx.x; i < r.n; i += OT) out[i] = 0.f;
+    return;
+  }
+  g += r.start;
+  int head = head_of(g, r.n);
+  if ((uintptr_t)(out + head) & 15) head = r.n;
+  const int nvec = (r.n - head) / 8;
+  const int tail0 = head + nvec * 8;
+  const bf16 zero = f2bf(0.f);
+  auto scalar = [&](int i) {
+    out[i] = bf2f(g[i]) * inv_world;
+    if (zero_grads) g[i] = zero;
+  };
+  for (int i = threadIdx.x; i < head; i += OT) scalar(i);
+  for (int i = threadIdx.x; i < nvec; i += OT) {
+    const int e0 = head + i * 8;
+    const bf16x8 g8 = *(const bf16x8*)(g + e0);
+    f32x4 lo, hi;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      lo[e] = bf2f(g8[e]) * inv_world;
+      hi[e] = bf2f(g8[4 + e]) * inv_world;
+    }
+    *(f32x4*)(out + e0) = lo;
+    *(f32x4*)(out + e0 + 4) = hi;
+    if (zero_grads) *(bf16x8*)(g + e0) = bf16x8{};
+  }
+  for (int i = tail0 + threadIdx.x; i < r.n; i += OT) scalar(i);
+}
+
+// ---- 4. unpack: param[i] = flat[state_off + i] for the tensors that had a gradient (nothing in a skipped step) ----
+__global__ __launch_bounds__(OT) void zero_unpack_kernel(const vp_mt_tensor* __restrict__ tensors,
+                                                         const vp_mt_chunk* __restrict__ chunks,
+                                                         const bf16* __restrict__ flat, int64_t flat_len,
+                                                         const vp_optim_scalars* __restrict__ sc) {
+  if (sc->skipped) return;
+  const ChunkRange r = chunk_range(tensors, chunks, blockIdx.x);
+  if (r.t.grad == nullptr || r.t.param == nullptr) return;
+  const int64_t o = r.t.state_off + r.start;
+  if (r.t.state_off < 0 || o + r.n > flat_len) return;
+  const bf16* in = flat + o;
+  bf16* w = (bf16*)r.t.param + r.start;
+  int head = head_of(w, r.n);
+  if (head_of(in, r.n) != head) head = r.n;
+  const int nvec = (r.n - head) / 8;
+  for (int i = threadIdx.x; i < head; i += OT) w[i] = in[i];
+  for (int i = threadIdx.x; i < nvec; i += OT) *(bf16x8*)(w + head + i * 8) = *(const bf16x8*)(in + head + i * 8);
+  for (int i = head + nvec * 8 + threadIdx.x; i < r.n; i += OT) w[i] = in[i];
+}
+
+// the piece of the shard range c describes (n = 0 when it does not fit the shard: nothing is read or written)
+struct ShardRange {
+  int64_t start;
+  int n;
+};
+VP_DEV ShardRange shard_range(const vp_zero_range* __restrict__ ranges, int c, int64_t per) {
+  const vp_zero_range rr = ranges[c];
+  ShardRange r;
+  r.start = rr.start;
+  r.n = (rr.start < 0 || rr.n < 0 || rr.n > VP_MT_CHUNK || rr.start + rr.n > per) ? 0 : rr.n;
+  return r;
+}
+
+// ---- 2. shard norm, stage 1: one fp32 sum of squares and one non-finite flag per range ----
+__global__ __launch_bounds__(OT) void zero_sqnorm_kernel(const vp_zero_range* __restrict__ ranges,
+                                                         const float* __restrict__ grad, int64_t per,
+                                                         float* __restrict__ partials, int* __restrict__ flags) {
+#pragma clang fp contract(off)
+  __shared__ float red[OT / 64];
+  __shared__ int bad_any;
+  const ShardRange r = shard_range(ranges, blockIdx.x, per);
+  const float* g = grad + r.start;
+  const int head = ((uintptr_t)g & 15) ? r.n : 0;
+  const int nvec = (r.n - head) / 4;
+  float acc = 0.f;
+  bool bad = false;
+  if (threadIdx.x == 0) bad_any = 0;
+  for (int i = threadIdx.x; i < head; i += OT) {
+    const float x = g[i];
+    bad |= f32_nonfinite(x);
+    acc = __builtin_fmaf(x, x, acc);
+  }
+  for (int i = threadIdx.x; i < nvec; i += OT) {
+    const f32x4 v = *(const f32x4*)(g + head + 4 * i);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      bad |= f32_nonfinite(v[e]);
+      acc = __builtin_fmaf(v[e], v[e], acc);
+    }
+  }
+  for (int i = head + nvec * 4 + threadIdx.x; i < r.n; i += OT) {
+    const float x = g[i];
+    bad |= f32_nonfinite(x);
+    acc = __builtin_fmaf(x, x, acc);
+  }
+  __syncthreads();
+  if (bad) bad_any = 1;  // (every writer stores the same value)
+  const float s = block_sum(acc, red);
+  if (threadIdx.x == 0) {
+    partials[blockIdx.x] = s;
+    flags[blockIdx.x] = bad_any;
+  }
+}
+
+// ---- 2. stage 2 (one workgroup): this rank's (sum, flag) record from its per-range slots, in a fixed order ----
+__global__ __launch_bounds__(OT) void zero_record_kernel(const float* __restrict__ partials,
+                                                         const int* __restrict__ flags, int n,
+                                                         vp_zero_record* __restrict__ rec) {
+  __shared__ float red[OT / 64];
+  __shared__ int bad_any;
+  const float s = sum_slots(partials, flags, 1, n, red, &bad_any);  // (optim_common.h: the finaliser's own sum)
+  if (threadIdx.x != 0) return;
+  rec->sqsum = s;
+  rec->nonfinite = bad_any;
+}
+
+// ---- 2. the finaliser over the ranks' records in rank order: optim.hip's, reading slots of stride 2 ----
+__global__ __launch_bounds__(OT) void zero_finalize_kernel(const vp_zero_record* __restrict__ records, int world,
+                                                           float max_norm, double beta1, double beta2,
+                                                           int skip_nonfinite, vp_optim_scalars* __restrict__ sc) {
+  static_assert(sizeof(vp_zero_record) == 8, "a record is one (fp32 sum, int32 flag) pair");
+  __shared__ float red[OT / 64];
+  __shared__ int bad_any;
+  optim_finalize_body((const float*)records, (const int*)records + 1, 2, world, max_norm, beta1, beta2,
+                      skip_nonfinite, 1, sc, red, &bad_any);
+}
+
+// ---- 3. AdamW on this rank's shard: fp32 gradient, master and moments in, bf16(p) out ----
+__global__ __launch_bounds__(OT) void zero_adamw_kernel(const vp_zero_range* __restrict__ ranges, int range_begin,
+                                                        const float* __restrict__ grad, float* __restrict__ master,
+                                                        float* __restrict__ exp_avg, float* __restrict__ exp_avg_sq,
+                                                        bf16* __restrict__ param, int64_t per,
+                                                        const vp_optim_scalars* __restrict__ sc, const AdamArgs a) {
+  if (sc->skipped) return;  // a skipped step writes no state and no parameter
+  const ShardRange r = shard_range(ranges, range_begin + blockIdx.x, per);
+  const float* g = grad + r.start;
+  float* pm = master + r.start;
+  float* mm = exp_avg + r.start;
+  float* vm = exp_avg_sq + r.start;
+  bf16* w = param + r.start;
+  // (range starts are multiples of 8 elements: with 16-byte aligned buffers every stream is in phase)
+  const bool vec = ((((uintptr_t)g | (uintptr_t)pm | (uintptr_t)mm | (uintptr_t)vm | (uintptr_t)w) & 15) == 0);
+  const int nvec = vec ? r.n / 8 : 0;
+  const AdamCoef k = adam_coef(a, sc);
+  for (int i = threadIdx.x; i < nvec; i += OT) {
+    const int o = i * 8;
+    f32x4 gg[2], p[2], m[2], v[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      gg[h] = *(const f32x4*)(g + o + 4 * h);
+      p[h] = *(const f32x4*)(pm + o + 4 * h);
+      m[h] = *(const f32x4*)(mm + o + 4 * h);
+      v[h] = *(const f32x4*)(vm + o + 4 * h);
+    }
+    bf16x8 w8;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float pe = p[e >> 2][e & 3], me = m[e >> 2][e & 3], ve = v[e >> 2][e & 3];
+      adam_element(gg[e >> 2][e & 3], pe, me, ve, a, k);
+      p[e >> 2][e & 3] = pe;
+      m[e >> 2][e & 3] = me;
+      v[e >> 2][e & 3] = ve;
+      w8[e] = f2bf(pe);
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      *(f32x4*)(pm + o + 4 * h) = p[h];
+      *(f32x4*)(mm + o + 4 * h) = m[h];
+      *(f32x4*)(vm + o + 4 * h) = v[h];
+    }
+    *(bf16x8*)(w + o) = w8;
+  }
+  for (int i = nvec * 8 + threadIdx.x; i < r.n; i += OT) {
+    float p = pm[i], m = mm[i], v = vm[i];
+    adam_element(g[i], p, m, v, a, k);
+    pm[i] = p;
+    mm[i] = m;
+    vm[i] = v;
+    w[i] = f2bf(p);
+  }
+}
+
+}  // namespace
+
+extern "C" int vp_zero_pack_bf16(const vp_mt_tensor* tensors, const vp_mt_chunk* chunks, int32_t n_chunks,
+                                 float* flat, int64_t flat_len, float inv_world, int32_t zero_grads, void* stream) {
+  if (n_chunks < 0 || flat_len < 0 || !(inv_world > 0.f && inv_world <= 1.f)) return VP_ERR_ARG;
+  if (n_chunks == 0) return VP_OK;
+  if (!tensors || !chunks || !flat) return VP_ERR_ARG;
+  hipLaunchKernelGGL(zero_pack_kernel, dim3(n_chunks), dim3(OT), 0, (hipStream_t)stream, tensors, chunks, flat,
+                     flat_len, inv_world, zero_grads);
+  VP_CHECK_LAUNCH();
+  return VP_OK;
+}
+
+extern "C" int vp_zero_unpack_bf16(const vp_mt_tensor* tensors, const vp_mt_chunk* chunks, int32_t n_chunks,
+                                   const void* flat, int64_t flat_len, const vp_optim_scalars* scalars,
+                                   void* stream) {
+  if (n_chunks < 0 || flat_len < 0 || !scalars) return VP_ERR_ARG;
+  if (n_chunks == 0) return VP_OK;
+  if (!tensors || !chunks || !flat) return VP_ERR_ARG;
+  hipLaunchKernelGGL(zero_unpack_kernel, dim3(n_chunks), dim3(OT), 0, (hipStream_t)stream, tensors, chunks,
+                     (const bf16*)flat, flat_len, scalars);
+  VP_CHECK_LAUNCH();
+  return VP_OK;
+}
+
+extern "C" int vp_zero_shard_sqnorm(const vp_zero_range* ranges, int32_t n_ranges, const float* grad_shard,
+                                    int64_t per, float* partials, int32_t* flags, vp_zero_record* record,
+                                    void* stream) {
+  if (n_ranges < 0 || per < 0 || !record) return VP_ERR_ARG;
+  if (n_ranges > 0) {
+    if (!ranges || !grad_shard || !partials || !flags) return VP_ERR_ARG;
+    hipLaunchKernelGGL(zero_sqnorm_kernel, dim3(n_ranges), dim3(OT), 0, (hipStream_t)stream, ranges, grad_shard, per,
+                       partials, flags);
+    VP_CHECK_LAUNCH();
+  }
+  // (a rank that owns only padding or idle tensors still publishes its record: sum 0, flag 0)
+  hipLaunchKernelGGL(zero_record_kernel, dim3(1), dim3(OT), 0, (hipStream_t)stream, (const float*)partials,
+                     (const int*)flags, n_ranges, record);
+  VP_CHECK_LAUNCH();
+  return VP_OK;
+}
+
+extern "C" int vp_zero_finalize(const vp_zero_record* records, int32_t world, float max_norm, double beta1,
+                                double beta2, int32_t skip_nonfinite, vp_optim_scalars* scalars, void* stream) {
+  if (!records || !scalars || world <= 0) return VP_ERR_ARG;
+  if (max_norm != max_norm) return VP_ERR_ARG;
+  if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0)) return VP_ERR_ARG;
+  hipLaunchKernelGGL(zero_finalize_kernel, dim3(1), dim3(OT), 0, (hipStream_t)stream, records, world, max_norm, beta1,
+                     beta2, skip_nonfinite, scalars);
+  VP_CHECK_LAUNCH();
+  return VP_OK;
+}
+
+extern "C" int vp_zero_shard_adamw(const vp_zero_range* ranges, int32_t range_begin, int32_t n_ranges,
+                                   const float* grad_shard, float* master, float* exp_avg, float* exp_avg_sq,
+                                   void* param_shard, int64_t per, const vp_optim_scalars* scalars, double lr,
+                                   double beta1, double beta2, double eps, double weight_decay, int32_t use_clip,
+                                   void* stream) {
+  if (n_ranges < 0 || range_begin < 0 || per < 0 || !scalars || !grad_shard || !master || !exp_avg || !exp_avg_sq ||
+      !param_shard)
+    return VP_ERR_ARG;
+  if (!adam_hyper_ok(lr, beta1, beta2, eps, weight_decay)) return VP_ERR_ARG;
+  if (n_ranges == 0) return VP_OK;
+  if (!ranges) return VP_ERR_ARG;
+  const AdamArgs a = adam_args(lr, beta1, beta2, eps, weight_decay, use_clip, 0);
+  hipLaunchKernelGGL(zero_adamw_kernel, dim3(n_ranges), dim3(OT), 0, (hipStream_t)stream, ranges, range_begin,
+                     grad_shard, master, exp_avg, exp_avg_sq, (bf16*)param_shard, per, scalars, a);
+  VP_CHECK_LAUNCH();
+  return VP_OK;
+}

@@ -16,6 +16,7 @@ Collectives here are issued in large flat buckets (few, big messages suit point-
 from __future__ import annotations
 
 import os
+import threading
 from typing import Callable, Dict, Iterable, List, Optional
 
 import torch
@@ -77,6 +78,116 @@ def _all_gather_rows(out: torch.Tensor, inp: torch.Tensor, group=None) -> None:
         raise ValueError("all-gather output must be contiguous")
     with _staged(out, group) as o, _staged(inp.contiguous(), group, writeback=False) as i:
         dist.all_gather_into_tensor(o.view(-1), i.view(-1), group=group)  # flat: one layout rule for every backend
+
+
+def reduce_scatter_sum(out: torch.Tensor, flat: torch.Tensor, group=None) -> None:
+    """out[per] = sum over the ranks of their flat[rank * per : (rank + 1) * per] (flat holds world * per elements)
+    on any backend.  RCCL reduces the device tensors as they are, in its own order.  A host backend (gloo: the CPU
+    tests, the one-GPU rehearsal) would sum along its ring, which is not rank order and not the same for every slice;
+    there the slices are exchanged on the host (one all-to-all of the staged copy) and added in rank order 0 .. P-1,
+    one fp32 rounding per add — LocalComm's sum, so a rehearsal is reproducible and equals the threads' result."""
+    world = dist.get_world_size(group)
+    if not out.is_contiguous() or not flat.is_contiguous():
+        raise ValueError("reduce-scatter tensors must be contiguous")
+    if flat.numel() != out.numel() * world or flat.dtype != out.dtype:
+        raise ValueError("reduce-scatter: flat must hold world slices of out's size and dtype")
+    if dist.get_backend(group) == "nccl":
+        dist.reduce_scatter_tensor(out.view(-1), flat.view(-1), op=dist.ReduceOp.SUM, group=group)
+        return
+    with _staged(flat, group, writeback=False) as i:
+        recv = torch.empty_like(i.view(-1))
+        dist.all_to_all_single(recv, i.view(-1), group=group)  # row j: rank j's slice for this rank
+        rows = recv.view(world, -1)
+        acc = rows[0].clone()
+        for j in range(1, world):
+            acc += rows[j]
+        out.view(-1).copy_(acc)
+
+
+def all_gather_flat(out: torch.Tensor, inp: torch.Tensor, group=None) -> None:
+    """out[world * n] = the ranks' inp[n] in rank order (exact copies; inp may be this rank's slice of out)."""
+    if out.numel() != inp.numel() * dist.get_world_size(group) or out.dtype != inp.dtype:
+        raise ValueError("all-gather: out must hold world slices of inp's size and dtype")
+    _all_gather_rows(out, inp, group)
+
+
+class GroupComm:
+    """The collectives of a sharded optimizer step (zero.ShardedFusedAdamW) on a torch.distributed process group.
+    The methods take the caller's rank first, as LocalComm's do, so one step code runs on both."""
+
+    def __init__(self, group=None):
+        if not dist.is_initialized():
+            raise ValueError("torch.distributed is not initialised (distributed.init) and no comm= was given")
+        self.group = group
+        self.world = dist.get_world_size(group)
+        self.rank = dist.get_rank(group)
+
+    def reduce_scatter_sum(self, rank: int, out: torch.Tensor, flat: torch.Tensor) -> None:
+        reduce_scatter_sum(out, flat, self.group)
+
+    def all_gather(self, rank: int, out: torch.Tensor, inp: torch.Tensor) -> None:
+        all_gather_flat(out, inp, self.group)
+
+
+class LocalComm:
+    """The same collectives for P ranks that are P threads of one process sharing one GPU stream (tests, a one-GPU
+    rehearsal; ulysses.ThreadComm's scheme): a call publishes the rank's buffer, waits for all P, does its copies /
+    adds, and waits again before the slots are reused — every copy is launched after its producer's launches, so
+    stream order makes it correct.  The reduce-scatter sums in rank order 0 .. P-1 (fp32 adds, one rounding each)."""
+
+    def __init__(self, P: int):
+        if P < 1:
+            raise ValueError("LocalComm needs at least one rank")
+        self.world = P
+        self.rank = None  # (every call names its rank)
+        self._slots: List[Optional[torch.Tensor]] = [None] * P
+        self._bar = threading.Barrier(P)
+
+    def reduce_scatter_sum(self, rank: int, out: torch.Tensor, flat: torch.Tensor) -> None:
+        n = out.numel()
+        if flat.numel() != n * self.world:
+            raise ValueError("reduce-scatter: flat must hold world slices of out's size")
+        self._slots[rank] = flat
+        self._bar.wait()
+        out.copy_(self._slots[0][rank * n:(rank + 1) * n])
+        for j in range(1, self.world):
+            out.add_(self._slots[j][rank * n:(rank + 1) * n])
+        self._bar.wait()
+
+    def all_gather(self, rank: int, out: torch.Tensor, inp: torch.Tensor) -> None:
+        n = inp.numel()
+        if out.numel() != n * self.world:
+            raise ValueError("all-gather: out must hold world slices of inp's size")
+        self._slots[rank] = inp
+        self._bar.wait()
+        for j in range(self.world):
+            dst = out[j * n:(j + 1) * n]
+            if dst.data_ptr() != self._slots[j].data_ptr():  # (this rank's own slice, gathered in place)
+                dst.copy_(self._slots[j].view(-1))
+        self._bar.wait()
+
+    def run(self, fn, *args, **kw):
+        """fn(rank, *args, **kw) on P threads; returns the P results (the first exception re-raised)."""
+        res: List = [None] * self.world
+        err: List = []
+
+        def body(r):
+            try:
+                res[r] = fn(r, *args, **kw)
+            except BaseException as e:  # noqa: BLE001 - re-raised below after every thread ended
+                err.append(e)
+                self._bar.abort()
+
+        ts = [threading.Thread(target=body, args=(r,)) for r in range(self.world)]
+        for t in ts:
+            t.start()
+        for t in ts:
+            t.join()
+        if err:
+            self._bar.reset()
+            real = [e for e in err if not isinstance(e, threading.BrokenBarrierError)]
+            raise (real or err)[0]
+        return res
 
 
 def _send(t: torch.Tensor, dst: int) -> None:

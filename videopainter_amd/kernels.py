@@ -1370,6 +1370,76 @@ def mt_adamw(tensors: torch.Tensor, chunks: torch.Tensor, chunk_begin: int, n_ch
                                      int(use_clip), int(zero_grads), _stream()), "vp_mt_adamw_bf16")
 
 
+# sharded training tail (csrc/zero.hip; videopainter_amd/zero.py builds the tables and runs the collectives between)
+
+def _flat1(t: torch.Tensor, name: str, dtype) -> None:
+    _chk(t, name, dtype)
+    if t.dim() != 1 or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous 1-D tensor")
+
+
+def zero_pack(tensors: torch.Tensor, chunks: torch.Tensor, n_chunks: int, flat: torch.Tensor, *, inv_world: float,
+              zero_grads: bool = False) -> None:
+    """flat[state_off + i] = float(grad[i]) * inv_world over the tables (zeros for a NULL gradient pointer)."""
+    _flat1(flat, "flat", torch.float32)
+    N.check(N.lib().vp_zero_pack_bf16(_p(tensors), _p(chunks), n_chunks, _p(flat), flat.numel(), inv_world,
+                                      int(zero_grads), _stream()), "vp_zero_pack_bf16")
+
+
+def zero_unpack(tensors: torch.Tensor, chunks: torch.Tensor, n_chunks: int, flat: torch.Tensor,
+                scalars: torch.Tensor) -> None:
+    """param[i] = flat[state_off + i] over the tables, for the tensors with a gradient (not in a skipped step)."""
+    _flat1(flat, "flat", BF16)
+    _chk(scalars, "scalars", torch.int32)
+    N.check(N.lib().vp_zero_unpack_bf16(_p(tensors), _p(chunks), n_chunks, _p(flat), flat.numel(), _p(scalars),
+                                        _stream()), "vp_zero_unpack_bf16")
+
+
+def zero_shard_sqnorm(ranges: Optional[torch.Tensor], n_ranges: int, grad_shard: torch.Tensor, partials: torch.Tensor,
+                      flags: torch.Tensor, record: torch.Tensor) -> None:
+    """This rank's (sum of squares, non-finite flag) record (int32[2] storage, N.ZeroRecord) of its gradient shard."""
+    _flat1(grad_shard, "grad_shard", torch.float32)
+    _chk(partials, "partials", torch.float32)
+    _chk(flags, "flags", torch.int32)
+    _chk(record, "record", torch.int32)
+    if partials.numel() < n_ranges or flags.numel() < n_ranges:
+        raise ValueError("zero_shard_sqnorm: partials / flags hold fewer than n_ranges slots")
+    if record.numel() * 4 < C.sizeof(N.ZeroRecord) or not record.is_contiguous():
+        raise ValueError("zero_shard_sqnorm: record too small")
+    N.check(N.lib().vp_zero_shard_sqnorm(_p(ranges), n_ranges, _p(grad_shard), grad_shard.numel(), _p(partials),
+                                         _p(flags), _p(record), _stream()), "vp_zero_shard_sqnorm")
+
+
+def zero_finalize(records: torch.Tensor, world: int, scalars: torch.Tensor, *, max_norm: float = 0.0,
+                  betas=(0.0, 0.0), skip_nonfinite: bool = False) -> None:
+    """optim_finalize(advance_step=True) over the ranks' records (int32 [world, 2] storage) in rank order."""
+    _chk(records, "records", torch.int32)
+    _chk(scalars, "scalars", torch.int32)
+    if records.numel() * 4 < world * C.sizeof(N.ZeroRecord) or not records.is_contiguous():
+        raise ValueError("zero_finalize: records hold fewer than world entries")
+    if scalars.numel() * 4 < C.sizeof(N.OptimScalars):
+        raise ValueError("zero_finalize: scalars block too small")
+    N.check(N.lib().vp_zero_finalize(_p(records), world, max_norm, betas[0], betas[1], int(skip_nonfinite),
+                                     _p(scalars), _stream()), "vp_zero_finalize")
+
+
+def zero_shard_adamw(ranges: Optional[torch.Tensor], range_begin: int, n_ranges: int, grad_shard: torch.Tensor,
+                     master: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, param_shard: torch.Tensor,
+                     scalars: torch.Tensor, *, lr: float, betas, eps: float, weight_decay: float,
+                     use_clip: bool) -> None:
+    """The AdamW update of ranges [range_begin, range_begin + n_ranges) of this rank's shard (one parameter group)."""
+    per = grad_shard.numel()
+    for t, n in ((grad_shard, "grad_shard"), (master, "master"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+        _flat1(t, n, torch.float32)
+    _flat1(param_shard, "param_shard", BF16)
+    if any(t.numel() != per for t in (master, exp_avg, exp_avg_sq, param_shard)):
+        raise ValueError("zero_shard_adamw: the shard buffers differ in length")
+    _chk(scalars, "scalars", torch.int32)
+    N.check(N.lib().vp_zero_shard_adamw(_p(ranges), range_begin, n_ranges, _p(grad_shard), _p(master), _p(exp_avg),
+                                        _p(exp_avg_sq), _p(param_shard), per, _p(scalars), lr, betas[0], betas[1],
+                                        eps, weight_decay, int(use_clip), _stream()), "vp_zero_shard_adamw")
+
+
 def scale(x: torch.Tensor, s: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """bf16(x * s) with s a one-element fp32 DEVICE tensor (no host read)."""
     _flat(x, "x")
