@@ -26,20 +26,23 @@ extern "C" {
 #define VP_ERR_UNSUPPORTED 1001
 
 /* ABI version: bump when any struct layout or signature below changes. */
-#define VP_ABI_VERSION 22
+#define VP_ABI_VERSION 23
 int vp_abi_version(void);
 /* "<sha256 of sources + flags>:<sha256 of the compiler version>" of the build (no reference counterpart) */
 const char* vp_build_digest(void);
 /* A/B switches of the library (kernel-variant selection only, never numerics of the default path; DESIGN_LOG.md §5):
  * VP_GEMM_VARIANT, VP_GEMM_NO_TAIL, VP_GEMM_GROUP, VP_GEMM8_VARIANT, VP_ATTN_BOUNDED_MODE, VP_ATTN_UNBOUNDED_MODE,
  * VP_ATTN_NO_SPLIT, VP_ATTN8_VARIANT, VP_T5_ATTN, VP_CONV_HOIST, VP_CONV_PIPE,
- * VP_ATTN_BWD_VARIANT, VP_ATTN_TAIL, VP_ATTN_PERSIST.  Each is read from the environment
+ * VP_ATTN_BWD_VARIANT, VP_ATTN_TAIL, VP_ATTN_PERSIST, and two that the library only stores for its Python front end
+ * ("0" = off): VP_CFG_SHARED (the CFG halves' shared first-block work) and VP_MOD_BATCHED (one launch for a forward's
+ * AdaLN modulation linears).  Each is read from the environment
  * once, when the library is loaded; afterwards only vp_set_knob changes it (value NULL = unset), e.g. a test that
  * runs two variants on the same operands.  Returns VP_ERR_ARG for an unknown name or a value over 31 bytes.  Host
  * only; not thread-safe against launches in flight on other host threads.  (ABI 14.) */
 int vp_set_knob(const char* name, const char* value);
-/* sizeof of the descriptor structs as compiled into the library: out[0..11] = gemm, attn, dpm, gemm_mx, attn_fp8,
- * conv3d, attn_bwd, mt_tensor, mt_chunk, optim_scalars, zero_range, zero_record (ABI check) */
+/* sizeof of the descriptor structs as compiled into the library: out[0..13] = gemm, attn, dpm, gemm_mx, attn_fp8,
+ * conv3d, attn_bwd, mt_tensor, mt_chunk, optim_scalars, zero_range, zero_record, attn_merge, linear_group (ABI
+ * check) */
 void vp_struct_sizes(int64_t* out);
 
 /* ---------------------------------------------------------------------------------------------------------------
@@ -233,6 +236,10 @@ typedef struct vp_attn_desc {
                              16x16x32 kernels only (a k2_full launch runs s16 / a16). */
 } vp_attn_desc;
 #define VP_ATTN_BOUNDED_SCORES 1
+/* flags bit (ABI 23): O is fp32 [B, Nq, H*64] (o_sb / o_sn in fp32 elements, multiples of 4; base 16-byte aligned) and
+ * receives softmax(...) V unrounded — a partial for vp_attention_merge_bf16, which then rounds once.  Needs
+ * out_scale == 1 and no accumulate.  Every bf16 kernel variant, the tail-piece combine and the a16 redo take it. */
+#define VP_ATTN_OUT_F32 2
 #define VP_ATTN_SCORE_BOUND 60.0f
 
 int vp_attention_fwd_bf16(const vp_attn_desc* d, void* stream);
@@ -249,6 +256,34 @@ int vp_attention_fwd_bf16_ws(const vp_attn_desc* d, void* workspace, int64_t wor
  * "w64f", "s16i", "p1"; "fp8:N" for the fp8 kernel's VP_ATTN8_VARIANT = N: 2 and 3, and 1 and 4 with that build) is
  * in this library, else 0.  Host-only.  A launch that names a variant outside the build returns VP_ERR_UNSUPPORTED. */
 int vp_attention_variant_built(const char* name);
+
+/* Merge of two attention partials over disjoint key sets (ABI 23): given (O_a, lse_a) and (O_b, lse_b) of the same
+ * queries, O = rnd((2^lse_a O_a + 2^lse_b O_b) / (2^lse_a + 2^lse_b)) per (batch, head, query) — the attention over
+ * the union of the two key sets.  O_a / O_b: bf16 [B, Nq, H*64], or with flags & VP_MERGE_IN_F32 both fp32 (the
+ * VP_ATTN_OUT_F32 outputs: the merged result is then rounded once, like a single attention call's; with bf16 partials
+ * it carries their rounding too).  O: bf16 [B, Nq, H*64].
+ * Element (b, h, n, d) at X[b*x_sb + n*x_sn + h*64 + d] (strides in elements, multiples of 8; bases 16-byte aligned);
+ * lse_a / lse_b: fp32 [B, H, Nq] in the log2 units of vp_attn_desc.lse, batch stride la_sb / lb_sb (elements).  A
+ * batch stride of 0 is allowed on either input: one partial read by every batch row (the video-query x video-key
+ * part the two classifier-free-guidance halves share).  The weights are taken relative to max(lse_a, lse_b), so
+ * nothing overflows; an input whose lse is -inf contributes nothing (its values are not read); both -inf: zeros. */
+typedef struct vp_attn_merge_desc {
+  int32_t B, H, Nq, head_dim;
+  const void* Oa;
+  int64_t oa_sb, oa_sn;
+  const float* lse_a;
+  int64_t la_sb;
+  const void* Ob;
+  int64_t ob_sb, ob_sn;
+  const float* lse_b;
+  int64_t lb_sb;
+  void* O;
+  int64_t o_sb, o_sn;
+  int32_t flags; /* VP_MERGE_IN_F32 */
+  int32_t pad0;
+} vp_attn_merge_desc;
+#define VP_MERGE_IN_F32 1
+int vp_attention_merge_bf16(const vp_attn_merge_desc* d, void* stream);
 
 /* fp8 attention (BASELINE config 5 "attn + FFN in fp8"; same math as vp_attention_fwd_bf16, single K/V segment).
  * base.Q / base.K: e4m3 [B, N, H*64] written by vp_head_norm_rope_fp8 (strides in bytes, multiples of 16), each
@@ -370,6 +405,20 @@ int vp_final_norm_bf16(const void* x, void* y, int32_t B, int32_t Ntok, int32_t 
  * ------------------------------------------------------------------------------------------------------------- */
 int vp_linear_small_bf16(const void* x, int64_t ldx, const void* W, const void* bias, void* y, int64_t ldy, int32_t M,
                          int32_t N, int32_t K, int32_t act_in, int32_t act_out, void* stream);
+
+/* G such linears of one shape on ONE input, in one launch (ABI 23): the AdaLN modulation linears of every block of a
+ * forward all read silu(temb), so a forward computes them together, right after the time embedding.  groups: a DEVICE
+ * table of G (W, bias) pairs, W bf16 [N, K] 16-byte aligned, bias bf16 [N] or NULL; group g writes y + g * y_gs, rows
+ * at stride ldy (elements).  Only the weight-streaming shapes (M <= 2, K <= 512, ldx % 8 == 0, x 16-byte aligned;
+ * anything else: VP_ERR_UNSUPPORTED), with that kernel's reduction order per output element: bit-equal to G calls of
+ * vp_linear_small_bf16. */
+typedef struct vp_linear_group {
+  const void* W;
+  const void* bias;
+} vp_linear_group;
+int vp_linear_small_batched_bf16(const void* x, int64_t ldx, const vp_linear_group* groups, int32_t G, void* y,
+                                 int64_t y_gs, int64_t ldy, int32_t M, int32_t N, int32_t K, int32_t act_in,
+                                 int32_t act_out, void* stream);
 
 /* sinusoidal timestep embedding, flip_sin_to_cos: out bf16 [B, dim] — get_timestep_embedding
  * (DF/models/embeddings.py:27-78); timesteps: device fp32 [B] (the reference casts to float). */

@@ -11,7 +11,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VP_HIP_LIB", os.path.join(_HERE, "_lib", "libvp_hip.so"))
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 vp = C.c_void_p
 i32 = C.c_int32
@@ -47,6 +47,17 @@ class AttnDesc(C.Structure):
                 ("O", vp), ("o_sb", i64), ("o_sn", i64),
                 ("scale", f32), ("out_scale", f32), ("accumulate", i32), ("flags", i32), ("lse", vp),
                 ("k2_full", vp), ("k2_len", vp), ("l_extra", vp)]
+
+
+class AttnMergeDesc(C.Structure):
+    _fields_ = [("B", i32), ("H", i32), ("Nq", i32), ("head_dim", i32),
+                ("Oa", vp), ("oa_sb", i64), ("oa_sn", i64), ("lse_a", vp), ("la_sb", i64),
+                ("Ob", vp), ("ob_sb", i64), ("ob_sn", i64), ("lse_b", vp), ("lb_sb", i64),
+                ("O", vp), ("o_sb", i64), ("o_sn", i64), ("flags", i32), ("pad0", i32)]
+
+
+class LinearGroup(C.Structure):
+    _fields_ = [("W", vp), ("bias", vp)]
 
 
 class GemmMxDesc(C.Structure):
@@ -134,6 +145,7 @@ _SIGS = {
     "vp_attention_workspace_bytes": (i64, [C.POINTER(AttnDesc)]),
     "vp_attention_fwd_bf16_ws": (i32, [C.POINTER(AttnDesc), vp, i64, vp]),
     "vp_attention_variant_built": (i32, [C.c_char_p]),
+    "vp_attention_merge_bf16": (i32, [C.POINTER(AttnMergeDesc), vp]),
     "vp_gemm_variant_built": (i32, [i32]),
     "vp_v_pack_fp8_bytes": (i64, [i32, i32, i32, C.POINTER(i64), C.POINTER(i64)]),
     "vp_v_pack_fp8": (i32, [vp, i64, i64, i32, i32, i32, vp, vp, vp]),
@@ -149,6 +161,7 @@ _SIGS = {
                                vp, vp, f32, vp, vp]),
     "vp_final_norm_bf16": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, f32, vp, i64, vp]),
     "vp_linear_small_bf16": (i32, [vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp]),
+    "vp_linear_small_batched_bf16": (i32, [vp, i64, vp, i32, vp, i64, i64, i32, i32, i32, i32, i32, vp]),
     "vp_timestep_embedding_bf16": (i32, [vp, vp, i32, i32, f32, vp]),
     "vp_patchify_bf16": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp]),
     "vp_patch_mask": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, vp]),
@@ -215,7 +228,7 @@ DIAG_SIGS = {
 # the library's A/B knobs (vp_set_knob): read from the environment once at load; knob_values mirrors them
 KNOBS = ("VP_GEMM_VARIANT", "VP_GEMM_NO_TAIL", "VP_GEMM_GROUP", "VP_GEMM8_VARIANT", "VP_ATTN_BOUNDED_MODE",
          "VP_ATTN_UNBOUNDED_MODE", "VP_ATTN_NO_SPLIT", "VP_ATTN8_VARIANT", "VP_T5_ATTN", "VP_CONV_HOIST", "VP_CONV_PIPE",
-         "VP_ATTN_BWD_VARIANT", "VP_ATTN_TAIL", "VP_ATTN_PERSIST")
+         "VP_ATTN_BWD_VARIANT", "VP_ATTN_TAIL", "VP_ATTN_PERSIST", "VP_CFG_SHARED", "VP_MOD_BATCHED")
 knob_values: dict = {}
 
 _lib = None
@@ -254,11 +267,12 @@ def lib():
         if src is not None and built.split(":")[0] != src:
             raise HipLibraryError(f"{LIB_PATH} was built from other sources (digest {built[:12]}.. != "
                                   f"{src[:12]}..); rebuild with `python -m videopainter_amd.build`")
-        sizes = (i64 * 12)()
+        sizes = (i64 * 14)()
         L.vp_struct_sizes(sizes)
         want = (C.sizeof(GemmDesc), C.sizeof(AttnDesc), C.sizeof(DpmDesc), C.sizeof(GemmMxDesc),
                 C.sizeof(AttnFp8Desc), C.sizeof(Conv3dDesc), C.sizeof(AttnBwdDesc), C.sizeof(MtTensor),
-                C.sizeof(MtChunk), C.sizeof(OptimScalars), C.sizeof(ZeroRange), C.sizeof(ZeroRecord))
+                C.sizeof(MtChunk), C.sizeof(OptimScalars), C.sizeof(ZeroRange), C.sizeof(ZeroRecord),
+                C.sizeof(AttnMergeDesc), C.sizeof(LinearGroup))
         if tuple(sizes) != want:
             raise HipLibraryError(f"descriptor size mismatch lib={tuple(sizes)} python={want}; rebuild")
         knob_values.update({k: os.environ.get(k) for k in KNOBS})  # what the library read at load

@@ -193,6 +193,37 @@ def bounded_scores(attn) -> bool:
     return cached[1]
 
 
+def cfg_shared_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, heads: int,
+                         text_len: int, *, scale: float, bounded_scores: bool = False) -> torch.Tensor:
+    """Joint self-attention of two batch rows whose video rows (tokens >= text_len) are the same and whose text rows
+    differ — the classifier-free-guidance halves in a model's first block.  q / k / v / out: [2, N, heads*64] views;
+    of q / k / v only batch 0 and batch 1's text rows are read.  The softmax over the joint keys is composed from
+    pieces over disjoint key sets (CogVideoXBlock._attend_cfg_shared): the video x video part once instead of twice."""
+    T = text_len
+    B, N, D = q.shape
+    if B != 2 or not 0 < T < N:
+        raise ValueError(f"cfg_shared_attention needs two batch rows with text and video rows, got {tuple(q.shape)}")
+    Nv = N - T
+    dev = q.device
+    qv, kv, vv = q[:1, T:], k[:1, T:], v[:1, T:]  # batch 0's video rows
+    kw = dict(scale=scale, bounded_scores=bounded_scores)
+    # (a) video queries x video keys, once
+    # (the partials stay fp32: the merge rounds to bf16 once, as a single call does)
+    o_v = torch.empty(1, Nv, D, device=dev, dtype=torch.float32)
+    lse_v = torch.empty(1, heads, Nv, device=dev, dtype=torch.float32)
+    K.attention(qv, kv, vv, o_v, heads, lse=lse_v, **kw)
+    # (b) the same queries x each half's text keys
+    o_t = torch.empty(2, Nv, D, device=dev, dtype=torch.float32)
+    lse_t = torch.empty(2, heads, Nv, device=dev, dtype=torch.float32)
+    K.attention(qv.expand(2, -1, -1), k[:, :T], v[:, :T], o_t, heads, lse=lse_t, **kw)
+    # (c) each half's text queries x (own text keys | the shared video keys)
+    K.attention(q[:, :T], k[:, :T], v[:, :T], out[:, :T], heads, k2=kv.expand(2, -1, -1), v2=vv.expand(2, -1, -1),
+                **kw)
+    # (d) video rows of both halves = merge of (a) and (b)
+    K.attention_merge(o_v.expand(2, -1, -1), lse_v.expand(2, -1, -1), o_t, lse_t, out[:, T:], heads)
+    return out
+
+
 class CogVideoXAttnProcessor2_0:
     """HIP restatement of `CogVideoXAttnProcessor2_0.__call__` (attention_processor.py:2107-2209)."""
 

@@ -116,8 +116,9 @@ class CogvideoXBranchModel(CogVideoXTransformer3DModel):
                 timestep: Union[int, float, torch.LongTensor] = None, timestep_cond: Optional[torch.Tensor] = None,
                 image_rotary_emb: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                 attention_kwargs: Optional[Dict[str, Any]] = None, mask_add: Optional[bool] = False,
-                wo_text: Optional[bool] = False, return_dict: bool = True):
-        """branch_cogvideox.py:295-434.  Returns a list of [B, Nv, D] bf16 injection tensors (views of one
+                wo_text: Optional[bool] = False, return_dict: bool = True, cfg_shared_video: bool = False):
+        """branch_cogvideox.py:295-434.  cfg_shared_video: as in CogVideoXTransformer3DModel.forward (here the promise
+        covers branch_cond too).  Returns a list of [B, Nv, D] bf16 injection tensors (views of one
         [B, T + Nv, D] buffer per block; the text rows of that buffer are scratch).  wo_text (:382-412, the training
         scripts' --wo_text): the blocks run on the video tokens alone (`forward_joint` with no text rows = the
         reference's `forward_wo_text`: the video AdaLN chunks, attention over the video tokens with RoPE on all of
@@ -161,8 +162,11 @@ class CogvideoXBranchModel(CogVideoXTransformer3DModel):
             x, T = x[:, T:].contiguous(), 0
         Ntok = x.shape[1]
         samples = []
+        mods = self.batched_modulations(emb)
         for i, block in enumerate(self.transformer_blocks):
-            x = block.forward_joint(x, T, emb, rope)
+            x = block.forward_joint(x, T, emb, rope, mod1=mods[2 * i] if mods is not None else None,
+                                    mod2=mods[2 * i + 1] if mods is not None else None,
+                                    cfg_shared_video=bool(cfg_shared_video) and i == 0)
             samples.append(x)
         outs = []
         for s, lin in zip(samples, self.branch_blocks):

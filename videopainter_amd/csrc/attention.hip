@@ -215,6 +215,16 @@ VP_DEV void store_out(const vp_attn_desc& d, const f32x16 (&o)[2], float l_run, 
   // softmax statistics for the backward (both lanes of a pair hold the same query, m and l: one writes)
   if (d.lse != nullptr && hl == 0 && !nonfinite(m_lse))  // (NaN: no statistics from this kernel; an opaque test, see nonfinite)
     d.lse[((int64_t)b * d.H + h) * d.Nq + q] = m_lse + __log2f(l_tot);
+  if (d.flags & VP_ATTN_OUT_F32) {  // an unrounded partial for vp_attention_merge_bf16
+    float* frow = (float*)d.O + (int64_t)b * d.o_sb + (int64_t)q * d.o_sn + h * 64;
+#pragma unroll
+    for (int dh = 0; dh < 2; ++dh)
+#pragma unroll
+      for (int gq = 0; gq < 4; ++gq)
+        *(f32x4*)(frow + dh * 32 + 8 * gq + 4 * hl) = (f32x4){o[dh][4 * gq] * inv, o[dh][4 * gq + 1] * inv,
+                                                               o[dh][4 * gq + 2] * inv, o[dh][4 * gq + 3] * inv};
+    return;
+  }
   bf16* orow = (bf16*)d.O + (int64_t)b * d.o_sb + (int64_t)q * d.o_sn + h * 64;
 #pragma unroll
   for (int dh = 0; dh < 2; ++dh)
@@ -348,6 +358,11 @@ __global__ __launch_bounds__(256) void attn_combine_kernel(const vp_attn_desc d,
   if (d.l_extra != nullptr) l += __builtin_amdgcn_exp2f(lx - mx);
   const float inv = 1.f / l;
   if (d.lse != nullptr && quad == 0) d.lse[((int64_t)b * d.H + h) * d.Nq + q] = mx + __log2f(l);
+  if (d.flags & VP_ATTN_OUT_F32) {
+    *(f32x4*)((float*)d.O + (int64_t)b * d.o_sb + (int64_t)q * d.o_sn + h * 64 + 4 * quad) =
+        (f32x4){acc[0] * inv, acc[1] * inv, acc[2] * inv, acc[3] * inv};
+    return;
+  }
   bf16* orow = (bf16*)d.O + (int64_t)b * d.o_sb + (int64_t)q * d.o_sn + h * 64 + 4 * quad;
   bf16x4 ov;
   bf16x4 old;
@@ -1337,6 +1352,12 @@ __global__ __launch_bounds__(NW4 * 64, 2) void attn_fwd_p2s(const vp_attn_desc d
     if (q >= d.Nq) continue;
     const float inv = 1.f / l_tot[qt];
     if (d.lse != nullptr && g == 0) d.lse[((int64_t)b * d.H + h) * d.Nq + q] = r.anc + __log2f(l_tot[qt]);
+    if (d.flags & VP_ATTN_OUT_F32) {
+      float* frow = (float*)d.O + (int64_t)b * d.o_sb + (int64_t)q * d.o_sn + h * 64 + 4 * g;
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) *(f32x4*)(frow + dt * 16) = r.o[dt][qt] * inv;
+      continue;
+    }
     bf16* orow = (bf16*)d.O + (int64_t)b * d.o_sb + (int64_t)q * d.o_sn + h * 64 + 4 * g;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) {
@@ -1722,6 +1743,12 @@ __global__ __launch_bounds__(NW4 * 64, 2) void attn_fwd_s16(const vp_attn_desc d
     if (q >= d.Nq) continue;
     const float inv = 1.f / l_tot;
     if (d.lse != nullptr && g == 0) d.lse[((int64_t)b * d.H + h) * d.Nq + q] = m[qt] + __log2f(l_tot);
+    if (d.flags & VP_ATTN_OUT_F32) {
+      float* frow = (float*)d.O + (int64_t)b * d.o_sb + (int64_t)q * d.o_sn + h * 64 + 4 * g;
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) *(f32x4*)(frow + dt * 16) = o[dt][qt] * inv;
+      continue;
+    }
     bf16* orow = (bf16*)d.O + (int64_t)b * d.o_sb + (int64_t)q * d.o_sn + h * 64 + 4 * g;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) {
@@ -2466,7 +2493,9 @@ int attn_check(const vp_attn_desc* d) {
       (d->v_sb % 8) || (d->o_sb % 4))
     return VP_ERR_ARG;
   if (d->Nk2 > 0 && ((d->k2_sn % 8) || (d->v2_sn % 8) || (d->k2_sb % 8) || (d->v2_sb % 8))) return VP_ERR_ARG;
-  if (d->flags & ~VP_ATTN_BOUNDED_SCORES) return VP_ERR_ARG;
+  if (d->flags & ~(VP_ATTN_BOUNDED_SCORES | VP_ATTN_OUT_F32)) return VP_ERR_ARG;
+  // fp32 output: an unrounded partial (no blend); 16-byte stores
+  if ((d->flags & VP_ATTN_OUT_F32) && (d->accumulate || d->out_scale != 1.f || ((uintptr_t)d->O & 15))) return VP_ERR_ARG;
   // the LDS-DMA source offsets are 32-bit: a tile's rows must lie within 2^31 bytes of its first row
   if ((int64_t)KB * d->k_sn * 2 >= ((int64_t)1 << 31) || (int64_t)KB * d->v_sn * 2 >= ((int64_t)1 << 31))
     return VP_ERR_ARG;

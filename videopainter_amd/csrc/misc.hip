@@ -248,7 +248,7 @@ const char* const knob_names[VPK_COUNT] = {"VP_GEMM_VARIANT",        "VP_GEMM_NO
                                            "VP_ATTN_UNBOUNDED_MODE", "VP_ATTN_NO_SPLIT",  "VP_ATTN8_VARIANT",
                                            "VP_T5_ATTN",             "VP_CONV_HOIST",     "VP_CONV_PIPE",
                                            "VP_ATTN_BWD_VARIANT",    "VP_ATTN_TAIL",
-                                           "VP_ATTN_PERSIST"};
+                                           "VP_ATTN_PERSIST",        "VP_CFG_SHARED",     "VP_MOD_BATCHED"};
 struct KnobTable {
   char val[VPK_COUNT][32];
   bool set[VPK_COUNT];
@@ -299,6 +299,8 @@ extern "C" void vp_struct_sizes(int64_t* out) {
   out[9] = (int64_t)sizeof(vp_optim_scalars);
   out[10] = (int64_t)sizeof(vp_zero_range);
   out[11] = (int64_t)sizeof(vp_zero_record);
+  out[12] = (int64_t)sizeof(vp_attn_merge_desc);
+  out[13] = (int64_t)sizeof(vp_linear_group);
 }
 
 // M <= 2 rows (the CFG pair's AdaLN / time-embedding vectors), K <= 512: a weight-streaming kernel.  Each wave owns
@@ -307,11 +309,9 @@ extern "C" void vp_struct_sizes(int64_t* out) {
 // memory (2 x 16 bytes per lane), no LDS and no barrier.  Same per-lane products and wave sums as the general
 // kernel: bit-identical results.
 constexpr int LSF_COLS = 8;
-__global__ __launch_bounds__(LS_THREADS) void linear_small_fast_kernel(const bf16* __restrict__ x, int64_t ldx,
-                                                                      const bf16* __restrict__ W,
-                                                                      const bf16* __restrict__ bias,
-                                                                      bf16* __restrict__ y, int64_t ldy, int M, int N,
-                                                                      int K, int act_in, int act_out) {
+VP_DEV void linear_small_fast_body(const bf16* __restrict__ x, int64_t ldx, const bf16* __restrict__ W,
+                                   const bf16* __restrict__ bias, bf16* __restrict__ y, int64_t ldy, int M, int N,
+                                   int K, int act_in, int act_out) {
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int nbase = (blockIdx.x * (LS_THREADS / 64) + wave) * LSF_COLS;
@@ -346,6 +346,113 @@ __global__ __launch_bounds__(LS_THREADS) void linear_small_fast_kernel(const bf1
       }
     }
   }
+}
+
+__global__ __launch_bounds__(LS_THREADS) void linear_small_fast_kernel(const bf16* __restrict__ x, int64_t ldx,
+                                                                      const bf16* __restrict__ W,
+                                                                      const bf16* __restrict__ bias,
+                                                                      bf16* __restrict__ y, int64_t ldy, int M, int N,
+                                                                      int K, int act_in, int act_out) {
+  linear_small_fast_body(x, ldx, W, bias, y, ldy, M, N, K, act_in, act_out);
+}
+
+// G linears of one shape on one input in one launch (the AdaLN modulation vectors of every block of a forward, which
+// all read silu(temb)): blockIdx.y picks the group's weight / bias from the device table, its output is y + g * y_gs.
+// The body is linear_small_fast_kernel's: per output element the same products and wave sums, bit-identical.
+__global__ __launch_bounds__(LS_THREADS) void linear_small_batched_kernel(const bf16* __restrict__ x, int64_t ldx,
+                                                                         const vp_linear_group* __restrict__ groups,
+                                                                         bf16* __restrict__ y, int64_t y_gs,
+                                                                         int64_t ldy, int M, int N, int K, int act_in,
+                                                                         int act_out) {
+  const vp_linear_group g = groups[blockIdx.y];
+  linear_small_fast_body(x, ldx, (const bf16*)g.W, (const bf16*)g.bias, y + (int64_t)blockIdx.y * y_gs, ldy, M, N, K,
+                         act_in, act_out);
+}
+
+extern "C" int vp_linear_small_batched_bf16(const void* x, int64_t ldx, const vp_linear_group* groups, int32_t G,
+                                            void* y, int64_t y_gs, int64_t ldy, int32_t M, int32_t N, int32_t K,
+                                            int32_t act_in, int32_t act_out, void* stream) {
+  if (!x || !groups || !y || G <= 0 || G > 65535 || M <= 0 || N <= 0 || K <= 0 || (K % 8) || ldx < K || ldy < N ||
+      y_gs < (int64_t)(M - 1) * ldy + N)
+    return VP_ERR_ARG;
+  // the weight-streaming kernel's shapes only (the per-call entry falls back to the LDS kernel; this one does not)
+  if (M > 2 || K > 512 || (ldx % 8) || ((uintptr_t)x & 15)) return VP_ERR_UNSUPPORTED;
+  const int cpb = (LS_THREADS / 64) * LSF_COLS;
+  hipLaunchKernelGGL(linear_small_batched_kernel, dim3((N + cpb - 1) / cpb, G), dim3(LS_THREADS), 0,
+                     (hipStream_t)stream, (const bf16*)x, ldx, groups, (bf16*)y, y_gs, ldy, M, N, K, act_in, act_out);
+  VP_CHECK_LAUNCH();
+  return VP_OK;
+}
+
+// ---- merge of two attention partials over disjoint key sets: O = (2^lse_a O_a + 2^lse_b O_b) / (2^lse_a + 2^lse_b)
+// per (batch, head, query), weights relative to max(lse_a, lse_b).  One workgroup per (batch, AM_ROWS queries): its
+// threads walk the rows' H * 8 sixteen-byte chunks, so the loads and stores are contiguous and the rows' lse values
+// (one cache line per head) are fetched once per workgroup. ----
+constexpr int AM_ROWS = 8;
+// 8 values of a partial: bf16 (one 16-byte load) or fp32 (two)
+VP_DEV void am_load8(const bf16* p, float (&v)[8]) {
+  const bf16x8 x = *(const bf16x8*)p;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) v[e] = bf2f(x[e]);
+}
+VP_DEV void am_load8(const float* p, float (&v)[8]) {
+  const f32x4 x0 = *(const f32x4*)p, x1 = *(const f32x4*)(p + 4);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] = x0[e], v[4 + e] = x1[e];
+}
+template <typename TI>
+__global__ __launch_bounds__(256) void attn_merge_kernel(const vp_attn_merge_desc d) {
+  const int b = blockIdx.y;
+  const int q0 = blockIdx.x * AM_ROWS;
+  const int cpr = d.H * 8;  // 16-byte chunks per row
+  const TI* oa = (const TI*)d.Oa + (int64_t)b * d.oa_sb;
+  const TI* ob = (const TI*)d.Ob + (int64_t)b * d.ob_sb;
+  bf16* o = (bf16*)d.O + (int64_t)b * d.o_sb;
+  const float* la = d.lse_a + (int64_t)b * d.la_sb;
+  const float* lb = d.lse_b + (int64_t)b * d.lb_sb;
+  for (int i = threadIdx.x; i < AM_ROWS * cpr; i += 256) {
+    const int r = i / cpr, c = i - r * cpr;
+    const int q = q0 + r;
+    if (q >= d.Nq) break;
+    const int h = c >> 3;
+    const float sa = la[(int64_t)h * d.Nq + q], sb = lb[(int64_t)h * d.Nq + q];
+    const float mx = fmaxf(sa, sb);
+    // an input whose lse is -inf holds no mass: weight 0 and its values are not used (they may be anything)
+    const float wa = sa == -INFINITY ? 0.f : exp2f(sa - mx);
+    const float wb = sb == -INFINITY ? 0.f : exp2f(sb - mx);
+    const float l = wa + wb;
+    float va[8] = {}, vb[8] = {};
+    bf16x8 vo;
+    if (wa != 0.f) am_load8(oa + (int64_t)q * d.oa_sn + c * 8, va);
+    if (wb != 0.f) am_load8(ob + (int64_t)q * d.ob_sn + c * 8, vb);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float num = fmaf(wa, va[e], wb * vb[e]);
+      vo[e] = f2bf(l > 0.f ? num / l : 0.f);
+    }
+    *(bf16x8*)(o + (int64_t)q * d.o_sn + c * 8) = vo;
+  }
+}
+
+extern "C" int vp_attention_merge_bf16(const vp_attn_merge_desc* d, void* stream) {
+  if (d == nullptr || !d->Oa || !d->Ob || !d->O || !d->lse_a || !d->lse_b) return VP_ERR_ARG;
+  if (d->head_dim != 64) return VP_ERR_UNSUPPORTED;
+  if (d->B <= 0 || d->B > 65535 || d->H <= 0 || d->Nq <= 0) return VP_ERR_ARG;
+  // 16-byte vector accesses: strides in multiples of 8 elements, aligned bases; a batch stride of 0 (one copy read by
+  // every batch row) is allowed on the inputs, not on the output
+  if ((d->oa_sn % 8) || (d->ob_sn % 8) || (d->o_sn % 8) || (d->oa_sb % 8) || (d->ob_sb % 8) || (d->o_sb % 8) ||
+      d->oa_sb < 0 || d->ob_sb < 0 || d->la_sb < 0 || d->lb_sb < 0 || (d->B > 1 && d->o_sb <= 0) ||
+      d->oa_sn < d->H * 64 || d->ob_sn < d->H * 64 || d->o_sn < d->H * 64)
+    return VP_ERR_ARG;
+  if (((uintptr_t)d->Oa | (uintptr_t)d->Ob | (uintptr_t)d->O) & 15) return VP_ERR_ARG;
+  if (d->flags & ~VP_MERGE_IN_F32) return VP_ERR_ARG;
+  const dim3 grid((d->Nq + AM_ROWS - 1) / AM_ROWS, d->B);
+  if (d->flags & VP_MERGE_IN_F32)
+    hipLaunchKernelGGL(attn_merge_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, *d);
+  else
+    hipLaunchKernelGGL(attn_merge_kernel<bf16>, grid, dim3(256), 0, (hipStream_t)stream, *d);
+  VP_CHECK_LAUNCH();
+  return VP_OK;
 }
 
 extern "C" int vp_linear_small_bf16(const void* x, int64_t ldx, const void* W, const void* bias, void* y,

@@ -259,6 +259,8 @@ enum VpKnob {
   VPK_ATTN_BWD_VARIANT,
   VPK_ATTN_TAIL,
   VPK_ATTN_PERSIST,
+  VPK_CFG_SHARED,
+  VPK_MOD_BATCHED,
   VPK_COUNT
 };
 const char* vp_knob(int k);

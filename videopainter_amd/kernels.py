@@ -349,14 +349,18 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tens
     row sums (include/vp_hip.h vp_attn_desc.k2_full).  k2_len: optional int32 [B] (device): only the first
     min(k2_len[b], Nk2) keys of segment 2 exist for batch row b.  l_extra: optional fp32 [B, heads, Nq]: log2 of
     extra row-sum mass per query in score units (scale * log2 e * q.k), keys with zero values outside the segments
-    (the resample processor's null keys, null_key_mass)."""
+    (the resample processor's null keys, null_key_mass).  An fp32 `out` receives the result unrounded (VP_ATTN_OUT_F32:
+    a partial for `attention_merge`; no out_scale / accumulate)."""
     segs = [(q, "q"), (k, "k"), (v, "v"), (out, "out")]
     if (k2 is None) != (v2 is None):
         raise ValueError("k2 and v2 must be given together")
     if k2 is not None:
         segs += [(k2, "k2"), (v2, "v2")]
+    out_f32 = out.dtype == torch.float32  # an unrounded partial for attention_merge (VP_ATTN_OUT_F32)
+    if out_f32 and (accumulate or out_scale != 1.0):
+        raise ValueError("an fp32 out takes no blend (out_scale / accumulate)")
     for t, n in segs:
-        _chk(t, n)
+        _chk(t, n, torch.float32 if (t is out and out_f32) else BF16)
         if t.dim() != 3 or t.stride(-1) != 1 or t.shape[-1] != heads * 64:
             raise ValueError(f"{n} must be [B, N, heads*64] with a contiguous last dim, got {tuple(t.shape)}")
         if t.shape[0] != q.shape[0]:
@@ -404,7 +408,7 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tens
             raise ValueError("lse must be contiguous fp32 [B, heads, Nq]")
         d.lse = _p(lse)
     # bounded_scores: the caller guarantees |scale * q.k| * log2 e <= SCORE_BOUND_LOG2 (score_bound_log2)
-    d.flags = ATTN_BOUNDED_SCORES if bounded_scores else 0
+    d.flags = (ATTN_BOUNDED_SCORES if bounded_scores else 0) | (ATTN_OUT_F32 if out_f32 else 0)
     L = N.lib()
     nb = L.vp_attention_workspace_bytes(C.byref(d))
     if nb < 0:
@@ -415,6 +419,33 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tens
     ev = _t0("attention")
     N.check(L.vp_attention_fwd_bf16_ws(C.byref(d), _p(ws), nb, _stream()), "vp_attention_fwd_bf16_ws")
     _t1("attention", ev)
+    return out
+
+
+def attention_merge(o_a: torch.Tensor, lse_a: torch.Tensor, o_b: torch.Tensor, lse_b: torch.Tensor,
+                    out: torch.Tensor, heads: int) -> torch.Tensor:
+    """out = (2^lse_a o_a + 2^lse_b o_b) / (2^lse_a + 2^lse_b) per (batch, head, query): two attention partials over
+    disjoint key sets merged into the attention over their union (vp_attention_merge_bf16).  o_a / o_b / out:
+    [B, Nq, heads*64] views (contiguous last dim), out bf16, o_a / o_b both bf16 or both fp32 (the unrounded partials
+    `attention` writes into an fp32 `out`: the merge then rounds once, like a single call); lse_a / lse_b: fp32
+    [B, heads, Nq], the `lse` output of `attention`.  An input may be an `expand`ed single batch row (batch stride 0)."""
+    B, Nq = out.shape[0], out.shape[1]
+    in_f32 = o_a.dtype == torch.float32
+    for t, n in ((o_a, "o_a"), (o_b, "o_b"), (out, "out")):
+        _chk(t, n, torch.float32 if (in_f32 and t is not out) else BF16)
+        if t.dim() != 3 or t.stride(-1) != 1 or tuple(t.shape) != (B, Nq, heads * 64):
+            raise ValueError(f"{n} must be [{B}, {Nq}, {heads * 64}] with a contiguous last dim, got {tuple(t.shape)}")
+    for t, n in ((lse_a, "lse_a"), (lse_b, "lse_b")):
+        _chk(t, n, torch.float32)
+        if tuple(t.shape) != (B, heads, Nq) or t.stride(2) != 1 or (Nq > 1 and t.stride(1) != Nq):
+            raise ValueError(f"{n} must be fp32 [{B}, {heads}, {Nq}] with contiguous rows, got {tuple(t.shape)}")
+    d = N.AttnMergeDesc()
+    d.B, d.H, d.Nq, d.head_dim = B, heads, Nq, 64
+    d.Oa, d.oa_sb, d.oa_sn, d.lse_a, d.la_sb = _p(o_a), o_a.stride(0), o_a.stride(1), _p(lse_a), lse_a.stride(0)
+    d.Ob, d.ob_sb, d.ob_sn, d.lse_b, d.lb_sb = _p(o_b), o_b.stride(0), o_b.stride(1), _p(lse_b), lse_b.stride(0)
+    d.O, d.o_sb, d.o_sn = _p(out), out.stride(0), out.stride(1)
+    d.flags = 1 if in_f32 else 0  # VP_MERGE_IN_F32
+    N.check(N.lib().vp_attention_merge_bf16(C.byref(d), _stream()), "vp_attention_merge_bf16")
     return out
 
 
@@ -504,6 +535,7 @@ def attention_bwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Te
 
 LOG2E = 1.4426950408889634
 ATTN_BOUNDED_SCORES = 1      # include/vp_hip.h VP_ATTN_BOUNDED_SCORES
+ATTN_OUT_F32 = 2             # include/vp_hip.h VP_ATTN_OUT_F32
 SCORE_BOUND_LOG2 = 60.0      # include/vp_hip.h VP_ATTN_SCORE_BOUND
 
 
@@ -813,6 +845,55 @@ def linear_small(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Ten
     out = torch.empty(M, Nn, device=x.device, dtype=BF16) if out is None else out
     N.check(N.lib().vp_linear_small_bf16(_p(x), x.stride(0), _p(weight), _p(bias), _p(out), out.stride(0), M, Nn, K,
                                          act_in, act_out, _stream()), "vp_linear_small_bf16")
+    return out
+
+
+class LinearGroupTable:
+    """The device table of vp_linear_small_batched_bf16: (weight, bias) pointers of G linears of one shape.  `key`
+    names the parameters' storage; a holder rebuilds the table when `key_of` of its linears no longer equals it (a
+    weight reload, a LoRA attach or fold that replaced a tensor, enable_fp8 — anything that moves a data_ptr)."""
+
+    def __init__(self, linears):
+        self.key = self.key_of(linears)
+        w0 = linears[0].weight
+        self.G, (self.N, self.K) = len(linears), w0.shape
+        host = (N.LinearGroup * self.G)()
+        for g, lin in enumerate(linears):
+            _chk(lin.weight, "weight")
+            if tuple(lin.weight.shape) != (self.N, self.K) or not lin.weight.is_contiguous() or \
+                    lin.weight.data_ptr() % 16 or lin.weight.device != w0.device:
+                raise ValueError("batched linears need contiguous, 16-byte aligned weights of one shape on one device")
+            if lin.bias is not None:
+                _chk(lin.bias, "bias")
+            host[g].W, host[g].bias = _p(lin.weight), _p(lin.bias)
+        raw = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8)
+        self.table = raw.to(w0.device)  # (synchronous copy from pageable memory: the host bytes may go at once)
+
+    @staticmethod
+    def key_of(linears):
+        return tuple((lin.weight.data_ptr(), None if lin.bias is None else lin.bias.data_ptr()) for lin in linears)
+
+    @classmethod
+    def cached(cls, holder: dict, linears) -> "LinearGroupTable":
+        """The table of `linears` kept in `holder` (a model's __dict__), rebuilt when a parameter's storage moved."""
+        tab = holder.get("_vp_linear_group_table")
+        if tab is None or tab.key != cls.key_of(linears):
+            tab = holder["_vp_linear_group_table"] = cls(linears)
+        return tab
+
+
+def linear_small_batched(x: torch.Tensor, table: LinearGroupTable, act_in: int = ACT_NONE,
+                         act_out: int = ACT_NONE) -> torch.Tensor:
+    """[G, M, N]: out[g] = linear_small(x, W_g, b_g, act_in, act_out) for the table's G linears, in one launch and
+    bit-equal to the separate calls (M <= 2, K <= 512: the shapes of the AdaLN modulation linears)."""
+    _chk(x, "x")
+    M, K = x.shape
+    if K != table.K or x.stride(1) != 1 or x.device != table.table.device:
+        raise ValueError(f"x must be [M, {table.K}] rows on the table's device, got {tuple(x.shape)}")
+    out = torch.empty(table.G, M, table.N, device=x.device, dtype=BF16)
+    N.check(N.lib().vp_linear_small_batched_bf16(_p(x), x.stride(0), _p(table.table), table.G, _p(out), out.stride(0),
+                                                 out.stride(1), M, table.N, K, act_in, act_out, _stream()),
+            "vp_linear_small_batched_bf16")
     return out
 
 

@@ -42,6 +42,9 @@ class WindowState:
     noise: Optional[torch.Tensor]
     old_pred: Optional[torch.Tensor] = None
     last_states: Optional[Dict[int, torch.Tensor]] = None
+    # the two CFG halves' conditioning (branch_in, mask1) is equal: with the latents and image_in, which are
+    # duplicated by construction, every model input but the text is then the same in both halves (cfg_shared_video)
+    cfg_shared: bool = False
     extra: dict = field(default_factory=dict)
 
 
@@ -81,7 +84,11 @@ class CogVideoXI2VDualInpaintAnyLHarness:
         branch_in = torch.cat([masked_video_latents.to(dev, BF16), m[:, :, :1]], dim=-3).contiguous()
         mask1 = m[:, :, :1].contiguous()
         init_mask = m.chunk(2)[0].contiguous()
-        return WindowState(latents=lat, image_in=image_in, branch_in=branch_in, mask1=mask1, init_mask=init_mask,
+        # compared once per window (one host sync), not per step
+        shared = (branch_in.shape[0] == 2 and torch.equal(branch_in[0], branch_in[1])
+                  and torch.equal(mask1[0], mask1[1]))
+        return WindowState(cfg_shared=bool(shared), latents=lat, image_in=image_in, branch_in=branch_in, mask1=mask1,
+                           init_mask=init_mask,
                            video_latents=None if video_latents is None else video_latents.to(dev, BF16).contiguous(),
                            noise=None if noise is None else noise.to(dev, BF16).contiguous())
 
@@ -116,9 +123,16 @@ class CogVideoXI2VDualInpaintAnyLHarness:
         lmi = torch.cat([lvi, st.image_in[sl]], dim=2)
         pe = prompt_embeds[sl]
         ts = torch.full((nb,), t_int, device=dev, dtype=torch.int64)
+        # both halves run here on duplicated latents, image latents and timestep; with equal conditioning only their
+        # text differs, and the models compute the halves' shared first-block work once (a model that does not
+        # declare the hint — a head-parallel view, a foreign module — is called as before)
+        shared = nb == 2 and self.cfg_pair is None and st.cfg_shared
+        hint_b = {"cfg_shared_video": True} if shared and getattr(self.branch, "takes_cfg_shared_video", False) else {}
+        hint_t = {"cfg_shared_video": True} if shared and getattr(self.transformer, "takes_cfg_shared_video",
+                                                                  False) else {}
         bs = self.branch(hidden_states=lvi, encoder_hidden_states=pe, branch_cond=st.branch_in[sl],
                          conditioning_scale=conditioning_scale, timestep=ts, image_rotary_emb=rope,
-                         attention_kwargs=attention_kwargs, return_dict=False)[0]
+                         attention_kwargs=attention_kwargs, return_dict=False, **hint_b)[0]
         akw = dict(attention_kwargs) if attention_kwargs else {}
         if prev_window_states is not None:
             akw["prev_hidden_states"] = prev_window_states
@@ -129,7 +143,7 @@ class CogVideoXI2VDualInpaintAnyLHarness:
             image_rotary_emb=rope, attention_kwargs=akw, add_first=add_first,
             branch_block_masks=st.mask1[sl] if mask_add else None,
             id_pool_resample_learnable=id_pool_resample_learnable,
-            return_hidden_states=True, return_resample_mask=True, return_dict=False)
+            return_hidden_states=True, return_resample_mask=True, return_dict=False, **hint_t)
         if capture_last_states and t_int == int(timesteps[-1]):
             st.last_states = {k: h for k, h in enumerate(hs_list)}
         del hs_list, bs

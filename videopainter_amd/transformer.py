@@ -11,6 +11,10 @@ video tokens, injection only on video tokens) is selected per row inside the ker
   -> to_out GEMM (+ gate * . + residual) -> norm2 linear -> AdaLN modulate -> FF1 GEMM (+GELU-tanh)
   -> FF2 GEMM (+ gate * . + residual + masked branch injection)
 
+(The norm linears of all blocks read silu(temb) alone: a model's forward runs them as one batched launch,
+`batched_modulations`.  With `forward(cfg_shared_video=True)` the first block computes the work its two batch rows —
+the classifier-free-guidance halves — share once, `CogVideoXBlock._attend_cfg_shared`.)
+
 With `return_hidden_states=True` every block writes its output into a fresh buffer that IS the returned
 `hidden_states_list[i]` (no copies).
 """
@@ -26,10 +30,10 @@ import torch.nn as nn
 from . import kernels as K
 from . import _native as NAT
 from .attention_processor import (Attention, CogVideoXAttnProcessor2_0, CogVideoXAttnProcessor2_0_resample,
-                                  CogVideoXAttnProcessor2_0_wo_text,
-                                  _rope_dev, _u8, project_out)
+                                  CogVideoXAttnProcessor2_0_wo_text, _fusable_norms, _rope_dev, _u8,
+                                  bounded_scores, cfg_shared_attention, project_out)
 from .embeddings import joint_sincos_pos_embedding
-from .lora import augmented_rows
+from .lora import AugmentedProjection, augmented_rows
 from .modules import Conv2dPatch, Dropout, LayerNorm, Linear, ModelMixin, _empty
 
 BF16 = torch.bfloat16
@@ -267,13 +271,60 @@ class CogVideoXBlock(nn.Module):
         attn.fp8_qk_exp = (K.qk_fp8_exponent(attn.norm_q.weight, attn.norm_q.bias, attn.scale * K.LOG2E),
                            K.qk_fp8_exponent(attn.norm_k.weight, attn.norm_k.bias))
 
+    # -- the CFG halves' shared first-block work --
+    def _cfg_shared_ok(self, x: torch.Tensor, text_len: int) -> bool:
+        """The shared path restates the plain bf16 block only: two batch rows with text, the standard processor with
+        the fused qk-norm + RoPE epilogue, no fp8 form and no unfused LoRA operand on the projections.  Anything else
+        (and VP_CFG_SHARED=0, the A/B knob) runs the plain path."""
+        a = self.attn1
+        return (NAT.knob_values.get("VP_CFG_SHARED") != "0" and x.shape[0] == 2 and 0 < text_len < x.shape[1]
+                and type(a.processor) is CogVideoXAttnProcessor2_0 and self.qkv_mx is None
+                and getattr(a, "fp8_qk_exp", None) is None and hasattr(a, "inner_dim") and a.inner_dim == x.shape[2]
+                and _fusable_norms(a) and AugmentedProjection.of((a.to_q, a.to_k, a.to_v, a.to_out[0])) is None)
+
+    def _attend_cfg_shared(self, x: torch.Tensor, text_len: int, mod1: torch.Tensor, rope) -> torch.Tensor:
+        """norm1 modulate -> QKV -> attention of a block whose two batch rows (the classifier-free-guidance halves)
+        hold the same video rows and differ in their text rows only: what the halves share is computed once.
+
+        The first N + T rows of the flat [2 N, D] view are batch 0 whole plus batch 1's text rows: the modulate and
+        the QKV GEMM (M = N + T; its epilogue takes text / video and the RoPE row from m % N) run on exactly those,
+        bit-equal to the plain path there; batch 1's video rows of xn / qkv are never written nor read.  The attention
+        over the joint keys is composed from pieces over disjoint key sets, all through strides (no copies):
+          (a) video queries x video keys of batch 0, B = 1                 -> O_v, lse_v   (the shared 97 %)
+          (b) the same queries (batch stride 0) x each half's text keys    -> O_t, lse_t
+          (c) each half's text queries x (own text keys | batch 0's video keys) -> o's text rows
+          (d) merge of (a) and (b) (vp_attention_merge_bf16)               -> o's video rows of both halves."""
+        B, N_, D = x.shape
+        T, a, H = text_len, self.attn1, self.attn1.heads
+        n1 = self.norm1.norm
+        xn = torch.empty_like(x)
+        K.adaln_modulate(x[:1], n1.weight, n1.bias, mod1[:1], T, n1.eps, out=xn[0])
+        K.adaln_modulate(x[1:, :T], n1.weight, n1.bias, mod1[1:], T, n1.eps, out=xn[1, :T])
+        qkv = torch.empty(B, N_, 3 * D, device=x.device, dtype=BF16)
+        M = N_ + T
+        K.gemm(xn.view(B * N_, D)[:M], [a.to_q.weight, a.to_k.weight, a.to_v.weight],
+               [a.to_q.bias, a.to_k.bias, a.to_v.bias], qkv.view(B * N_, 3 * D)[:M],
+               epilogue=NAT.EPI_BIAS_QKNORM_ROPE, qk_norm=(a.norm_q, a.norm_k), rope=rope, tokens_per_batch=N_,
+               text_len=T)
+        del xn
+        q, k, v = qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:]
+        o = torch.empty(B, N_, D, device=x.device, dtype=BF16)
+        cfg_shared_attention(q, k, v, o, H, T, scale=a.scale, bounded_scores=bounded_scores(a))
+        return o
+
     # -- joint-buffer fast path used by the models --
     def forward_joint(self, x: torch.Tensor, text_len: int, temb: torch.Tensor, rope=None,
                       resample_mask: Optional[torch.Tensor] = None, prev_joint: Optional[torch.Tensor] = None,
                       prev_clip_weight: Optional[float] = None, prev_resample_mask: Optional[torch.Tensor] = None,
                       inject: Optional[torch.Tensor] = None, inject_mask: Optional[torch.Tensor] = None,
-                      out: Optional[torch.Tensor] = None, attend=None, attn_save: Optional[dict] = None) -> torch.Tensor:
-        """attend: optional replacement of the processor's attention, `attend(attn, xn, text_len, rope) -> o`
+                      out: Optional[torch.Tensor] = None, attend=None, attn_save: Optional[dict] = None,
+                      mod1: Optional[torch.Tensor] = None, mod2: Optional[torch.Tensor] = None,
+                      cfg_shared_video: bool = False) -> torch.Tensor:
+        """mod1 / mod2: the norm1 / norm2 modulation vectors [B, 6D] when the model computed every block's in one
+        launch (batched_modulations); absent, the block computes its own.  cfg_shared_video: the caller's promise that
+        the two batch rows of x hold the same video rows (the CFG halves entering the model's first block) — the
+        block then computes their shared work once (_attend_cfg_shared) where it runs the plain bf16 path.
+        attend: optional replacement of the processor's attention, `attend(attn, xn, text_len, rope) -> o`
         [B, N, D] (the Ulysses head-parallel split, videopainter_amd/ulysses.py).  attn_save: a dict that receives the
         attention output "o" and its softmax statistics "lse" (a training forward keeps them for the backward,
         autograd.SAVE_ATTENTION); left empty where the attention is not the single-segment bf16 one."""
@@ -282,11 +333,17 @@ class CogVideoXBlock(nn.Module):
         processor = self.attn1.processor
         if not isinstance(processor, CogVideoXAttnProcessor2_0):
             raise ValueError(f"Unsupported processor type: {type(processor)}")
-        mod1 = self.norm1.modulation(temb)
+        if mod1 is None:
+            mod1 = self.norm1.modulation(temb)
         qkv = None
         if attend is not None and (self.qkv_mx is not None or self.out_mx is not None):
             raise NotImplementedError("the head-parallel split runs the bf16 path")
-        if self.qkv_mx is not None:
+        o = None
+        if (cfg_shared_video and attend is None and attn_save is None and prev_joint is None
+                and self._cfg_shared_ok(x, text_len)):
+            o = self._attend_cfg_shared(x, text_len, mod1, rope)
+            xn = None
+        elif self.qkv_mx is not None:
             a = self.attn1
             xq = K.adaln_modulate_mx(x, self.norm1.norm.weight, self.norm1.norm.bias, mod1, text_len,
                                      self.norm1.norm.eps)
@@ -311,14 +368,15 @@ class CogVideoXBlock(nn.Module):
         if (attn_save is not None and attend is None and type(processor) is CogVideoXAttnProcessor2_0 and pn is None
                 and qkv is None and getattr(self.attn1, "fp8_qk_exp", None) is None):
             lse = torch.empty(B, self.attn1.heads, Ntok, device=x.device, dtype=torch.float32)
-        if attend is not None:
-            o = attend(self.attn1, xn, text_len, rope, pn, prev_clip_weight, resample_mask, prev_resample_mask)
-        elif lse is not None:
-            o = processor.attend(self.attn1, xn, text_len, rope, lse_out=lse)
-            attn_save["o"], attn_save["lse"] = o, lse
-        else:
-            o = processor.attend(self.attn1, xn if xn is not None else x, text_len, rope, pn, prev_clip_weight,
-                                 resample_mask, prev_resample_mask, qkv=qkv)
+        if o is None:  # (else: the shared path attended already)
+            if attend is not None:
+                o = attend(self.attn1, xn, text_len, rope, pn, prev_clip_weight, resample_mask, prev_resample_mask)
+            elif lse is not None:
+                o = processor.attend(self.attn1, xn, text_len, rope, lse_out=lse)
+                attn_save["o"], attn_save["lse"] = o, lse
+            else:
+                o = processor.attend(self.attn1, xn if xn is not None else x, text_len, rope, pn, prev_clip_weight,
+                                     resample_mask, prev_resample_mask, qkv=qkv)
         del qkv
         del xn, pn
         x_mid = torch.empty_like(x)
@@ -333,7 +391,8 @@ class CogVideoXBlock(nn.Module):
                         resid=xf, mod=mod1, gate_chunk=2, gate_text_chunk=5, tokens_per_batch=Ntok,
                         text_len=text_len)
             del o
-        mod2 = self.norm2.modulation(temb)
+        if mod2 is None:
+            mod2 = self.norm2.modulation(temb)
         ff0 = self.ff.net[0].proj
         ff2 = self.ff.net[2]
         if out is None:
@@ -382,6 +441,7 @@ class CogVideoXTransformer3DModel(ModelMixin):
     """Drop-in for DF/models/transformers/cogvideox_transformer_3d.py:218-646."""
 
     _is_branch = False
+    takes_cfg_shared_video = True  # forward() accepts the hint (the harness passes it only to models that say so)
 
     def __init__(self, num_attention_heads: int = 30, attention_head_dim: int = 64, in_channels: int = 16,
                  out_channels: Optional[int] = 16, flip_sin_to_cos: bool = True, freq_shift: int = 0,
@@ -589,6 +649,20 @@ class CogVideoXTransformer3DModel(ModelMixin):
         from .autograd import time_embed_apply
         return time_embed_apply(self.time_embedding, temb0)
 
+    def batched_modulations(self, emb: torch.Tensor) -> Optional[torch.Tensor]:
+        """Every block's norm1 / norm2 modulation vectors in one launch: bf16 [2 L, B, 6 D], entry 2 i the norm1 and
+        2 i + 1 the norm2 modulation of block i, bit-equal to the blocks' own `modulation(emb)` calls — they all read
+        silu(emb), and one by one each is a latency-bound launch on the dependency chain between the big kernels.
+        The pointer table is cached on the model and rebuilt when a parameter's storage moves.  None (the blocks then
+        compute their own): VP_MOD_BATCHED=0 (A/B), or a shape outside the weight-streaming kernel's."""
+        blocks = self.transformer_blocks
+        if NAT.knob_values.get("VP_MOD_BATCHED") == "0" or len(blocks) == 0:
+            return None
+        if emb.shape[0] > 2 or emb.shape[1] > 512 or emb.shape[1] % 8 or emb.stride(0) % 8 or emb.data_ptr() % 16:
+            return None
+        lins = [lin for blk in blocks for lin in (blk.norm1.linear, blk.norm2.linear)]
+        return K.linear_small_batched(emb, K.LinearGroupTable.cached(self.__dict__, lins), act_in=K.ACT_SILU)
+
     def forward(self, hidden_states: torch.Tensor, encoder_hidden_states: torch.Tensor,
                 timestep: Union[int, float, torch.LongTensor], timestep_cond: Optional[torch.Tensor] = None,
                 image_rotary_emb: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
@@ -596,9 +670,14 @@ class CogVideoXTransformer3DModel(ModelMixin):
                 branch_block_masks: Optional[torch.Tensor] = None, add_first: Optional[bool] = False,
                 self_guidance_hidden_states=None, self_guidance_masks=None,
                 return_hidden_states: Optional[bool] = False, return_resample_mask: Optional[bool] = False,
-                id_pool_resample_learnable: Optional[bool] = False, return_dict: bool = True):
+                id_pool_resample_learnable: Optional[bool] = False, return_dict: bool = True,
+                cfg_shared_video: bool = False):
         """Reference :472-646.  With autograd on and a parameter or input requiring grad, the differentiable path
-        (videopainter_amd/autograd.py: gradient-checkpointed blocks on the HIP backward kernels) runs instead."""
+        (videopainter_amd/autograd.py: gradient-checkpointed blocks on the HIP backward kernels) runs instead.
+        cfg_shared_video (no reference counterpart): the caller's promise that the two batch rows are the
+        classifier-free-guidance halves of one sample — equal hidden_states and timestep, only the text differs — so
+        the first block computes their shared work once (CogVideoXBlock._attend_cfg_shared); same result up to the
+        rounding of that block's attention."""
         from . import autograd as AG
         if AG.needs_grad(self, hidden_states, encoder_hidden_states, branch_block_samples):
             if self_guidance_hidden_states is not None or self_guidance_masks is not None:
@@ -661,6 +740,7 @@ class CogVideoXTransformer3DModel(ModelMixin):
         interval = int(np.ceil(nl / len(bs))) if bs else 1
         hidden_states_list: List[torch.Tensor] = []
         ping = None
+        mods = self.batched_modulations(emb)
         for i, block in enumerate(self.transformer_blocks):
             inj = None
             if bs is not None:
@@ -683,7 +763,10 @@ class CogVideoXTransformer3DModel(ModelMixin):
             # runs without its fused injection, and vp_guide_rows_bf16 applies both)
             x = block.forward_joint(x, T, emb, rope, rm_u8, pj, prev_w if pj is not None else None,
                                     prev_mask if pj is not None else None, inj if guide is None else None,
-                                    tok_mask if (inj is not None and branch_block_masks is not None) else None, out)
+                                    tok_mask if (inj is not None and branch_block_masks is not None) else None, out,
+                                    mod1=mods[2 * i] if mods is not None else None,
+                                    mod2=mods[2 * i + 1] if mods is not None else None,
+                                    cfg_shared_video=bool(cfg_shared_video) and i == 0)
             if guide is not None:
                 xv = x[:, T:]
                 K.guide_rows(xv, guide.expand_as(xv), tok_mask, inj, inject_all=branch_block_masks is None)
