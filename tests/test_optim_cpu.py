@@ -55,6 +55,30 @@ def test_tables_match_the_c_structs():
     assert L.vp_abi_version() >= 21
 
 
+def test_pack_tables_places_every_table_on_a_16_byte_boundary():
+    from videopainter_amd.optim import pack_tables
+    from videopainter_amd.zero import RANGE_DTYPE
+    numels = [3, CHUNK + 1, 5]  # 3 tensor rows of 32 bytes, 4 chunk rows of 8 bytes, 3 range rows of 16 bytes
+    tt = build_tensor_table([16, 32, 48], [64, 80, 96], [0, 8, CHUNK + 16], numels)
+    ct = build_chunk_table(numels)
+    rt = np.zeros(3, dtype=RANGE_DTYPE)
+    rt["start"], rt["n"] = [0, 8, 24], [3, 9, 5]
+    odd = np.arange(5, dtype=np.uint8)  # a table whose size is no multiple of 16
+    tables = [tt, odd, ct, rt]
+    image, offs = pack_tables(tables)
+    assert image.dtype == np.uint8 and image.ndim == 1 and len(offs) == len(tables)
+    assert all(o % 16 == 0 for o in offs)
+    for a, o in zip(tables, offs):
+        assert image[o:o + a.nbytes].tobytes() == a.tobytes()  # byte for byte, no overlap with the next table
+    assert offs == sorted(offs) and all(o + a.nbytes <= n for a, o, n in zip(tables, offs, offs[1:] + [image.size]))
+    _, two = pack_tables([tt, ct])
+    assert two == [0, len(numels) * 32]  # the single-GPU layout: the chunk table right behind the tensor rows
+    image, offs = pack_tables([])
+    assert image.size == 0 and offs == []
+    image, offs = pack_tables([build_tensor_table([], [], [], []), build_chunk_table([]), np.zeros(0, RANGE_DTYPE)])
+    assert image.size == 0 and offs == [0, 0, 0]
+
+
 def test_entry_points_reject_bad_arguments_without_a_gpu():
     L = N.lib()
     p = 4096  # a non-null "pointer": every call below must return before any launch

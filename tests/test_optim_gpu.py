@@ -247,35 +247,38 @@ def test_zero_grads_in_the_update_pass():
 
 def test_unaligned_views_take_the_scalar_paths():
     """Parameters / gradients that are slices at odd element offsets (no common 16-byte phase, or a shared non-zero
-    one) run the scalar head / whole-chunk scalar path: the same per-element arithmetic, bit-identical results."""
+    one) run the scalar head / whole-chunk scalar path: the same per-element arithmetic, bit-identical results.
+    Offsets (4, 4) share a phase the fp32 state can follow (a head of 4 elements, then the vector body, then a tail);
+    3 elements give the norm and the clip a head of 5; sizes below 8, 9 and CHUNK + 1 give pieces of fewer elements
+    than one vector, a vector with a one-element tail, and a second chunk of one element."""
     from videopainter_amd import FusedAdamW, clip_grad_norm_, get_gradient_norm
     from videopainter_amd.optim import CHUNK
     g = torch.Generator().manual_seed(5)
-    n = CHUNK + 37
-    w = (torch.randn(n, generator=g) * 0.02).to(BF16).to(dev)
-    gr = (torch.randn(n, generator=g) * 1e-3).to(BF16).to(dev)
-    res = []
-    for po, go in ((0, 0), (3, 3), (3, 5), (1, 0)):
-        pbuf = torch.zeros(n + 16, device=dev, dtype=BF16)
-        gbuf = torch.zeros(n + 16, device=dev, dtype=BF16)
-        p = torch.nn.Parameter(pbuf[po:po + n])
-        p.data.copy_(w)
-        p.grad = gbuf[go:go + n]
-        p.grad.copy_(gr)
-        opt = FusedAdamW([p], lr=1e-5, **HYP)
-        opt.step()
-        nrm = get_gradient_norm([p])
-        clip_grad_norm_([p], 0.01)
-        coef = torch.clamp(0.01 / (nrm + 1e-6), max=1.0)
-        assert torch.equal(p.grad, (gr.float() * coef).to(BF16))
-        want = float(gr.double().norm())
-        assert abs(float(nrm) - want) / want <= 1e-5
-        # nothing outside the views was written
-        assert not pbuf[:po].any() and not pbuf[po + n:].any() and not gbuf[:go].any() and not gbuf[go + n:].any()
-        res.append([p.detach().clone(), opt.state[p]["master"].clone(), opt.state[p]["exp_avg"].clone(),
-                    opt.state[p]["exp_avg_sq"].clone()])
-    assert all(same(r, res[0]) for r in res[1:])
-    assert not torch.equal(res[0][1], w.float())
+    for n in (CHUNK + 37, CHUNK + 1, 9, 7, 1):
+        w = (torch.randn(n, generator=g) * 0.02).to(BF16).to(dev)
+        gr = (torch.randn(n, generator=g) * 1e-3).to(BF16).to(dev)
+        res = []
+        for po, go in ((0, 0), (3, 3), (3, 5), (1, 0), (4, 4)):
+            pbuf = torch.zeros(n + 16, device=dev, dtype=BF16)
+            gbuf = torch.zeros(n + 16, device=dev, dtype=BF16)
+            p = torch.nn.Parameter(pbuf[po:po + n])
+            p.data.copy_(w)
+            p.grad = gbuf[go:go + n]
+            p.grad.copy_(gr)
+            opt = FusedAdamW([p], lr=1e-5, **HYP)
+            opt.step()
+            nrm = get_gradient_norm([p])
+            clip_grad_norm_([p], 0.01)
+            coef = torch.clamp(0.01 / (nrm + 1e-6), max=1.0)
+            assert torch.equal(p.grad, (gr.float() * coef).to(BF16))
+            want = float(gr.double().norm())
+            assert abs(float(nrm) - want) / want <= 1e-5
+            # nothing outside the views was written
+            assert not pbuf[:po].any() and not pbuf[po + n:].any() and not gbuf[:go].any() and not gbuf[go + n:].any()
+            res.append([p.detach().clone(), opt.state[p]["master"].clone(), opt.state[p]["exp_avg"].clone(),
+                        opt.state[p]["exp_avg_sq"].clone()])
+        assert all(same(r, res[0]) for r in res[1:]), n
+        assert not torch.equal(res[0][1], w.float())
 
 
 # ------------------------------------------------------------------------------------------------------------------

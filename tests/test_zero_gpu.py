@@ -434,34 +434,38 @@ def test_checkpoint_interchange():
 
 def test_unaligned_views_take_the_scalar_paths():
     """Parameters / gradients that are slices at odd element offsets run the scalar head / whole-chunk scalar paths of
-    pack and unpack: bit-identical to FusedAdamW on aligned tensors, and nothing outside the views is written."""
+    pack and unpack: bit-identical to FusedAdamW on aligned tensors, and nothing outside the views is written.
+    Offsets (4, 4) give pack a head of 4 elements before its vector body (the fp32 staging can follow that phase);
+    sizes below 8, 9 and CHUNK + 1 give pieces (chunks and ranges) of fewer elements than one vector, a vector with a
+    one-element tail, and a second piece of one element."""
     from videopainter_amd import FusedAdamW, ShardedFusedAdamW
     from videopainter_amd.distributed import LocalComm
     from videopainter_amd.optim import CHUNK
     g = torch.Generator().manual_seed(5)
-    n = CHUNK + 37
-    w = (torch.randn(n, generator=g) * 0.02).to(BF16).to(dev)
-    gr = (torch.randn(n, generator=g) * 1e-3).to(BF16).to(dev)
-    p0 = torch.nn.Parameter(w.clone())
-    p0.grad = gr.clone()
-    ref = FusedAdamW([p0], lr=1e-5, **HYP)
-    ref.step()
-    for po, go in ((0, 0), (3, 3), (3, 5), (1, 0)):
-        pbuf = torch.zeros(n + 16, device=dev, dtype=BF16)
-        gbuf = torch.zeros(n + 16, device=dev, dtype=BF16)
-        p = torch.nn.Parameter(pbuf[po:po + n])
-        p.data.copy_(w)
-        p.grad = gbuf[go:go + n]
-        p.grad.copy_(gr)
-        opt = ShardedFusedAdamW([p], lr=1e-5, **HYP, comm=LocalComm(1), rank=0, zero_grads=(go == 5))
-        opt.step()
-        assert torch.equal(p.detach(), p0.detach()), (po, go)
-        st = ref.state[p0]
-        assert torch.equal(opt.master_shard[:n], st["master"]) and torch.equal(opt.exp_avg_shard[:n], st["exp_avg"])
-        assert torch.equal(opt.exp_avg_sq_shard[:n], st["exp_avg_sq"])
-        assert not pbuf[:po].any() and not pbuf[po + n:].any() and not gbuf[:go].any() and not gbuf[go + n:].any()
-        assert torch.equal(p.grad, torch.zeros_like(gr) if go == 5 else gr)
-    assert not torch.equal(ref.state[p0]["master"], w.float())
+    for n in (CHUNK + 37, CHUNK + 1, 9, 7, 1):
+        w = (torch.randn(n, generator=g) * 0.02).to(BF16).to(dev)
+        gr = (torch.randn(n, generator=g) * 1e-3).to(BF16).to(dev)
+        p0 = torch.nn.Parameter(w.clone())
+        p0.grad = gr.clone()
+        ref = FusedAdamW([p0], lr=1e-5, **HYP)
+        ref.step()
+        for po, go in ((0, 0), (3, 3), (3, 5), (1, 0), (4, 4)):
+            pbuf = torch.zeros(n + 16, device=dev, dtype=BF16)
+            gbuf = torch.zeros(n + 16, device=dev, dtype=BF16)
+            p = torch.nn.Parameter(pbuf[po:po + n])
+            p.data.copy_(w)
+            p.grad = gbuf[go:go + n]
+            p.grad.copy_(gr)
+            opt = ShardedFusedAdamW([p], lr=1e-5, **HYP, comm=LocalComm(1), rank=0, zero_grads=(go >= 4))
+            opt.step()
+            assert torch.equal(p.detach(), p0.detach()), (n, po, go)
+            st = ref.state[p0]
+            assert torch.equal(opt.master_shard[:n], st["master"])
+            assert torch.equal(opt.exp_avg_shard[:n], st["exp_avg"])
+            assert torch.equal(opt.exp_avg_sq_shard[:n], st["exp_avg_sq"])
+            assert not pbuf[:po].any() and not pbuf[po + n:].any() and not gbuf[:go].any() and not gbuf[go + n:].any()
+            assert torch.equal(p.grad, torch.zeros_like(gr) if go >= 4 else gr)
+        assert not torch.equal(ref.state[p0]["master"], w.float())
 
 
 def test_reallocated_gradients():

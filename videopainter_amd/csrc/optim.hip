@@ -3,7 +3,7 @@
 // is memory-bound streaming: one workgroup per VP_MT_CHUNK elements of one tensor, 16-byte loads / stores in the
 // body, scalar head / tail.  Reductions are two-stage (a partial per chunk in its own slot, then one workgroup that
 // sums the slots in a fixed order): no float atomics, bit-identical run to run.
-#include "optim_common.h"  // shared with csrc/zero.hip: workgroup sum, chunk decoding, adam_element, the finaliser
+#include "optim_common.h"  // shared with csrc/zero.hip: stream_piece, sqnorm_piece, adam_piece, the finaliser
 
 namespace {
 
@@ -13,42 +13,9 @@ using namespace vp_optim;
 __global__ __launch_bounds__(OT) void mt_sqnorm_kernel(const vp_mt_tensor* __restrict__ tensors,
                                                        const vp_mt_chunk* __restrict__ chunks,
                                                        float* __restrict__ partials, int* __restrict__ flags) {
-#pragma clang fp contract(off)
-  __shared__ float red[OT / 64];
-  __shared__ int bad_any;
   const ChunkRange r = chunk_range(tensors, chunks, blockIdx.x);
   const bf16* g = (const bf16*)r.t.grad + r.start;
-  const int head = head_of(g, r.n);
-  const int nvec = (r.n - head) / 8;
-  float acc = 0.f;
-  bool bad = false;
-  if (threadIdx.x == 0) bad_any = 0;
-  for (int i = threadIdx.x; i < head; i += OT) {
-    const bf16 x = g[i];
-    bad |= bf16_nonfinite(x);
-    acc = __builtin_fmaf(bf2f(x), bf2f(x), acc);
-  }
-  const bf16x8* gv = (const bf16x8*)(g + head);
-  for (int i = threadIdx.x; i < nvec; i += OT) {
-    const bf16x8 v = gv[i];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      bad |= bf16_nonfinite(v[e]);
-      acc = __builtin_fmaf(bf2f(v[e]), bf2f(v[e]), acc);
-    }
-  }
-  for (int i = head + nvec * 8 + threadIdx.x; i < r.n; i += OT) {
-    const bf16 x = g[i];
-    bad |= bf16_nonfinite(x);
-    acc = __builtin_fmaf(bf2f(x), bf2f(x), acc);
-  }
-  __syncthreads();
-  if (bad) bad_any = 1;  // (every writer stores the same value)
-  const float s = block_sum(acc, red);
-  if (threadIdx.x == 0) {
-    partials[blockIdx.x] = s;
-    flags[blockIdx.x] = bad_any;
-  }
+  sqnorm_piece(g, head_of(g, r.n), r.n, partials, flags);
 }
 
 // ---- a. stage 2: one workgroup; thread t sums slots t, t + OT, ... in order, then the fixed block sum ----
@@ -56,9 +23,7 @@ __global__ __launch_bounds__(OT) void optim_finalize_kernel(const float* __restr
                                                             const int* __restrict__ flags, int n, float max_norm,
                                                             double beta1, double beta2, int skip_nonfinite,
                                                             int advance_step, vp_optim_scalars* __restrict__ sc) {
-  __shared__ float red[OT / 64];
-  __shared__ int bad_any;
-  optim_finalize_body(partials, flags, 1, n, max_norm, beta1, beta2, skip_nonfinite, advance_step, sc, red, &bad_any);
+  optim_finalize_body(partials, flags, 1, n, max_norm, beta1, beta2, skip_nonfinite, advance_step, sc);
 }
 
 // ---- b. in-place scale by the device clip coefficient ----
@@ -69,21 +34,18 @@ __global__ __launch_bounds__(OT) void mt_scale_kernel(const vp_mt_tensor* __rest
   if (coef == 1.f) return;
   const ChunkRange r = chunk_range(tensors, chunks, blockIdx.x);
   bf16* g = (bf16*)r.t.grad + r.start;
-  const int head = head_of(g, r.n);
-  const int nvec = (r.n - head) / 8;
-  for (int i = threadIdx.x; i < head; i += OT) g[i] = f2bf(bf2f(g[i]) * coef);
-  bf16x8* gv = (bf16x8*)(g + head);
-  for (int i = threadIdx.x; i < nvec; i += OT) {
-    bf16x8 v = gv[i];
+  stream_piece<8>(
+      head_of(g, r.n), r.n, [&](int i) { g[i] = f2bf(bf2f(g[i]) * coef); },
+      [&](int o) {
+        float x[8];
+        load8(g + o, x);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = f2bf(bf2f(v[e]) * coef);
-    gv[i] = v;
-  }
-  for (int i = head + nvec * 8 + threadIdx.x; i < r.n; i += OT) g[i] = f2bf(bf2f(g[i]) * coef);
+        for (int e = 0; e < 8; ++e) x[e] *= coef;
+        store8(g + o, x);
+      });
 }
 
-// ---- c. AdamW with fp32 master weights ----
-// (AdamArgs / AdamCoef / adam_element: optim_common.h)
+// ---- c. AdamW with fp32 master weights (adam_piece: optim_common.h) ----
 __global__ __launch_bounds__(OT) void mt_adamw_kernel(const vp_mt_tensor* __restrict__ tensors,
                                                       const vp_mt_chunk* __restrict__ chunks, int chunk_begin,
                                                       float* __restrict__ master, float* __restrict__ exp_avg,
@@ -100,59 +62,11 @@ __global__ __launch_bounds__(OT) void mt_adamw_kernel(const vp_mt_tensor* __rest
   int head = head_of(g, r.n);
   if (head_of(w, r.n) != head || (((uintptr_t)(pm + head) | (uintptr_t)(mm + head) | (uintptr_t)(vm + head)) & 15))
     head = r.n;
-  const int nvec = (r.n - head) / 8;
-  const int tail0 = head + nvec * 8;
-  const bf16 zero = f2bf(0.f);
   if (sc->skipped) {  // a skipped step writes no state and no parameter
-    if (!a.zero_grads) return;
-    for (int i = threadIdx.x; i < head; i += OT) g[i] = zero;
-    bf16x8* gz = (bf16x8*)(g + head);
-    for (int i = threadIdx.x; i < nvec; i += OT) gz[i] = bf16x8{};
-    for (int i = tail0 + threadIdx.x; i < r.n; i += OT) g[i] = zero;
+    if (a.zero_grads) zero_piece(g, head, r.n);
     return;
   }
-  const AdamCoef k = adam_coef(a, sc);
-
-  auto scalar = [&](int i) {
-    float p = pm[i], m = mm[i], v = vm[i];
-    adam_element(bf2f(g[i]), p, m, v, a, k);
-    pm[i] = p;
-    mm[i] = m;
-    vm[i] = v;
-    w[i] = f2bf(p);
-    if (a.zero_grads) g[i] = zero;
-  };
-  for (int i = threadIdx.x; i < head; i += OT) scalar(i);
-  for (int i = threadIdx.x; i < nvec; i += OT) {
-    const int o = head + i * 8;
-    const bf16x8 g8 = *(const bf16x8*)(g + o);
-    f32x4 p[2], m[2], v[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      p[h] = *(const f32x4*)(pm + o + 4 * h);
-      m[h] = *(const f32x4*)(mm + o + 4 * h);
-      v[h] = *(const f32x4*)(vm + o + 4 * h);
-    }
-    bf16x8 w8;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      float pe = p[e >> 2][e & 3], me = m[e >> 2][e & 3], ve = v[e >> 2][e & 3];
-      adam_element(bf2f(g8[e]), pe, me, ve, a, k);
-      p[e >> 2][e & 3] = pe;
-      m[e >> 2][e & 3] = me;
-      v[e >> 2][e & 3] = ve;
-      w8[e] = f2bf(pe);
-    }
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      *(f32x4*)(pm + o + 4 * h) = p[h];
-      *(f32x4*)(mm + o + 4 * h) = m[h];
-      *(f32x4*)(vm + o + 4 * h) = v[h];
-    }
-    *(bf16x8*)(w + o) = w8;
-    if (a.zero_grads) *(bf16x8*)(g + o) = bf16x8{};
-  }
-  for (int i = tail0 + threadIdx.x; i < r.n; i += OT) scalar(i);
+  adam_piece(g, pm, mm, vm, w, head, r.n, a, adam_coef(a, sc));
 }
 
 // ---- y = bf16(x * *s) ----
@@ -201,7 +115,6 @@ VP_DEV float loss_element(float o, float x, float t, float mk, float sa, float s
 
 __global__ __launch_bounds__(OT) void v_loss_kernel(const LossArgs a) {
 #pragma clang fp contract(off)
-  __shared__ float red[OT / 64];
   const int b = blockIdx.y;
   int64_t t = a.timesteps[b];
   t = t < 0 ? 0 : (t >= a.n_alphas ? a.n_alphas - 1 : t);
@@ -220,7 +133,6 @@ __global__ __launch_bounds__(OT) void v_loss_kernel(const LossArgs a) {
   bf16* pd = a.dout + base;
   int head = head_of(po, n);
   if (head_of(px, n) != head || head_of(pt, n) != head || head_of(pd, n) != head) head = n;
-  const int nvec = (n - head) / 8;
   const int CHW = a.C * a.HW;
   const int64_t mbase = (int64_t)b * a.F * a.HW;
   auto mask_at = [&](int i) -> float {  // i: element inside the sample
@@ -229,34 +141,32 @@ __global__ __launch_bounds__(OT) void v_loss_kernel(const LossArgs a) {
     return a.mask_is_f32 ? ((const float*)a.mask)[mi] : bf2f(((const bf16*)a.mask)[mi]);
   };
   float q = 0.f, qm = 0.f;
-  auto scalar = [&](int i) {
-    pd[i] = f2bf(loss_element(bf2f(po[i]), bf2f(px[i]), bf2f(pt[i]), mask_at(start + i), sa, sb, lambda, gc, q, qm));
-  };
-  for (int i = threadIdx.x; i < head; i += OT) scalar(i);
-  for (int i = threadIdx.x; i < nvec; i += OT) {
-    const int o = head + i * 8;
-    const bf16x8 o8 = *(const bf16x8*)(po + o);
-    const bf16x8 x8 = *(const bf16x8*)(px + o);
-    const bf16x8 t8 = *(const bf16x8*)(pt + o);
-    bf16x8 d8;
+  stream_piece<8>(
+      head, n,
+      [&](int i) {
+        pd[i] = f2bf(loss_element(bf2f(po[i]), bf2f(px[i]), bf2f(pt[i]), mask_at(start + i), sa, sb, lambda, gc, q,
+                                  qm));
+      },
+      [&](int o) {
+        float o8[8], x8[8], t8[8], d8[8];
+        load8(po + o, o8);
+        load8(px + o, x8);
+        load8(pt + o, t8);
 #pragma unroll
-    for (int e = 0; e < 8; ++e)
-      d8[e] = f2bf(loss_element(bf2f(o8[e]), bf2f(x8[e]), bf2f(t8[e]), mask_at(start + o + e), sa, sb, lambda, gc, q,
-                                qm));
-    *(bf16x8*)(pd + o) = d8;
-  }
-  for (int i = head + nvec * 8 + threadIdx.x; i < n; i += OT) scalar(i);
-  const float s = block_sum(w * (q + lambda * qm), red);
+        for (int e = 0; e < 8; ++e)
+          d8[e] = loss_element(o8[e], x8[e], t8[e], mask_at(start + o + e), sa, sb, lambda, gc, q, qm);
+        store8(pd + o, d8);
+      });
+  const float s = block_sum(w * (q + lambda * qm));
   if (threadIdx.x == 0) a.partials[(int64_t)b * a.chunks_per_sample + blockIdx.x] = s;
 }
 
 __global__ __launch_bounds__(OT) void sum_partials_kernel(const float* __restrict__ partials, int64_t n, float scale,
                                                           float* __restrict__ out) {
 #pragma clang fp contract(off)
-  __shared__ float red[OT / 64];
   float acc = 0.f;
   for (int64_t i = threadIdx.x; i < n; i += OT) acc += partials[i];
-  const float s = block_sum(acc, red);
+  const float s = block_sum(acc);
   if (threadIdx.x == 0) out[0] = s * scale;
 }
 
@@ -277,8 +187,7 @@ extern "C" int vp_optim_finalize(const float* partials, const int32_t* flags, in
                                  double beta1, double beta2, int32_t skip_nonfinite, int32_t advance_step,
                                  vp_optim_scalars* scalars, void* stream) {
   if (!scalars || n_chunks < 0 || (n_chunks > 0 && (!partials || !flags))) return VP_ERR_ARG;
-  if (max_norm != max_norm) return VP_ERR_ARG;
-  if (advance_step && !(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0)) return VP_ERR_ARG;
+  if (!finalize_args_ok(max_norm, beta1, beta2, advance_step)) return VP_ERR_ARG;
   hipLaunchKernelGGL(optim_finalize_kernel, dim3(1), dim3(OT), 0, (hipStream_t)stream, partials, flags, n_chunks,
                      max_norm, beta1, beta2, skip_nonfinite, advance_step, scalars);
   VP_CHECK_LAUNCH();

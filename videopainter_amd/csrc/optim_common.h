@@ -1,9 +1,13 @@
-// What the optimizer kernels of csrc/optim.hip (one GPU) and csrc/zero.hip (data-parallel, sharded state) share: the
-// workgroup shape, the fixed-order workgroup sum, the chunk decoding of the multi-tensor tables, the per-element AdamW
-// update and the finaliser of the gradient norm.  The two AdamW kernels call the SAME adam_element() with the same
-// AdamArgs / AdamCoef, and every multiply-add in it is spelled out with contraction off, so they cannot drift apart by
-// a fused multiply-add: a world-1 sharded step is bit-identical to the single-GPU step.
+// What the optimizer kernels of csrc/optim.hip (one GPU) and csrc/zero.hip (data-parallel, sharded state) share —
+// everything but the decoding of their tables and the choice of each piece's scalar head: the workgroup shape and its
+// fixed-order sum, stream_piece (scalar head / 16-byte body / scalar tail of one piece), the zero fill, the gradient
+// norm's first stage (sqnorm_piece) and finaliser, the AdamW update of one piece (adam_piece) and the host-side
+// argument checks.  Both AdamW kernels are adam_piece around the SAME adam_element(), and every multiply-add in it is
+// spelled out with contraction off, so they cannot drift apart by a fused multiply-add: a world-1 sharded step is
+// bit-identical to the single-GPU step.
 #pragma once
+#include <type_traits>
+
 #include "vp_common.h"
 
 namespace vp_optim {
@@ -12,7 +16,8 @@ constexpr int OT = 256;  // threads per workgroup; VP_MT_CHUNK = OT * 8 elements
 static_assert(VP_MT_CHUNK % (OT * 8) == 0, "a chunk is whole rounds of 8 elements per thread");
 
 // fixed-order sum over the workgroup (xor butterfly inside a wave, then the waves in order); valid in thread 0
-VP_DEV float block_sum(float v, float* red) {
+VP_DEV float block_sum(float v) {
+  __shared__ float red[OT / 64];
   v = wave_sum(v);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
@@ -25,8 +30,35 @@ VP_DEV float block_sum(float v, float* red) {
   return s;
 }
 
-VP_DEV bool bf16_nonfinite(bf16 x) { return (__builtin_bit_cast(uint16_t, x) & 0x7f80u) == 0x7f80u; }
-VP_DEV bool f32_nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+// the two element types of a gradient (bf16 from the backward, fp32 after the reduce-scatter) and their 16-byte vector
+VP_DEV bool nonfinite(bf16 x) { return (__builtin_bit_cast(uint16_t, x) & 0x7f80u) == 0x7f80u; }
+VP_DEV bool nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+VP_DEV float to_f32(bf16 x) { return bf2f(x); }
+VP_DEV float to_f32(float x) { return x; }
+template <class T>
+using vec16_t = std::conditional_t<sizeof(T) == 2, bf16x8, f32x4>;
+
+// 8 consecutive elements as fp32 (16-byte accesses: p is 16-byte aligned)
+VP_DEV void load8(const bf16* p, float (&x)[8]) {
+  const bf16x8 v = *(const bf16x8*)p;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) x[e] = bf2f(v[e]);
+}
+VP_DEV void load8(const float* p, float (&x)[8]) {
+  const f32x4 lo = *(const f32x4*)p, hi = *(const f32x4*)(p + 4);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) x[e] = lo[e], x[4 + e] = hi[e];
+}
+VP_DEV void store8(bf16* p, const float (&x)[8]) {
+  bf16x8 v;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) v[e] = f2bf(x[e]);
+  *(bf16x8*)p = v;
+}
+VP_DEV void store8(float* p, const float (&x)[8]) {
+  *(f32x4*)p = f32x4{x[0], x[1], x[2], x[3]};
+  *(f32x4*)(p + 4) = f32x4{x[4], x[5], x[6], x[7]};
+}
 
 // the element range of chunk c: tensor entry, first element, count
 struct ChunkRange {
@@ -51,6 +83,54 @@ VP_DEV int head_of(const void* p, int n) {
   if (a & 1) return n;
   const int h = (int)(((16 - (a & 15)) & 15) >> 1);
   return h < n ? h : n;
+}
+
+// ---- one piece (n <= VP_MT_CHUNK elements) over the workgroup: scalar(i) for the first `head` elements, vec(o) for
+// every whole W-element vector after them (o: its first element), scalar(i) for the tail.  head == n: all scalar. ----
+template <int W, class S, class V>
+VP_DEV void stream_piece(int head, int n, S&& scalar, V&& vec) {
+  const int nvec = (n - head) / W;
+  for (int i = threadIdx.x; i < head; i += OT) scalar(i);
+  for (int i = threadIdx.x; i < nvec; i += OT) vec(head + i * W);
+  for (int i = head + nvec * W + threadIdx.x; i < n; i += OT) scalar(i);
+}
+
+// x[0, n) = 0 (x + head on a 16-byte boundary, or head == n)
+template <class T>
+VP_DEV void zero_piece(T* __restrict__ x, int head, int n) {
+  stream_piece<16 / sizeof(T)>(
+      head, n, [&](int i) { x[i] = T(0.f); }, [&](int o) { *(vec16_t<T>*)(x + o) = vec16_t<T>{}; });
+}
+
+// ---- stage 1 of a gradient norm over one piece: the fp32 sum of squares (thread t folds its elements in index
+// order, one fma each, then the fixed block sum) and the non-finite flag of g[0, n) into slot blockIdx.x ----
+template <class T>
+VP_DEV void sqnorm_piece(const T* __restrict__ g, int head, int n, float* __restrict__ partials,
+                         int* __restrict__ flags) {
+#pragma clang fp contract(off)
+  constexpr int W = 16 / sizeof(T);
+  __shared__ int bad_any;
+  float acc = 0.f;
+  bool bad = false;
+  if (threadIdx.x == 0) bad_any = 0;
+  auto one = [&](T x) {
+    bad |= nonfinite(x);
+    acc = __builtin_fmaf(to_f32(x), to_f32(x), acc);
+  };
+  stream_piece<W>(
+      head, n, [&](int i) { one(g[i]); },
+      [&](int o) {
+        const vec16_t<T> v = *(const vec16_t<T>*)(g + o);
+#pragma unroll
+        for (int e = 0; e < W; ++e) one(v[e]);
+      });
+  __syncthreads();
+  if (bad) bad_any = 1;  // (every writer stores the same value)
+  const float s = block_sum(acc);
+  if (threadIdx.x == 0) {
+    partials[blockIdx.x] = s;
+    flags[blockIdx.x] = bad_any;
+  }
 }
 
 // ---- AdamW with fp32 master weights: the per-element update ----
@@ -78,8 +158,13 @@ inline AdamArgs adam_args(double lr, double beta1, double beta2, double eps, dou
   return a;
 }
 
+// host: the argument checks of the entry points
+inline bool betas_ok(double beta1, double beta2) { return beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0; }
 inline bool adam_hyper_ok(double lr, double beta1, double beta2, double eps, double weight_decay) {
-  return lr >= 0.0 && eps >= 0.0 && weight_decay >= 0.0 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0;
+  return lr >= 0.0 && eps >= 0.0 && weight_decay >= 0.0 && betas_ok(beta1, beta2);
+}
+inline bool finalize_args_ok(float max_norm, double beta1, double beta2, int advance_step) {
+  return max_norm == max_norm && (!advance_step || betas_ok(beta1, beta2));
 }
 
 VP_DEV AdamCoef adam_coef(const AdamArgs& a, const vp_optim_scalars* __restrict__ sc) {
@@ -101,13 +186,50 @@ VP_DEV void adam_element(float g, float& p, float& m, float& v, const AdamArgs& 
   p = p - k.step_size * (m / denom);          // param.addcdiv_(exp_avg, denom, value=-step_size)
 }
 
+// ---- the update of one piece: gradient g[0, n) (bf16, or fp32 from the reduce-scatter), master and moments in and
+// out, bf16(master) into w.  The caller picks `head` (every stream 16-byte aligned at `head`, or head == n); that
+// decides which path an element takes, not its value.  Only a bf16 gradient can be zeroed in the same pass. ----
+template <class G>
+VP_DEV void adam_piece(G* __restrict__ g, float* __restrict__ pm, float* __restrict__ mm, float* __restrict__ vm,
+                       bf16* __restrict__ w, int head, int n, const AdamArgs& a, const AdamCoef& k) {
+  constexpr bool can_zero = std::is_same_v<G, bf16>;
+  stream_piece<8>(
+      head, n,
+      [&](int i) {
+        float p = pm[i], m = mm[i], v = vm[i];
+        adam_element(to_f32(g[i]), p, m, v, a, k);
+        pm[i] = p;
+        mm[i] = m;
+        vm[i] = v;
+        w[i] = f2bf(p);
+        if constexpr (can_zero)
+          if (a.zero_grads) g[i] = f2bf(0.f);
+      },
+      [&](int o) {
+        float g8[8], p[8], m[8], v[8];
+        load8(g + o, g8);
+        load8(pm + o, p);
+        load8(mm + o, m);
+        load8(vm + o, v);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) adam_element(g8[e], p[e], m[e], v[e], a, k);
+        store8(pm + o, p);
+        store8(mm + o, m);
+        store8(vm + o, v);
+        store8(w + o, p);
+        if constexpr (can_zero)
+          if (a.zero_grads) *(bf16x8*)(g + o) = bf16x8{};
+      });
+}
+
 // ---- second stage of every reduction here (one workgroup): the fixed-order sum of n slots and the OR of their flags.
 // Thread t takes slots t, t + OT, ... in order, then the fixed block sum; slot i is partials[i * stride] /
-// flags[i * stride].  The sum is valid in thread 0, *bad_any in every thread after the call. ----
+// flags[i * stride].  The sum is valid in thread 0, *any_bad in every thread after the call. ----
 VP_DEV float sum_slots(const float* __restrict__ partials, const int* __restrict__ flags, int stride, int n,
-                       float* red, int* bad_any) {
+                       int* any_bad) {
 #pragma clang fp contract(off)
-  if (threadIdx.x == 0) *bad_any = 0;
+  __shared__ int bad_any;
+  if (threadIdx.x == 0) bad_any = 0;
   float acc = 0.f;
   bool bad = false;
   for (int i = threadIdx.x; i < n; i += OT) {
@@ -115,20 +237,22 @@ VP_DEV float sum_slots(const float* __restrict__ partials, const int* __restrict
     bad |= flags[(int64_t)i * stride] != 0;
   }
   __syncthreads();
-  if (bad) *bad_any = 1;
-  return block_sum(acc, red);
+  if (bad) bad_any = 1;
+  const float s = block_sum(acc);
+  *any_bad = bad_any;
+  return s;
 }
 
 // ---- the finaliser of the gradient norm: sum_slots, then the scalars block (stride 1: the per-chunk workspace of one
 // GPU; stride 2: the (sum, flag) records of the ranks, in rank order) ----
 VP_DEV void optim_finalize_body(const float* __restrict__ partials, const int* __restrict__ flags, int stride, int n,
                                 float max_norm, double beta1, double beta2, int skip_nonfinite, int advance_step,
-                                vp_optim_scalars* __restrict__ sc, float* red, int* bad_any) {
+                                vp_optim_scalars* __restrict__ sc) {
 #pragma clang fp contract(off)
-  const float s = sum_slots(partials, flags, stride, n, red, bad_any);
+  int nonfinite;
+  const float s = sum_slots(partials, flags, stride, n, &nonfinite);
   if (threadIdx.x != 0) return;
   const float norm = sqrtf(s);
-  const int nonfinite = *bad_any;
   sc->grad_norm = norm;
   sc->nonfinite = nonfinite;
   float coef = 1.f;

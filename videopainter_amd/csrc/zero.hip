@@ -25,38 +25,27 @@ __global__ __launch_bounds__(OT) void zero_pack_kernel(const vp_mt_tensor* __res
   float* out = flat + o;
   bf16* g = (bf16*)r.t.grad;
   if (g == nullptr) {
-    const int head = ((uintptr_t)out & 15) ? r.n : 0;
-    const int nvec = (r.n - head) / 4;
-    for (int i = threadIdx.x; i < head; i += OT) out[i] = 0.f;
-    for (int i = threadIdx.x; i < nvec; i += OT) *(f32x4*)(out + head + 4 * i) = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int i = head + nvec * 4 + threadIdx.x; i < r.n; i += OT) out[i] = 0.f;
+    zero_piece(out, ((uintptr_t)out & 15) ? r.n : 0, r.n);
     return;
   }
   g += r.start;
   int head = head_of(g, r.n);
   if ((uintptr_t)(out + head) & 15) head = r.n;
-  const int nvec = (r.n - head) / 8;
-  const int tail0 = head + nvec * 8;
   const bf16 zero = f2bf(0.f);
-  auto scalar = [&](int i) {
-    out[i] = bf2f(g[i]) * inv_world;
-    if (zero_grads) g[i] = zero;
-  };
-  for (int i = threadIdx.x; i < head; i += OT) scalar(i);
-  for (int i = threadIdx.x; i < nvec; i += OT) {
-    const int e0 = head + i * 8;
-    const bf16x8 g8 = *(const bf16x8*)(g + e0);
-    f32x4 lo, hi;
+  stream_piece<8>(
+      head, r.n,
+      [&](int i) {
+        out[i] = bf2f(g[i]) * inv_world;
+        if (zero_grads) g[i] = zero;
+      },
+      [&](int e0) {
+        float x[8];
+        load8(g + e0, x);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      lo[e] = bf2f(g8[e]) * inv_world;
-      hi[e] = bf2f(g8[4 + e]) * inv_world;
-    }
-    *(f32x4*)(out + e0) = lo;
-    *(f32x4*)(out + e0 + 4) = hi;
-    if (zero_grads) *(bf16x8*)(g + e0) = bf16x8{};
-  }
-  for (int i = tail0 + threadIdx.x; i < r.n; i += OT) scalar(i);
+        for (int e = 0; e < 8; ++e) x[e] *= inv_world;
+        store8(out + e0, x);
+        if (zero_grads) *(bf16x8*)(g + e0) = bf16x8{};
+      });
 }
 
 // ---- 4. unpack: param[i] = flat[state_off + i] for the tensors that had a gradient (nothing in a skipped step) ----
@@ -73,10 +62,8 @@ __global__ __launch_bounds__(OT) void zero_unpack_kernel(const vp_mt_tensor* __r
   bf16* w = (bf16*)r.t.param + r.start;
   int head = head_of(w, r.n);
   if (head_of(in, r.n) != head) head = r.n;
-  const int nvec = (r.n - head) / 8;
-  for (int i = threadIdx.x; i < head; i += OT) w[i] = in[i];
-  for (int i = threadIdx.x; i < nvec; i += OT) *(bf16x8*)(w + head + i * 8) = *(const bf16x8*)(in + head + i * 8);
-  for (int i = head + nvec * 8 + threadIdx.x; i < r.n; i += OT) w[i] = in[i];
+  stream_piece<8>(
+      head, r.n, [&](int i) { w[i] = in[i]; }, [&](int e0) { *(bf16x8*)(w + e0) = *(const bf16x8*)(in + e0); });
 }
 
 // the piece of the shard range c describes (n = 0 when it does not fit the shard: nothing is read or written)
@@ -96,50 +83,17 @@ VP_DEV ShardRange shard_range(const vp_zero_range* __restrict__ ranges, int c, i
 __global__ __launch_bounds__(OT) void zero_sqnorm_kernel(const vp_zero_range* __restrict__ ranges,
                                                          const float* __restrict__ grad, int64_t per,
                                                          float* __restrict__ partials, int* __restrict__ flags) {
-#pragma clang fp contract(off)
-  __shared__ float red[OT / 64];
-  __shared__ int bad_any;
   const ShardRange r = shard_range(ranges, blockIdx.x, per);
   const float* g = grad + r.start;
-  const int head = ((uintptr_t)g & 15) ? r.n : 0;
-  const int nvec = (r.n - head) / 4;
-  float acc = 0.f;
-  bool bad = false;
-  if (threadIdx.x == 0) bad_any = 0;
-  for (int i = threadIdx.x; i < head; i += OT) {
-    const float x = g[i];
-    bad |= f32_nonfinite(x);
-    acc = __builtin_fmaf(x, x, acc);
-  }
-  for (int i = threadIdx.x; i < nvec; i += OT) {
-    const f32x4 v = *(const f32x4*)(g + head + 4 * i);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      bad |= f32_nonfinite(v[e]);
-      acc = __builtin_fmaf(v[e], v[e], acc);
-    }
-  }
-  for (int i = head + nvec * 4 + threadIdx.x; i < r.n; i += OT) {
-    const float x = g[i];
-    bad |= f32_nonfinite(x);
-    acc = __builtin_fmaf(x, x, acc);
-  }
-  __syncthreads();
-  if (bad) bad_any = 1;  // (every writer stores the same value)
-  const float s = block_sum(acc, red);
-  if (threadIdx.x == 0) {
-    partials[blockIdx.x] = s;
-    flags[blockIdx.x] = bad_any;
-  }
+  sqnorm_piece(g, ((uintptr_t)g & 15) ? r.n : 0, r.n, partials, flags);
 }
 
 // ---- 2. stage 2 (one workgroup): this rank's (sum, flag) record from its per-range slots, in a fixed order ----
 __global__ __launch_bounds__(OT) void zero_record_kernel(const float* __restrict__ partials,
                                                          const int* __restrict__ flags, int n,
                                                          vp_zero_record* __restrict__ rec) {
-  __shared__ float red[OT / 64];
-  __shared__ int bad_any;
-  const float s = sum_slots(partials, flags, 1, n, red, &bad_any);  // (optim_common.h: the finaliser's own sum)
+  int bad_any;
+  const float s = sum_slots(partials, flags, 1, n, &bad_any);  // (optim_common.h: the finaliser's own sum)
   if (threadIdx.x != 0) return;
   rec->sqsum = s;
   rec->nonfinite = bad_any;
@@ -150,10 +104,8 @@ __global__ __launch_bounds__(OT) void zero_finalize_kernel(const vp_zero_record*
                                                            float max_norm, double beta1, double beta2,
                                                            int skip_nonfinite, vp_optim_scalars* __restrict__ sc) {
   static_assert(sizeof(vp_zero_record) == 8, "a record is one (fp32 sum, int32 flag) pair");
-  __shared__ float red[OT / 64];
-  __shared__ int bad_any;
   optim_finalize_body((const float*)records, (const int*)records + 1, 2, world, max_norm, beta1, beta2,
-                      skip_nonfinite, 1, sc, red, &bad_any);
+                      skip_nonfinite, 1, sc);
 }
 
 // ---- 3. AdamW on this rank's shard: fp32 gradient, master and moments in, bf16(p) out ----
@@ -171,44 +123,7 @@ __global__ __launch_bounds__(OT) void zero_adamw_kernel(const vp_zero_range* __r
   bf16* w = param + r.start;
   // (range starts are multiples of 8 elements: with 16-byte aligned buffers every stream is in phase)
   const bool vec = ((((uintptr_t)g | (uintptr_t)pm | (uintptr_t)mm | (uintptr_t)vm | (uintptr_t)w) & 15) == 0);
-  const int nvec = vec ? r.n / 8 : 0;
-  const AdamCoef k = adam_coef(a, sc);
-  for (int i = threadIdx.x; i < nvec; i += OT) {
-    const int o = i * 8;
-    f32x4 gg[2], p[2], m[2], v[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      gg[h] = *(const f32x4*)(g + o + 4 * h);
-      p[h] = *(const f32x4*)(pm + o + 4 * h);
-      m[h] = *(const f32x4*)(mm + o + 4 * h);
-      v[h] = *(const f32x4*)(vm + o + 4 * h);
-    }
-    bf16x8 w8;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      float pe = p[e >> 2][e & 3], me = m[e >> 2][e & 3], ve = v[e >> 2][e & 3];
-      adam_element(gg[e >> 2][e & 3], pe, me, ve, a, k);
-      p[e >> 2][e & 3] = pe;
-      m[e >> 2][e & 3] = me;
-      v[e >> 2][e & 3] = ve;
-      w8[e] = f2bf(pe);
-    }
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      *(f32x4*)(pm + o + 4 * h) = p[h];
-      *(f32x4*)(mm + o + 4 * h) = m[h];
-      *(f32x4*)(vm + o + 4 * h) = v[h];
-    }
-    *(bf16x8*)(w + o) = w8;
-  }
-  for (int i = nvec * 8 + threadIdx.x; i < r.n; i += OT) {
-    float p = pm[i], m = mm[i], v = vm[i];
-    adam_element(g[i], p, m, v, a, k);
-    pm[i] = p;
-    mm[i] = m;
-    vm[i] = v;
-    w[i] = f2bf(p);
-  }
+  adam_piece(g, pm, mm, vm, w, vec ? 0 : r.n, r.n, a, adam_coef(a, sc));
 }
 
 }  // namespace
@@ -256,8 +171,7 @@ extern "C" int vp_zero_shard_sqnorm(const vp_zero_range* ranges, int32_t n_range
 extern "C" int vp_zero_finalize(const vp_zero_record* records, int32_t world, float max_norm, double beta1,
                                 double beta2, int32_t skip_nonfinite, vp_optim_scalars* scalars, void* stream) {
   if (!records || !scalars || world <= 0) return VP_ERR_ARG;
-  if (max_norm != max_norm) return VP_ERR_ARG;
-  if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0)) return VP_ERR_ARG;
+  if (!finalize_args_ok(max_norm, beta1, beta2, 1)) return VP_ERR_ARG;
   hipLaunchKernelGGL(zero_finalize_kernel, dim3(1), dim3(OT), 0, (hipStream_t)stream, records, world, max_norm, beta1,
                      beta2, skip_nonfinite, scalars);
   VP_CHECK_LAUNCH();

@@ -1408,14 +1408,24 @@ def wgrad(dy: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
 MT_CHUNK = N.MT_CHUNK
 
 
+def _chk_scalars(scalars: torch.Tensor, who: str) -> None:
+    _chk(scalars, "scalars", torch.int32)
+    if scalars.numel() * 4 < C.sizeof(N.OptimScalars):
+        raise ValueError(f"{who}: scalars block too small")
+
+
+def _chk_slots(partials: torch.Tensor, flags: torch.Tensor, n: int, who: str, what: str) -> None:
+    _chk(partials, "partials", torch.float32)
+    _chk(flags, "flags", torch.int32)
+    if partials.numel() < n or flags.numel() < n:
+        raise ValueError(f"{who}: partials / flags hold fewer than {what} slots")
+
+
 def mt_grad_sqnorm(tensors: torch.Tensor, chunks: torch.Tensor, n_chunks: int, partials: torch.Tensor,
                    flags: torch.Tensor) -> None:
     """Stage 1 of the gradient norm over the device tables `tensors` / `chunks` (optim.MultiTensorTables): one fp32
     sum of squares and one non-finite flag per chunk."""
-    _chk(partials, "partials", torch.float32)
-    _chk(flags, "flags", torch.int32)
-    if partials.numel() < n_chunks or flags.numel() < n_chunks:
-        raise ValueError("mt_grad_sqnorm: partials / flags hold fewer than n_chunks slots")
+    _chk_slots(partials, flags, n_chunks, "mt_grad_sqnorm", "n_chunks")
     N.check(N.lib().vp_mt_grad_sqnorm_bf16(_p(tensors), _p(chunks), n_chunks, _p(partials), _p(flags), _stream()),
             "vp_mt_grad_sqnorm_bf16")
 
@@ -1425,9 +1435,7 @@ def optim_finalize(partials: torch.Tensor, flags: torch.Tensor, n_chunks: int, s
                    advance_step: bool = False) -> None:
     """Stage 2: the norm, the non-finite flag, the clip coefficient and (advance_step) the step counter and bias
     corrections into the int32[8] `scalars` block (N.OptimScalars)."""
-    _chk(scalars, "scalars", torch.int32)
-    if scalars.numel() * 4 < C.sizeof(N.OptimScalars):
-        raise ValueError("optim_finalize: scalars block too small")
+    _chk_scalars(scalars, "optim_finalize")
     N.check(N.lib().vp_optim_finalize(_p(partials), _p(flags), n_chunks, max_norm, betas[0], betas[1],
                                       int(skip_nonfinite), int(advance_step), _p(scalars), _stream()),
             "vp_optim_finalize")
@@ -1435,7 +1443,7 @@ def optim_finalize(partials: torch.Tensor, flags: torch.Tensor, n_chunks: int, s
 
 def mt_scale(tensors: torch.Tensor, chunks: torch.Tensor, n_chunks: int, scalars: torch.Tensor) -> None:
     """grad = bf16(grad * clip_coef) in place over the tables' gradients (clip_coef on the device, in `scalars`)."""
-    _chk(scalars, "scalars", torch.int32)
+    _chk_scalars(scalars, "mt_scale")
     N.check(N.lib().vp_mt_scale_bf16(_p(tensors), _p(chunks), n_chunks, _p(scalars), _stream()), "vp_mt_scale_bf16")
 
 
@@ -1445,7 +1453,7 @@ def mt_adamw(tensors: torch.Tensor, chunks: torch.Tensor, chunk_begin: int, n_ch
     """The AdamW update of chunks [chunk_begin, chunk_begin + n_chunks) (one parameter group)."""
     for t, n in ((master, "master"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
         _chk(t, n, torch.float32)
-    _chk(scalars, "scalars", torch.int32)
+    _chk_scalars(scalars, "mt_adamw")
     N.check(N.lib().vp_mt_adamw_bf16(_p(tensors), _p(chunks), chunk_begin, n_chunks, _p(master), _p(exp_avg),
                                      _p(exp_avg_sq), _p(scalars), lr, betas[0], betas[1], eps, weight_decay,
                                      int(use_clip), int(zero_grads), _stream()), "vp_mt_adamw_bf16")
@@ -1471,7 +1479,7 @@ def zero_unpack(tensors: torch.Tensor, chunks: torch.Tensor, n_chunks: int, flat
                 scalars: torch.Tensor) -> None:
     """param[i] = flat[state_off + i] over the tables, for the tensors with a gradient (not in a skipped step)."""
     _flat1(flat, "flat", BF16)
-    _chk(scalars, "scalars", torch.int32)
+    _chk_scalars(scalars, "zero_unpack")
     N.check(N.lib().vp_zero_unpack_bf16(_p(tensors), _p(chunks), n_chunks, _p(flat), flat.numel(), _p(scalars),
                                         _stream()), "vp_zero_unpack_bf16")
 
@@ -1480,11 +1488,8 @@ def zero_shard_sqnorm(ranges: Optional[torch.Tensor], n_ranges: int, grad_shard:
                       flags: torch.Tensor, record: torch.Tensor) -> None:
     """This rank's (sum of squares, non-finite flag) record (int32[2] storage, N.ZeroRecord) of its gradient shard."""
     _flat1(grad_shard, "grad_shard", torch.float32)
-    _chk(partials, "partials", torch.float32)
-    _chk(flags, "flags", torch.int32)
+    _chk_slots(partials, flags, n_ranges, "zero_shard_sqnorm", "n_ranges")
     _chk(record, "record", torch.int32)
-    if partials.numel() < n_ranges or flags.numel() < n_ranges:
-        raise ValueError("zero_shard_sqnorm: partials / flags hold fewer than n_ranges slots")
     if record.numel() * 4 < C.sizeof(N.ZeroRecord) or not record.is_contiguous():
         raise ValueError("zero_shard_sqnorm: record too small")
     N.check(N.lib().vp_zero_shard_sqnorm(_p(ranges), n_ranges, _p(grad_shard), grad_shard.numel(), _p(partials),
@@ -1495,11 +1500,9 @@ def zero_finalize(records: torch.Tensor, world: int, scalars: torch.Tensor, *, m
                   betas=(0.0, 0.0), skip_nonfinite: bool = False) -> None:
     """optim_finalize(advance_step=True) over the ranks' records (int32 [world, 2] storage) in rank order."""
     _chk(records, "records", torch.int32)
-    _chk(scalars, "scalars", torch.int32)
+    _chk_scalars(scalars, "zero_finalize")
     if records.numel() * 4 < world * C.sizeof(N.ZeroRecord) or not records.is_contiguous():
         raise ValueError("zero_finalize: records hold fewer than world entries")
-    if scalars.numel() * 4 < C.sizeof(N.OptimScalars):
-        raise ValueError("zero_finalize: scalars block too small")
     N.check(N.lib().vp_zero_finalize(_p(records), world, max_norm, betas[0], betas[1], int(skip_nonfinite),
                                      _p(scalars), _stream()), "vp_zero_finalize")
 
@@ -1515,7 +1518,7 @@ def zero_shard_adamw(ranges: Optional[torch.Tensor], range_begin: int, n_ranges:
     _flat1(param_shard, "param_shard", BF16)
     if any(t.numel() != per for t in (master, exp_avg, exp_avg_sq, param_shard)):
         raise ValueError("zero_shard_adamw: the shard buffers differ in length")
-    _chk(scalars, "scalars", torch.int32)
+    _chk_scalars(scalars, "zero_shard_adamw")
     N.check(N.lib().vp_zero_shard_adamw(_p(ranges), range_begin, n_ranges, _p(grad_shard), _p(master), _p(exp_avg),
                                         _p(exp_avg_sq), _p(param_shard), per, _p(scalars), lr, betas[0], betas[1],
                                         eps, weight_decay, int(use_clip), _stream()), "vp_zero_shard_adamw")

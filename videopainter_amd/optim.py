@@ -13,10 +13,14 @@ writes the bf16 parameters back every step.
 
 Nothing here copies device memory to the host or synchronises: the norm, the clip coefficient, the non-finite flag,
 the step counter and the bias corrections live in a small device block the kernels read.
+
+The data-parallel optimizer (zero.ShardedFusedAdamW) is built on the same parts: `_FlatAdamW` (validation, the flat
+layout of `flat_offsets`, the scalars block, the state-dict checks, the step prologue) and `DeviceTables` (the table
+uploader over `pack_tables`).
 """
 from __future__ import annotations
 
-from typing import Iterable, List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -60,22 +64,72 @@ def _check_grad(g: torch.Tensor, what: str) -> None:
         raise ValueError(f"{what} must be contiguous")
 
 
-class MultiTensorTables:
-    """The device tables (tensor table + chunk table) of a list of gradients, and the reduction workspace.
+def _align(n: int) -> int:
+    return (n + _STATE_ALIGN - 1) // _STATE_ALIGN * _STATE_ALIGN
 
-    The tables are rebuilt on the host and uploaded (one asynchronous copy from pinned memory, on the current stream)
-    only when a pointer, a size or the set of tensors changed since the last call — so persistent `.grad` tensors
-    cost nothing per step, and gradients reallocated every step (`p.grad = None`, `zero_grad(set_to_none=True)`)
-    cost one small copy."""
+
+def flat_offsets(numels: Sequence[int]) -> Tuple[List[int], int]:
+    """(state offset of every tensor, T): the flat element space of the optimizer state, every tensor aligned to 8
+    elements."""
+    offs, total = [], 0
+    for n in numels:
+        offs.append(total)
+        total += _align(int(n))
+    return offs, total
+
+
+def pack_tables(arrays: Sequence[np.ndarray]) -> Tuple[np.ndarray, List[int]]:
+    """(uint8 image, byte offset of every table): the tables laid end to end, each on a 16-byte boundary.  A tensor
+    row is 32 bytes, so a chunk table after a tensor table begins at n_tensors * 32."""
+    parts, offs, at = [], [], 0
+    for a in arrays:
+        b = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+        offs.append(at)
+        parts += [b, np.zeros((-b.size) % 16, dtype=np.uint8)]
+        at += b.size + (-b.size) % 16
+    return (np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8)), offs
+
+
+class DeviceTables:
+    """Host-built tables in one device buffer, and the reduction workspace (one `partials` / `flags` slot per piece).
+
+    A user builds its tables on the host and hands them to `upload` (one asynchronous copy from pinned memory, on the
+    current stream) only when its key — the pointers, sizes and set of tensors — changed since the last call: so
+    persistent `.grad` tensors cost nothing per step, and gradients reallocated every step (`p.grad = None`,
+    `zero_grad(set_to_none=True)`) cost one small copy."""
 
     def __init__(self, device: torch.device):
         self.device = device
         self.key = None
-        self.buf = None  # uint8 device buffer: tensor table, then chunk table
-        self.n_tensors = 0
-        self.n_chunks = 0
+        self.buf = None  # uint8 device buffer: the tables in upload order
+        self.offsets: List[int] = []
         self.partials = None
         self.flags = None
+
+    def upload(self, key, arrays: Sequence[np.ndarray], slots: int) -> None:
+        host, self.offsets = pack_tables(arrays)
+        if host.size:
+            if self.buf is None or self.buf.numel() < host.size:
+                self.buf = torch.empty(max(host.size, 4096), device=self.device, dtype=torch.uint8)
+            pinned = torch.empty(host.size, dtype=torch.uint8, pin_memory=True)
+            pinned.copy_(torch.from_numpy(host))
+            self.buf[:host.size].copy_(pinned, non_blocking=True)
+        if self.partials is None or self.partials.numel() < slots:
+            self.partials = torch.empty(max(slots, 1024), device=self.device, dtype=torch.float32)
+            self.flags = torch.empty(max(slots, 1024), device=self.device, dtype=torch.int32)
+        self.key = key
+
+    def table(self, i: int) -> Optional[torch.Tensor]:
+        return None if self.buf is None else self.buf[self.offsets[i]:]
+
+
+class MultiTensorTables(DeviceTables):
+    """The tensor table and the chunk table of a list of gradients; one reduction slot per chunk."""
+
+    def __init__(self, device: torch.device):
+        super().__init__(device)
+        self.n_tensors = 0
+        self.n_chunks = 0
         self.numels: List[int] = []
 
     def update(self, grads: Sequence[torch.Tensor], params: Optional[Sequence[torch.Tensor]] = None,
@@ -91,19 +145,8 @@ class MultiTensorTables:
         ct = build_chunk_table(ne)
         if len(ne) >= 2 ** 31 or ct.shape[0] >= 2 ** 31:
             raise ValueError("too many tensors / chunks")
-        host = np.concatenate((tt.view(np.uint8).reshape(-1), ct.view(np.uint8).reshape(-1)))
-        nbytes = host.size
-        if nbytes:
-            if self.buf is None or self.buf.numel() < nbytes:
-                self.buf = torch.empty(max(nbytes, 4096), device=self.device, dtype=torch.uint8)
-            pinned = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
-            pinned.copy_(torch.from_numpy(host))
-            self.buf[:nbytes].copy_(pinned, non_blocking=True)
+        self.upload(key, (tt, ct), int(ct.shape[0]))
         self.n_tensors, self.n_chunks, self.numels = len(ne), int(ct.shape[0]), ne
-        if self.partials is None or self.partials.numel() < self.n_chunks:
-            self.partials = torch.empty(max(self.n_chunks, 1024), device=self.device, dtype=torch.float32)
-            self.flags = torch.empty(max(self.n_chunks, 1024), device=self.device, dtype=torch.int32)
-        self.key = key
 
     @property
     def tensors(self) -> Optional[torch.Tensor]:
@@ -111,7 +154,7 @@ class MultiTensorTables:
 
     @property
     def chunks(self) -> Optional[torch.Tensor]:
-        return None if self.buf is None else self.buf[self.n_tensors * 32:]
+        return self.table(1)
 
     def chunks_of(self, first_tensor: int, n: int):
         """(first chunk, chunk count) of tensors [first_tensor, first_tensor + n) of the list."""
@@ -175,7 +218,160 @@ def clip_grad_norm_(parameters, max_norm: float, norm_type: float = 2.0) -> torc
     return _functional(parameters, max_norm, True)
 
 
-class FusedAdamW(torch.optim.Optimizer):
+_STATE_KEYS = ("master", "exp_avg", "exp_avg_sq")
+
+
+class _FlatAdamW(torch.optim.Optimizer):
+    """What `FusedAdamW` and `zero.ShardedFusedAdamW` share: the validation of hyper-parameters and parameters, the
+    trainable parameters laid out in one flat element space (`flat_offsets`), the int32[8] device scalars block
+    (N.OptimScalars) with its read-only views, the checks of a loaded state dict and the prologue of `step()`.  A
+    subclass owns the state buffers, the step itself and its checkpoint formats."""
+
+    def __init__(self, params, lr, betas, eps, weight_decay, max_grad_norm, skip_nonfinite, zero_grads):
+        """Validates everything and lays out the flat space; allocates nothing (`_alloc_scalars` is the subclass's
+        first device allocation, after its own checks)."""
+        name = type(self).__name__
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError(f"Invalid betas: {betas}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError(f"Invalid max_grad_norm: {max_grad_norm}")
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay))
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.zero_grads = bool(zero_grads)
+        self._params, self._group_of = [], []  # the trainable parameters in list order, and their group index
+        for gi, g in enumerate(self.param_groups):
+            for p in g["params"]:
+                if p.requires_grad:
+                    self._params.append(p)
+                    self._group_of.append(gi)
+        if not self._params:
+            raise ValueError(f"{name}: no parameter requires a gradient")
+        for p in self._params:
+            if p.dtype != BF16:
+                raise TypeError(f"{name} parameters must be torch.bfloat16, got {p.dtype}")
+            if p.layout != torch.strided or not p.is_contiguous():
+                raise ValueError(f"{name} parameters must be dense and contiguous")
+            if p.grad is not None and p.grad.is_sparse:
+                raise ValueError(f"{name} does not support sparse gradients")
+        if not all(p.is_cuda for p in self._params):
+            raise ValueError(f"{name} parameters must be device tensors")
+        if len({p.device for p in self._params}) > 1:
+            raise ValueError(f"{name} parameters must be on one device")
+        self._device = self._params[0].device
+        offs, self.total = flat_offsets([p.numel() for p in self._params])
+        self._offs = dict(zip(self._params, offs))
+
+    def _alloc_scalars(self) -> None:
+        self._scalars = torch.zeros(8, device=self._device, dtype=torch.int32)  # N.OptimScalars
+        self._scalars_f = self._scalars.view(torch.float32)
+
+    # the device scalars of the last step
+    @property
+    def grad_norm(self) -> torch.Tensor:
+        return self._scalars_f[0]
+
+    @property
+    def clip_coef(self) -> torch.Tensor:
+        return self._scalars_f[1]
+
+    @property
+    def nonfinite(self) -> torch.Tensor:
+        return self._scalars[2]
+
+    @property
+    def step_count(self) -> torch.Tensor:
+        return self._scalars[3]
+
+    @property
+    def last_step_skipped(self) -> torch.Tensor:
+        return self._scalars[6]
+
+    @property
+    def scalars(self) -> torch.Tensor:
+        """The whole int32[8] block (N.OptimScalars)."""
+        return self._scalars
+
+    def flat_offset(self, p: torch.Tensor) -> int:
+        """The flat element offset of trainable parameter `p`: its state is elements [offset, offset + p.numel()) of
+        the flat space (`total` elements in all)."""
+        if p not in self._offs:
+            raise KeyError("not a trainable parameter of this optimizer")
+        return self._offs[p]
+
+    def _begin_step(self, closure):
+        """The prologue of step(): (the closure's loss, the betas every group shares), after checking every gradient
+        there is."""
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        name = type(self).__name__
+        betas = self.param_groups[0]["betas"]
+        for group in self.param_groups:
+            if tuple(group["betas"]) != tuple(betas):
+                raise ValueError(f"{name}: betas must be the same in every parameter group")
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                if p not in self._offs:
+                    raise ValueError(f"{name}: a parameter that did not require a gradient at construction has one")
+                _check_grad(p.grad, "gradient")
+        return loss, betas
+
+    def _indexed(self):
+        i = 0
+        for g in self.param_groups:
+            for p in g["params"]:
+                yield i, p
+                i += 1
+
+    def _groups_dict(self):
+        groups, i = [], 0
+        for g in self.param_groups:
+            d = {k: v for k, v in g.items() if k != "params"}
+            d["params"] = list(range(i, i + len(g["params"])))
+            i += len(g["params"])
+            groups.append(d)
+        return groups
+
+    def _check_groups(self, state_dict) -> None:
+        groups = state_dict["param_groups"]
+        if len(groups) != len(self.param_groups) or any(len(a["params"]) != len(b["params"])
+                                                        for a, b in zip(groups, self.param_groups)):
+            raise ValueError("loaded state dict has different parameter groups")
+
+    def _full_state(self, state_dict):
+        """[(trainable parameter, its {master, exp_avg, exp_avg_sq})] of a full-format state dict, every shape
+        checked before anything is copied."""
+        state, out = state_dict["state"], []
+        for i, p in self._indexed():
+            if p not in self._offs:
+                continue
+            s = state.get(i, state.get(str(i)))
+            if s is None:
+                raise ValueError(f"loaded state dict has no state for parameter {i}")
+            for k in _STATE_KEYS:
+                if tuple(s[k].shape) != tuple(p.shape):
+                    raise ValueError(f"loaded {k} of parameter {i} has shape {tuple(s[k].shape)}")
+            out.append((p, s))
+        return out
+
+    def _restore_options(self, state_dict) -> None:
+        """The groups' options and the step counter of a loaded state dict (after the state itself)."""
+        for mine, theirs in zip(self.param_groups, state_dict["param_groups"]):
+            mine.update({k: v for k, v in theirs.items() if k != "params"})
+        self._scalars[3:4].fill_(int(state_dict.get("step", 0)))
+        self._scalars[6:7].zero_()
+
+
+class FusedAdamW(_FlatAdamW):
     """torch.optim.AdamW (amsgrad=False, maximize=False) for bf16 device parameters with fp32 master weights.
 
     State lives in three flat fp32 device buffers (master, exp_avg, exp_avg_sq); `state[p]` exposes per-parameter
@@ -199,46 +395,12 @@ class FusedAdamW(torch.optim.Optimizer):
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
                  *, max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, zero_grads: bool = False):
-        if not 0.0 <= lr:
-            raise ValueError(f"Invalid learning rate: {lr}")
-        if not 0.0 <= eps:
-            raise ValueError(f"Invalid epsilon value: {eps}")
-        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
-            raise ValueError(f"Invalid betas: {betas}")
-        if not 0.0 <= weight_decay:
-            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
-        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
-            raise ValueError(f"Invalid max_grad_norm: {max_grad_norm}")
-        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay))
-        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
-        self.skip_nonfinite = bool(skip_nonfinite)
-        self.zero_grads = bool(zero_grads)
-        # validate everything before the first device allocation
-        self._params = [p for g in self.param_groups for p in g["params"] if p.requires_grad]
-        if not self._params:
-            raise ValueError("FusedAdamW: no parameter requires a gradient")
-        for p in self._params:
-            if p.dtype != BF16:
-                raise TypeError(f"FusedAdamW parameters must be torch.bfloat16, got {p.dtype}")
-            if p.layout != torch.strided or not p.is_contiguous():
-                raise ValueError("FusedAdamW parameters must be dense and contiguous")
-            if p.grad is not None and p.grad.is_sparse:
-                raise ValueError("FusedAdamW does not support sparse gradients")
-        if not all(p.is_cuda for p in self._params):
-            raise ValueError("FusedAdamW parameters must be device tensors")
-        if len({p.device for p in self._params}) > 1:
-            raise ValueError("FusedAdamW parameters must be on one device")
-        dev = self._params[0].device
-        self._offs, total = {}, 0
-        for p in self._params:
-            self._offs[p] = total
-            total += (p.numel() + _STATE_ALIGN - 1) // _STATE_ALIGN * _STATE_ALIGN
-        self._master = torch.zeros(max(total, 1), device=dev, dtype=torch.float32)
+        super().__init__(params, lr, betas, eps, weight_decay, max_grad_norm, skip_nonfinite, zero_grads)
+        self._alloc_scalars()
+        self._master = torch.zeros(max(self.total, 1), device=self._device, dtype=torch.float32)
         self._exp_avg = torch.zeros_like(self._master)
         self._exp_avg_sq = torch.zeros_like(self._master)
-        self._scalars = torch.zeros(8, device=dev, dtype=torch.int32)  # N.OptimScalars
-        self._scalars_f = self._scalars.view(torch.float32)
-        self._tables = MultiTensorTables(dev)
+        self._tables = MultiTensorTables(self._device)
         with torch.no_grad():
             for p in self._params:
                 o, n = self._offs[p], p.numel()
@@ -247,59 +409,20 @@ class FusedAdamW(torch.optim.Optimizer):
                                      exp_avg=self._exp_avg[o:o + n].view(p.shape),
                                      exp_avg_sq=self._exp_avg_sq[o:o + n].view(p.shape))
 
-    # the device scalars of the last step
-    @property
-    def grad_norm(self) -> torch.Tensor:
-        return self._scalars_f[0]
-
-    @property
-    def clip_coef(self) -> torch.Tensor:
-        return self._scalars_f[1]
-
-    @property
-    def nonfinite(self) -> torch.Tensor:
-        return self._scalars[2]
-
-    @property
-    def step_count(self) -> torch.Tensor:
-        return self._scalars[3]
-
-    @property
-    def last_step_skipped(self) -> torch.Tensor:
-        return self._scalars[6]
-
     @torch.no_grad()
     def step(self, closure=None):
         from . import kernels as K
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        betas = self.param_groups[0]["betas"]
-        grads, params, offs, counts = [], [], [], []
-        for group in self.param_groups:
-            if tuple(group["betas"]) != tuple(betas):
-                raise ValueError("FusedAdamW: betas must be the same in every parameter group")
-            n = 0
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                if p not in self._offs:
-                    raise ValueError("FusedAdamW: a parameter that did not require a gradient at construction has one")
-                _check_grad(p.grad, "gradient")
-                grads.append(p.grad)
-                params.append(p)
-                offs.append(self._offs[p])
-                n += 1
-            counts.append(n)
+        loss, betas = self._begin_step(closure)
+        params = [p for g in self.param_groups for p in g["params"] if p.grad is not None]
         t = self._tables
-        with torch.cuda.device(self._master.device):
-            t.update(grads, params, offs)
+        with torch.cuda.device(self._device):
+            t.update([p.grad for p in params], params, [self._offs[p] for p in params])
             K.mt_grad_sqnorm(t.tensors, t.chunks, t.n_chunks, t.partials, t.flags)
             K.optim_finalize(t.partials, t.flags, t.n_chunks, self._scalars, max_norm=self.max_grad_norm or 0.0,
                              betas=betas, skip_nonfinite=self.skip_nonfinite, advance_step=True)
             first = 0
-            for group, n in zip(self.param_groups, counts):
+            for group in self.param_groups:  # the active tensors of a group are one run of the list
+                n = sum(p.grad is not None for p in group["params"])
                 c0, nc = t.chunks_of(first, n)
                 first += n
                 K.mt_adamw(t.tensors, t.chunks, c0, nc, self._master, self._exp_avg, self._exp_avg_sq, self._scalars,
@@ -308,48 +431,19 @@ class FusedAdamW(torch.optim.Optimizer):
                            zero_grads=self.zero_grads)
         return loss
 
-    def _indexed(self):
-        i = 0
-        for g in self.param_groups:
-            for p in g["params"]:
-                yield i, p
-                i += 1
-
     def state_dict(self):
         """{"state": {index: {master, exp_avg, exp_avg_sq}}, "param_groups": [...], "step": int} — clones; reading
         the step counter is the one device-to-host copy of this class (not on the step path)."""
-        groups, i = [], 0
-        for g in self.param_groups:
-            d = {k: v for k, v in g.items() if k != "params"}
-            d["params"] = list(range(i, i + len(g["params"])))
-            i += len(g["params"])
-            groups.append(d)
-        state = {i: {k: self.state[p][k].detach().clone() for k in ("master", "exp_avg", "exp_avg_sq")}
+        state = {i: {k: self.state[p][k].detach().clone() for k in _STATE_KEYS}
                  for i, p in self._indexed() if p in self._offs}
-        return {"state": state, "param_groups": groups, "step": int(self._scalars[3].item())}
+        return {"state": state, "param_groups": self._groups_dict(), "step": int(self._scalars[3].item())}
 
     @torch.no_grad()
     def load_state_dict(self, state_dict):
-        groups = state_dict["param_groups"]
-        if len(groups) != len(self.param_groups) or any(len(a["params"]) != len(b["params"])
-                                                        for a, b in zip(groups, self.param_groups)):
-            raise ValueError("loaded state dict has different parameter groups")
-        state = state_dict["state"]
-        for i, p in self._indexed():
-            if p not in self._offs:
-                continue
-            s = state.get(i, state.get(str(i)))
-            if s is None:
-                raise ValueError(f"loaded state dict has no state for parameter {i}")
-            for k in ("master", "exp_avg", "exp_avg_sq"):
-                if tuple(s[k].shape) != tuple(p.shape):
-                    raise ValueError(f"loaded {k} of parameter {i} has shape {tuple(s[k].shape)}")
-        for i, p in self._indexed():
-            if p in self._offs:
-                s = state.get(i, state.get(str(i)))
-                for k in ("master", "exp_avg", "exp_avg_sq"):
-                    self.state[p][k].copy_(s[k])
-        for mine, theirs in zip(self.param_groups, groups):
-            mine.update({k: v for k, v in theirs.items() if k != "params"})
-        self._scalars[3:4].fill_(int(state_dict.get("step", 0)))
-        self._scalars[6:7].zero_()
+        self._check_groups(state_dict)
+        for p, s in self._full_state(state_dict):
+            for k in _STATE_KEYS:
+                self.state[p][k].copy_(s[k])
+        self._restore_options(state_dict)
+
+

@@ -2,10 +2,11 @@
 updated bf16 parameters all-gathered back (csrc/zero.hip; the reference trains under DeepSpeed ZeRO stage 2 + bf16,
 train/VideoPainter.sh with accelerate_config_machine_single_ds.yaml).
 
-Layout.  The flat element space is `FusedAdamW`'s: every trainable parameter at its state offset, aligned to 8
-elements, T elements in all.  per = ceil(T / world) rounded up to a multiple of 8, the flat length is world * per and
-rank r owns [r * per, (r + 1) * per): a shard boundary may cut a tensor, a 16384-element chunk or a parameter group
-anywhere that is a multiple of 8, and a rank may own nothing but padding.  Each rank holds
+Layout.  The flat element space is `FusedAdamW`'s (optim.flat_offsets, laid out by the base class both optimizers
+derive from): every trainable parameter at its state offset, aligned to 8 elements, T elements in all.  per =
+ceil(T / world) rounded up to a multiple of 8, the flat length is world * per and rank r owns [r * per, (r + 1) * per):
+a shard boundary may cut a tensor, a 16384-element chunk or a parameter group anywhere that is a multiple of 8, and a
+rank may own nothing but padding.  Each rank holds
 
     master, exp_avg, exp_avg_sq   fp32 [per]           12 B per parameter / world
     gradient staging              fp32 [world * per]   4 B per parameter (full size: the reduce-scatter is one
@@ -34,23 +35,12 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .optim import BF16, CHUNK, _STATE_ALIGN, _check_grad, build_chunk_table, build_tensor_table
+from .optim import (BF16, CHUNK, _STATE_ALIGN, _STATE_KEYS, DeviceTables, _align, _FlatAdamW, build_chunk_table,
+                    build_tensor_table)
+from .optim import flat_offsets  # noqa: F401  (part of this module's interface too)
 
 RANGE_DTYPE = np.dtype([("start", "<i8"), ("n", "<i4"), ("pad", "<i4")])  # N.ZeroRange
 assert RANGE_DTYPE.itemsize == C.sizeof(N.ZeroRange)
-
-
-def _align(n: int) -> int:
-    return (n + _STATE_ALIGN - 1) // _STATE_ALIGN * _STATE_ALIGN
-
-
-def flat_offsets(numels: Sequence[int]) -> Tuple[List[int], int]:
-    """(state offset of every tensor, T): FusedAdamW's flat element space, every tensor aligned to 8 elements."""
-    offs, total = [], 0
-    for n in numels:
-        offs.append(total)
-        total += _align(int(n))
-    return offs, total
 
 
 def shard_size(total: int, world: int) -> int:
@@ -89,24 +79,18 @@ def build_range_table(offs: Sequence[int], numels: Sequence[int], active: Sequen
     return tab, (np.concatenate(owner) if owner else np.zeros(0, dtype=np.int64))
 
 
-class _ShardTables:
+class _ShardTables(DeviceTables):
     """The device tables of one step — the tensor and chunk tables of ALL trainable tensors (pack / unpack; a NULL
-    gradient pointer marks an idle tensor) and this rank's range table — in one buffer, uploaded as
-    optim.MultiTensorTables does: pinned memory, one asynchronous copy on the current stream, rebuilt only when a
-    pointer or the set of tensors with a gradient changed."""
+    gradient pointer marks an idle tensor) and this rank's range table, one reduction slot per range — rebuilt only
+    when a pointer or the set of tensors with a gradient changed."""
 
     def __init__(self, device, offs, numels, group_of, n_groups, rank, per):
-        self.device = device
+        super().__init__(device)
         self.offs, self.numels = list(offs), list(numels)
         self.group_of, self.n_groups, self.rank, self.per = list(group_of), n_groups, rank, per
-        self.key = None
-        self.buf = None
         self.n_chunks = 0
         self.n_ranges = 0
         self.group_ranges: List[Tuple[int, int]] = [(0, 0)] * n_groups  # (first range, count) per parameter group
-        self.partials = None
-        self.flags = None
-        self._ct_off = self._rt_off = 0
 
     def update(self, grad_ptrs: Sequence[int], param_ptrs: Sequence[int]) -> None:
         key = (tuple(grad_ptrs), tuple(param_ptrs))
@@ -117,19 +101,7 @@ class _ShardTables:
         rt, owner = build_range_table(self.offs, self.numels, [g != 0 for g in grad_ptrs], self.rank, self.per)
         if ct.shape[0] >= 2 ** 31 or rt.shape[0] >= 2 ** 31:
             raise ValueError("too many chunks / ranges")
-        parts = []
-        for a in (tt, ct, rt):  # every table on a 16-byte boundary of the buffer
-            b = a.view(np.uint8).reshape(-1)
-            pad = (-b.size) % 16
-            parts += [b, np.zeros(pad, dtype=np.uint8)]
-        self._ct_off = tt.nbytes + (-tt.nbytes) % 16
-        self._rt_off = self._ct_off + ct.nbytes + (-ct.nbytes) % 16
-        host = np.concatenate(parts)
-        if self.buf is None or self.buf.numel() < host.size:
-            self.buf = torch.empty(max(host.size, 4096), device=self.device, dtype=torch.uint8)
-        pinned = torch.empty(host.size, dtype=torch.uint8, pin_memory=True)
-        pinned.copy_(torch.from_numpy(host))
-        self.buf[:host.size].copy_(pinned, non_blocking=True)
+        self.upload(key, (tt, ct, rt), int(rt.shape[0]))
         self.n_chunks, self.n_ranges = int(ct.shape[0]), int(rt.shape[0])
         groups = np.asarray(self.group_of, dtype=np.int64)[owner] if owner.size else owner
         first = 0
@@ -137,10 +109,6 @@ class _ShardTables:
             cnt = int((groups == g).sum())
             self.group_ranges[g] = (first, cnt)
             first += cnt
-        if self.partials is None or self.partials.numel() < self.n_ranges:
-            self.partials = torch.empty(max(self.n_ranges, 1024), device=self.device, dtype=torch.float32)
-            self.flags = torch.empty(max(self.n_ranges, 1024), device=self.device, dtype=torch.int32)
-        self.key = key
 
     @property
     def tensors(self) -> torch.Tensor:
@@ -148,14 +116,14 @@ class _ShardTables:
 
     @property
     def chunks(self) -> torch.Tensor:
-        return self.buf[self._ct_off:]
+        return self.table(1)
 
     @property
     def ranges(self) -> torch.Tensor:
-        return self.buf[self._rt_off:]
+        return self.table(2)
 
 
-class ShardedFusedAdamW(torch.optim.Optimizer):
+class ShardedFusedAdamW(_FlatAdamW):
     """The data-parallel counterpart of `FusedAdamW`: the same per-element AdamW arithmetic (one shared device
     function), gradients averaged over the ranks by a reduce-scatter, fp32 master weights and moments kept for this
     rank's 1 / world slice of the flat parameter space only (ZeRO stage 1 / 2 style), the updated bf16 parameters
@@ -189,42 +157,9 @@ class ShardedFusedAdamW(torch.optim.Optimizer):
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
                  *, max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, zero_grads: bool = False,
                  process_group=None, comm=None, rank: Optional[int] = None):
-        if not 0.0 <= lr:
-            raise ValueError(f"Invalid learning rate: {lr}")
-        if not 0.0 <= eps:
-            raise ValueError(f"Invalid epsilon value: {eps}")
-        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
-            raise ValueError(f"Invalid betas: {betas}")
-        if not 0.0 <= weight_decay:
-            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
-        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
-            raise ValueError(f"Invalid max_grad_norm: {max_grad_norm}")
         if comm is not None and process_group is not None:
             raise ValueError("ShardedFusedAdamW: give process_group= or comm=, not both")
-        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay))
-        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
-        self.skip_nonfinite = bool(skip_nonfinite)
-        self.zero_grads = bool(zero_grads)
-        # validate everything before the first device allocation
-        self._params, self._group_of = [], []
-        for gi, g in enumerate(self.param_groups):
-            for p in g["params"]:
-                if p.requires_grad:
-                    self._params.append(p)
-                    self._group_of.append(gi)
-        if not self._params:
-            raise ValueError("ShardedFusedAdamW: no parameter requires a gradient")
-        for p in self._params:
-            if p.dtype != BF16:
-                raise TypeError(f"ShardedFusedAdamW parameters must be torch.bfloat16, got {p.dtype}")
-            if p.layout != torch.strided or not p.is_contiguous():
-                raise ValueError("ShardedFusedAdamW parameters must be dense and contiguous")
-            if p.grad is not None and p.grad.is_sparse:
-                raise ValueError("ShardedFusedAdamW does not support sparse gradients")
-        if not all(p.is_cuda for p in self._params):
-            raise ValueError("ShardedFusedAdamW parameters must be device tensors")
-        if len({p.device for p in self._params}) > 1:
-            raise ValueError("ShardedFusedAdamW parameters must be on one device")
+        super().__init__(params, lr, betas, eps, weight_decay, max_grad_norm, skip_nonfinite, zero_grads)
         if comm is None:
             from .distributed import GroupComm
             comm = GroupComm(process_group)
@@ -236,25 +171,22 @@ class ShardedFusedAdamW(torch.optim.Optimizer):
         self._comm, self.world, self.rank = comm, int(comm.world), int(rank)
         if not 0 <= self.rank < self.world:
             raise ValueError(f"rank {self.rank} outside world size {self.world}")
-        dev = self._params[0].device
-        numels = [p.numel() for p in self._params]
-        offs, self.total = flat_offsets(numels)
-        self._offs = dict(zip(self._params, offs))
+        dev = self._device
         self.per = per = shard_size(self.total, self.world)
         self._lo, self._hi = self.rank * per, (self.rank + 1) * per
+        self._alloc_scalars()
         self._master = torch.zeros(per, device=dev, dtype=torch.float32)
         self._exp_avg = torch.zeros_like(self._master)
         self._exp_avg_sq = torch.zeros_like(self._master)
         self._grad_shard = torch.zeros_like(self._master)
         self._flat32 = torch.zeros(self.world * per, device=dev, dtype=torch.float32)  # gradient staging
         self._flat16 = torch.zeros(self.world * per, device=dev, dtype=BF16)            # parameter staging
-        self._scalars = torch.zeros(8, device=dev, dtype=torch.int32)  # N.OptimScalars
-        self._scalars_f = self._scalars.view(torch.float32)
         self._record = torch.zeros(2, device=dev, dtype=torch.int32)                # N.ZeroRecord
         self._records = torch.zeros(2 * self.world, device=dev, dtype=torch.int32)  # every rank's, in rank order
-        self._tables = _ShardTables(dev, offs, numels, self._group_of, len(self.param_groups), self.rank, per)
+        self._tables = _ShardTables(dev, self._offs.values(), [p.numel() for p in self._params], self._group_of,
+                                    len(self.param_groups), self.rank, per)
         with torch.no_grad():  # masters = the fp32 value of the bf16 parameters, this rank's slice
-            for p, o in zip(self._params, offs):
+            for p, o in self._offs.items():
                 self._copy_slice(self._master, p.detach().reshape(-1), o)
 
     def _copy_slice(self, shard: torch.Tensor, full: torch.Tensor, off: int) -> None:
@@ -262,32 +194,6 @@ class ShardedFusedAdamW(torch.optim.Optimizer):
         lo, hi = max(off, self._lo), min(off + full.numel(), self._hi)
         if lo < hi:
             shard[lo - self._lo:hi - self._lo].copy_(full[lo - off:hi - off])
-
-    # the device scalars of the last step (bit-identical on every rank)
-    @property
-    def grad_norm(self) -> torch.Tensor:
-        return self._scalars_f[0]
-
-    @property
-    def clip_coef(self) -> torch.Tensor:
-        return self._scalars_f[1]
-
-    @property
-    def nonfinite(self) -> torch.Tensor:
-        return self._scalars[2]
-
-    @property
-    def step_count(self) -> torch.Tensor:
-        return self._scalars[3]
-
-    @property
-    def last_step_skipped(self) -> torch.Tensor:
-        return self._scalars[6]
-
-    @property
-    def scalars(self) -> torch.Tensor:
-        """The whole int32[8] block (N.OptimScalars)."""
-        return self._scalars
 
     # this rank's slice of the flat state
     @property
@@ -302,14 +208,8 @@ class ShardedFusedAdamW(torch.optim.Optimizer):
     def exp_avg_sq_shard(self) -> torch.Tensor:
         return self._exp_avg_sq
 
-    # the layout, for checkpoint tools and tests: total (T), per, world and rank are plain attributes
-    def flat_offset(self, p: torch.Tensor) -> int:
-        """The flat element offset of trainable parameter `p` (FusedAdamW's state offset): its state is elements
-        [offset, offset + p.numel()) of the ranks' shards laid end to end."""
-        if p not in self._offs:
-            raise KeyError("not a trainable parameter of this optimizer")
-        return self._offs[p]
-
+    # (the layout, for checkpoint tools and tests: total (T), per, world and rank are plain attributes; flat_offset(p)
+    # is the base class's)
     @property
     def comm(self):
         """The communicator the step runs on (distributed.GroupComm or the comm= given)."""
@@ -333,25 +233,8 @@ class ShardedFusedAdamW(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None):
         from . import kernels as K
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        betas = self.param_groups[0]["betas"]
-        for group in self.param_groups:
-            if tuple(group["betas"]) != tuple(betas):
-                raise ValueError("ShardedFusedAdamW: betas must be the same in every parameter group")
-            for p in group["params"]:
-                if p.grad is not None and p not in self._offs:
-                    raise ValueError("ShardedFusedAdamW: a parameter that did not require a gradient at construction "
-                                     "has one")
-        gp = []
-        for p in self._params:
-            if p.grad is None:
-                gp.append(0)
-            else:
-                _check_grad(p.grad, "gradient")
-                gp.append(p.grad.data_ptr())
+        loss, betas = self._begin_step(closure)
+        gp = [0 if p.grad is None else p.grad.data_ptr() for p in self._params]
         t, c, r = self._tables, self._comm, self.rank
         with torch.cuda.device(self._master.device):
             t.update(gp, [p.data_ptr() for p in self._params])
@@ -373,22 +256,6 @@ class ShardedFusedAdamW(torch.optim.Optimizer):
         return loss
 
     # ---- checkpoints ----
-    def _groups_dict(self):
-        groups, i = [], 0
-        for g in self.param_groups:
-            d = {k: v for k, v in g.items() if k != "params"}
-            d["params"] = list(range(i, i + len(g["params"])))
-            i += len(g["params"])
-            groups.append(d)
-        return groups
-
-    def _indexed(self):
-        i = 0
-        for g in self.param_groups:
-            for p in g["params"]:
-                yield i, p
-                i += 1
-
     def state_dict(self):
         """This rank's shard: {"world", "rank", "per", "step", "master", "exp_avg", "exp_avg_sq" (fp32 [per] clones),
         "param_groups"}.  Reloads into the same world size and rank only; `full_state_dict()` is the portable form.
@@ -419,11 +286,8 @@ class ShardedFusedAdamW(torch.optim.Optimizer):
         or full_state_dict() of any world size): this rank's slice of every tensor.  Restores masters, moments, the
         parameter groups' options and the step counter; the bf16 parameters are left as they are (a checkpoint's
         model weights are bf16(master) already)."""
-        groups = state_dict["param_groups"]
-        if len(groups) != len(self.param_groups) or any(len(a["params"]) != len(b["params"])
-                                                        for a, b in zip(groups, self.param_groups)):
-            raise ValueError("loaded state dict has different parameter groups")
-        keys = ("master", "exp_avg", "exp_avg_sq")
+        self._check_groups(state_dict)
+        keys = _STATE_KEYS
         mine = dict(zip(keys, (self._master, self._exp_avg, self._exp_avg_sq)))
         if "state" not in state_dict:
             if (state_dict["world"], state_dict["rank"], state_dict["per"]) != (self.world, self.rank, self.per):
@@ -436,22 +300,7 @@ class ShardedFusedAdamW(torch.optim.Optimizer):
             for k in keys:
                 mine[k].copy_(state_dict[k])
         else:
-            state = state_dict["state"]
-            for i, p in self._indexed():
-                if p not in self._offs:
-                    continue
-                s = state.get(i, state.get(str(i)))
-                if s is None:
-                    raise ValueError(f"loaded state dict has no state for parameter {i}")
+            for p, s in self._full_state(state_dict):
                 for k in keys:
-                    if tuple(s[k].shape) != tuple(p.shape):
-                        raise ValueError(f"loaded {k} of parameter {i} has shape {tuple(s[k].shape)}")
-            for i, p in self._indexed():
-                if p in self._offs:
-                    s = state.get(i, state.get(str(i)))
-                    for k in keys:
-                        self._copy_slice(mine[k], s[k].reshape(-1), self._offs[p])
-        for g, theirs in zip(self.param_groups, groups):
-            g.update({k: v for k, v in theirs.items() if k != "params"})
-        self._scalars[3:4].fill_(int(state_dict.get("step", 0)))
-        self._scalars[6:7].zero_()
+                    self._copy_slice(mine[k], s[k].reshape(-1), self._offs[p])
+        self._restore_options(state_dict)
