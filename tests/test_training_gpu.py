@@ -166,14 +166,15 @@ def test_block_backward_matches_oracle():
         _check(n, ours[n], gp32[n], gp16[n])
 
 
-@pytest.mark.parametrize("lora", [False, True], ids=["plain", "lora"])
-def test_saved_attention_backward_is_bit_identical(monkeypatch, lora):
+@pytest.mark.parametrize("lora,inject", [(False, False), (True, False), (False, True)],
+                         ids=["plain", "lora", "inject"])
+def test_saved_attention_backward_is_bit_identical(monkeypatch, lora, inject):
     """autograd.SAVE_ACTIVATIONS (the training forward keeps every intermediate the backward reads) and
     SAVE_ATTENTION (the attention output + lse only) against the full recompute: the same forward output bits (the
     saving forward's fused QKV / GELU epilogues with their aux outputs = forward_joint's launches) and the same
     gradient bits
     (also with an unfused trainable adapter on the projections), up to the atomic-order noise of the qk-norm affine
-    sums."""
+    sums.  inject: with a branch sample injected under a mask (FF2's epilogue) — its gradient bits too."""
     from videopainter_amd import autograd as AG
     from videopainter_amd.autograd import block_apply
     tr, br, _, _ = _models()
@@ -191,6 +192,8 @@ def test_saved_attention_backward_is_bit_identical(monkeypatch, lora):
     x = torch.randn(2, T + 288, 128, generator=g).bfloat16()
     temb = torch.randn(2, 32, generator=g).bfloat16()
     dout = torch.randn(2, T + 288, 128, generator=g).bfloat16()
+    inj = torch.randn(2, 288, 128, generator=g).bfloat16()
+    inj_mask = (torch.rand(2, 288, generator=g) < 0.5).to(torch.uint8).to(dev)
     res = []
     # all intermediates kept (the training forward runs the backward's front) / the attention only / recompute all
     for acts, attn in ((True, True), (False, True), (False, False)):
@@ -200,13 +203,18 @@ def test_saved_attention_backward_is_bit_identical(monkeypatch, lora):
             p.grad = None
         xd = x.to(dev).requires_grad_()
         td = temb.to(dev).requires_grad_()
-        out = block_apply(blk, xd, T, td, (i["rope"][0].to(dev), i["rope"][1].to(dev)))
+        injd = inj.to(dev).requires_grad_() if inject else None
+        out = block_apply(blk, xd, T, td, (i["rope"][0].to(dev), i["rope"][1].to(dev)), injd,
+                          inj_mask if inject else None)
         out.backward(dout.to(dev))
         res.append((out.detach(), xd.grad, td.grad,
-                    {n: p.grad.clone() for n, p in blk.named_parameters() if p.grad is not None}))
-    o0, gx0, gt0, gp0 = res[-1]
-    for o1, gx1, gt1, gp1 in res[:-1]:
+                    {n: p.grad.clone() for n, p in blk.named_parameters() if p.grad is not None},
+                    injd.grad if inject else None))
+    o0, gx0, gt0, gp0, gi0 = res[-1]
+    assert not inject or float(gi0.float().abs().max()) > 0
+    for o1, gx1, gt1, gp1, gi1 in res[:-1]:
         assert torch.equal(o1, o0) and torch.equal(gx1, gx0) and torch.equal(gt1, gt0)
+        assert not inject or torch.equal(gi1, gi0)
         assert gp1.keys() == gp0.keys() and len(gp1) > 0
         for n in gp1:
             if ".norm_q." in n or ".norm_k." in n:

@@ -8,7 +8,8 @@ The processors work on any `attn` object exposing to_q/to_k/to_v/to_out[0]/norm_
 reference `Attention` holding bf16 device weights).
 
 `attend()` is the fused core (QKV projection -> qk-LN + RoPE -> flash attention, everything before to_out); the
-block calls it directly so that to_out runs as one GEMM with the gated residual fused in its epilogue.
+block calls it directly so that to_out runs as one GEMM with the gated residual fused in its epilogue; `_qkv` is its
+projection step alone (all a backward that kept its attention output recomputes of it).
 """
 from __future__ import annotations
 
@@ -122,9 +123,16 @@ def _rows(t: torch.Tensor) -> torch.Tensor:
     return t if t.stride(-1) == 1 else t.contiguous()
 
 
-def _qkv(attn, x: torch.Tensor, norm_rope=None) -> torch.Tensor:
+def keeps_all(keep: Optional[dict]) -> bool:
+    """A forward's `keep` dict (CogVideoXBlock.forward_joint) is at the level "all"."""
+    return keep is not None and keep["level"] == "all"
+
+
+def _qkv(attn, x: torch.Tensor, norm_rope=None, keep: Optional[dict] = None) -> torch.Tensor:
     """The fused QKV projection; with norm_rope = (text_len, rope) q and k leave the GEMM already through norm_q /
-    norm_k and RoPE (the epilogue EPI_BIAS_QKNORM_ROPE: bit-equal to the GEMM + vp_head_norm_rope_bf16 on each)."""
+    norm_k and RoPE (the epilogue EPI_BIAS_QKNORM_ROPE: bit-equal to the GEMM + vp_head_norm_rope_bf16 on each).
+    keep, at the level "all", receives "qkv", the pre-norm q | k "qkp" (the fused epilogue's aux output, requested
+    then only) and, with train, the operand the GEMM read, "xq" (x, or its K-augmented form under unfused LoRA)."""
     B, Ntok, D = x.shape
     out = torch.empty(B, Ntok, 3 * attn.inner_dim if hasattr(attn, "inner_dim") else 3 * D, device=x.device,
                       dtype=BF16)
@@ -137,10 +145,18 @@ def _qkv(attn, x: torch.Tensor, norm_rope=None) -> torch.Tensor:
         text_len, rope = norm_rope
         kw = dict(epilogue=NAT.EPI_BIAS_QKNORM_ROPE, qk_norm=(attn.norm_q, attn.norm_k), rope=rope,
                   tokens_per_batch=Ntok, text_len=text_len)
+        if keeps_all(keep):
+            keep["qkp"] = torch.empty(B, Ntok, 2 * D, device=x.device, dtype=BF16)
+            kw["aux"] = keep["qkp"].view(B * Ntok, 2 * D)
     if aug is not None:  # LoRA adapters, unfused (lora.AugmentedProjection)
-        aug.gemm(aug.input(a), bs, out.view(B * Ntok, -1), **kw)
+        a = aug.input(a)
+        aug.gemm(a, bs, out.view(B * Ntok, -1), **kw)
     else:
         K.gemm(a, ws, bs, out.view(B * Ntok, -1), **kw)
+    if keeps_all(keep):
+        keep["qkv"] = out
+        if keep["train"]:
+            keep["xq"] = a
     return out
 
 
@@ -229,64 +245,72 @@ class CogVideoXAttnProcessor2_0:
 
     def attend(self, attn, x: torch.Tensor, text_len: int, image_rotary_emb=None, prev_hidden_states=None,
                prev_clip_weight=None, resample_mask=None, prev_resample_mask=None,
-               qkv: Optional[torch.Tensor] = None, lse_out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """lse_out: optional fp32 [B, H, N] receiving the softmax statistics of the (single-segment, bf16) attention
-        — a training forward keeps them with the output for the backward (autograd.SAVE_ATTENTION)."""
+               qkv: Optional[torch.Tensor] = None, keep: Optional[dict] = None) -> torch.Tensor:
+        """keep: a dict that receives the attention output "o" and its softmax statistics "lse" (fp32 [B, H, N]) —
+        a training forward keeps them for the backward (autograd.SAVE_ATTENTION) — and at the level "all" what the
+        projection keeps (_qkv); the single-segment bf16 attention only."""
         B, Ntok, D = x.shape
         H = attn.heads
         rope = _rope_dev(image_rotary_emb, x.device)
         fp8 = getattr(attn, "fp8_qk_exp", None)
-        if lse_out is not None and (fp8 is not None or prev_hidden_states is not None):
-            raise ValueError("lse_out: the single-segment bf16 attention only")
-        fused = qkv is None and fp8 is None and _fusable_norms(attn)
+        if keep is not None and (fp8 is not None or prev_hidden_states is not None or qkv is not None):
+            raise ValueError("keep: the single-segment bf16 attention only")
+        # (the pre-norm q | k a keep-all forward stores are the fused epilogue's second output: it runs that epilogue
+        # whatever VP_NO_QKV_FUSION says — the same bits as the separate launches)
+        fused = qkv is None and fp8 is None and (keeps_all(keep) or _fusable_norms(attn))
         if qkv is None:  # (the block may hand over an fp8 projection)
-            qkv = _qkv(attn, x, (text_len, rope) if fused else None)
+            qkv = _qkv(attn, x, (text_len, rope) if fused else None, keep)
         q, k, v = qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:]
-        eps_k = attn.norm_k.eps
+        nq, nk = attn.norm_q, attn.norm_k
         if fp8 is not None:
-            return self._attend_fp8(attn, q, k, v, text_len, rope, fp8, prev_hidden_states, prev_clip_weight)
-        if not fused:
-            K.head_norm_rope(q, q, H, text_len, attn.norm_q.weight, attn.norm_q.bias, attn.norm_q.eps, rope)
-            K.head_norm_rope(k, k, H, text_len, attn.norm_k.weight, attn.norm_k.bias, eps_k, rope)
-        o = augmented_rows((attn.to_out[0],), B, Ntok, D, x.device)
-        if prev_hidden_states is not None and prev_clip_weight is not None and prev_clip_weight > 0.0:
-            pkv = _kv(attn, _rows(prev_hidden_states))
-            pk, pv = pkv[..., :D], pkv[..., D:]
-            K.head_norm_rope(pk, pk, H, text_len, attn.norm_k.weight, attn.norm_k.bias, eps_k, rope)
-            w = float(prev_clip_weight)
-            bs = bounded_scores(attn)
-            K.attention(q, k, v, o, H, scale=attn.scale, out_scale=1.0 - w, bounded_scores=bs)
-            K.attention(q, pk, pv, o, H, scale=attn.scale, out_scale=w, accumulate=True, bounded_scores=bs)
+            # fp8 attention (BASELINE config 5): qk-norm + RoPE written as e4m3 with the static power-of-two factors
+            # chosen by `CogVideoXBlock.enable_fp8_attention` (Q's includes scale * log2 e), V packed to e4m3 V^T with
+            # per-(d, 32 keys) scales, the block-scaled MFMA kernel
+            q_exp, k_exp = fp8
+
+            def operands(k_, v_):
+                return (K.head_norm_rope_fp8(k_, H, text_len, nk.weight, nk.bias, nk.eps, rope, 2.0 ** k_exp),
+                        K.v_pack_fp8(v_, H))
+
+            def attention(k_, v_, **kw):
+                K.attention_fp8(q8, k_, v_, o, H, q_exp, k_exp, **kw)
+            q8 = K.head_norm_rope_fp8(q, H, text_len, nq.weight, nq.bias, nq.eps, rope,
+                                      attn.scale * K.LOG2E * 2.0 ** q_exp)
+            own = operands(k, v)
         else:
-            K.attention(q, k, v, o, H, scale=attn.scale, bounded_scores=bounded_scores(attn), lse=lse_out)
+            if not fused:
+                K.head_norm_rope(q, q, H, text_len, nq.weight, nq.bias, nq.eps, rope)
+                K.head_norm_rope(k, k, H, text_len, nk.weight, nk.bias, nk.eps, rope)
+
+            def operands(k_, v_):
+                return K.head_norm_rope(k_, k_, H, text_len, nk.weight, nk.bias, nk.eps, rope), v_
+
+            def attention(k_, v_, **kw):
+                K.attention(q, k_, v_, o, H, scale=attn.scale, bounded_scores=bs, **kw)
+            own, bs = (k, v), bounded_scores(attn)
+        o = augmented_rows((attn.to_out[0],), B, Ntok, D, x.device)
+        alone = {}
+        if keep is not None:
+            keep["o"], keep["lse"] = o, torch.empty(B, H, Ntok, device=x.device, dtype=torch.float32)
+            alone["lse"] = keep["lse"]
+        self._blend(attn, own, prev_hidden_states, prev_clip_weight, operands, attention, **alone)
         return o
 
     @staticmethod
-    def _attend_fp8(attn, q, k, v, text_len, rope, exps, prev_hidden_states, prev_clip_weight) -> torch.Tensor:
-        """fp8 attention (BASELINE config 5): qk-norm + RoPE written as e4m3 with the static power-of-two factors
-        chosen by `CogVideoXBlock.enable_fp8_attention` (Q's includes scale * log2 e), V packed to e4m3 V^T with
-        per-(d, 32 keys) scales, the block-scaled MFMA kernel; the prev-clip blend as in the bf16 path."""
-        B, Ntok, D = q.shape
-        H = attn.heads
-        q_exp, k_exp = exps
-        qmul = attn.scale * K.LOG2E * 2.0 ** q_exp
-        q8 = K.head_norm_rope_fp8(q, H, text_len, attn.norm_q.weight, attn.norm_q.bias, attn.norm_q.eps, rope, qmul)
-        k8 = K.head_norm_rope_fp8(k, H, text_len, attn.norm_k.weight, attn.norm_k.bias, attn.norm_k.eps, rope,
-                                  2.0 ** k_exp)
-        vp = K.v_pack_fp8(v, H)
-        o = augmented_rows((attn.to_out[0],), B, Ntok, D, q.device)
-        if prev_hidden_states is not None and prev_clip_weight is not None and prev_clip_weight > 0.0:
-            pkv = _kv(attn, _rows(prev_hidden_states))
-            pk8 = K.head_norm_rope_fp8(pkv[..., :D], H, text_len, attn.norm_k.weight, attn.norm_k.bias,
-                                       attn.norm_k.eps, rope, 2.0 ** k_exp)
-            pvp = K.v_pack_fp8(pkv[..., D:], H)
-            del pkv
-            w = float(prev_clip_weight)
-            K.attention_fp8(q8, k8, vp, o, H, q_exp, k_exp, out_scale=1.0 - w)
-            K.attention_fp8(q8, pk8, pvp, o, H, q_exp, k_exp, out_scale=w, accumulate=True)
-        else:
-            K.attention_fp8(q8, k8, vp, o, H, q_exp, k_exp)
-        return o
+    def _blend(attn, own, prev_hidden_states, prev_clip_weight, operands, attention, **alone) -> None:
+        """`attention(k, v, **kw)` over this window's keys `own`, or — with the previous window's states and a
+        weight w > 0 — the prev-clip blend (1 - w) x that + w x the attention over the previous window's K / V
+        (projected in bf16, then `operands(pk, pv)`): two calls into one output.  alone: the unblended call's lse."""
+        if prev_hidden_states is None or prev_clip_weight is None or prev_clip_weight <= 0.0:
+            attention(*own, **alone)
+            return
+        pkv = _kv(attn, _rows(prev_hidden_states))
+        D = pkv.shape[-1] // 2
+        prev = operands(pkv[..., :D], pkv[..., D:])
+        del pkv
+        w = float(prev_clip_weight)
+        attention(*own, out_scale=1.0 - w)
+        attention(*prev, out_scale=w, accumulate=True)
 
     def __call__(self, attn, hidden_states: torch.Tensor, encoder_hidden_states: torch.Tensor,
                  attention_mask: Optional[torch.Tensor] = None, resample_mask: Optional[torch.Tensor] = None,

@@ -6,9 +6,13 @@ The caller is the reference's training step (train/train_cogvideox_inpainting_i2
 transformer into the branch's parameters.  Each piece is a `torch.autograd.Function` whose forward is the inference
 path itself (same launches, same rounding points) and whose backward runs only native kernels:
 
-  * `_BlockFn` — one CogVideoXBlock (cogvideox_transformer_3d.py:125-184), gradient-checkpointed: only the block
-    input is saved; the backward recomputes mod1/mod2, the AdaLN outputs, the pre-norm q/k/v, the normed q/k, the
-    attention output + softmax statistics, the gated residual and the FF1 pre-activation, then runs
+  * `_BlockFn` — one CogVideoXBlock (cogvideox_transformer_3d.py:125-184), gradient-checkpointed.  Its forward IS
+    `block.forward_joint`, with a `keep` dict that the block's stages fill (transformer.py): level "all" while the
+    device has room (SAVE_ACTIVATIONS: mod1 / mod2, q | k | v normed and pre-norm, the attention output + softmax
+    statistics, the gated residual, the FF1 pre-activation; with trainable parameters also the AdaLN outputs, the QKV
+    operand and h), else "attention" (SAVE_ATTENTION: the attention output + statistics), else nothing.  What was not
+    kept the backward recomputes with the same stages (`_block_front`: stopping after the FF front, skipping the
+    attention call when its output was kept), then runs
       FF2 dgrad -> GELU' -> FF1 dgrad -> AdaLN2' (+ residual) -> gate1 row-scale -> to_out dgrad
       -> flash-attention backward -> (LayerNorm(64) + RoPE)' for q, k -> fused QKV dgrad -> AdaLN1' (+ residual)
     with the dgrad GEMMs against cached transposed weights.  Trainable blocks add the weight gradients (one GEMM over
@@ -40,8 +44,8 @@ import torch
 
 from . import _native as NAT
 from . import kernels as K
-from .attention_processor import bounded_scores
-from .attention_processor import project_out
+from .attention_processor import (CogVideoXAttnProcessor2_0, CogVideoXAttnProcessor2_0_resample, _qkv,
+                                  bounded_scores, keeps_all, project_out)
 from .lora import AugmentedProjection, augmented_rows
 
 BF16 = torch.bfloat16
@@ -189,9 +193,12 @@ def _check_block_trainable_path(block, resample_mask=None) -> None:
     if (block.ff_mx is not None or block.qkv_mx is not None or getattr(block, "out_mx", None) is not None
             or getattr(a, "fp8_qk_exp", None) is not None):
         raise NotImplementedError("the backward runs the bf16 path: disable the fp8 modes for training")
-    from .attention_processor import CogVideoXAttnProcessor2_0_resample
-    if isinstance(a.processor, CogVideoXAttnProcessor2_0_resample) and resample_mask is None:
-        raise ValueError("the resample processor needs resample_mask (id_pool_resample needs masks)")
+    if isinstance(a.processor, CogVideoXAttnProcessor2_0_resample):
+        if resample_mask is None:
+            raise ValueError("the resample processor needs resample_mask (id_pool_resample needs masks)")
+    elif resample_mask is not None:
+        # (such a block's forward ignores the mask, while the backward would differentiate the resample attention)
+        raise NotImplementedError("resample_mask on a block without the resample processor has no backward")
 
 
 def _put_linear_grads(G: _Grads, lin, dw: torch.Tensor) -> None:
@@ -199,111 +206,47 @@ def _put_linear_grads(G: _Grads, lin, dw: torch.Tensor) -> None:
     G.put(lin.weight, dw)
 
 
+def _resample_attention(a, xn: torch.Tensor, T: int, rope, resample_mask: torch.Tensor, keep: dict) -> None:
+    """The resample processor's attention as the backward differentiates it, in place of the block's attention
+    stage: keys / values as one explicit 2N-key sequence [K; K2], [V; V2] with K2 = LN(mask . k) + RoPE (masked
+    rows: = K's rows; null rows: the norm_k bias, rotated) and V2 = mask . v.  keep receives the pre-norm
+    projections "qkv", the normed queries "qn", "kc" / "vc", and "o" / "lse"."""
+    B, Ntok, D = xn.shape
+    H, dev, nq, nk = a.heads, xn.device, a.norm_q, a.norm_k
+    qkv = _qkv(a, xn, None, keep)
+    q, k, v = qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:]
+    qn = torch.empty(B, Ntok, D, device=dev, dtype=BF16)
+    kc = torch.empty(B, 2 * Ntok, D, device=dev, dtype=BF16)
+    vc = torch.empty(B, 2 * Ntok, D, device=dev, dtype=BF16)
+    K.head_norm_rope(k, kc[:, Ntok:], H, T, nk.weight, nk.bias, nk.eps, rope, tok_mask=resample_mask, pre_scale=1.0)
+    vc[:, :Ntok].copy_(v)
+    K.mask_scale_rows(v, vc[:, Ntok:], resample_mask, 1.0)
+    K.head_norm_rope(q, qn, H, T, nq.weight, nq.bias, nq.eps, rope)
+    K.head_norm_rope(k, kc[:, :Ntok], H, T, nk.weight, nk.bias, nk.eps, rope)
+    o = augmented_rows((a.to_out[0],), B, Ntok, D, dev)
+    lse = torch.empty(B, H, Ntok, device=dev, dtype=F32)
+    K.attention(qn, kc, vc, o, H, scale=a.scale, bounded_scores=bounded_scores(a), lse=lse)
+    keep.update(qn=qn, kc=kc, vc=vc, o=o, lse=lse)
+
+
 def _block_front(block, x: torch.Tensor, T: int, temb: torch.Tensor, rope, resample_mask, attn_saved=None,
                  with_h: bool = False) -> dict:
-    """forward_joint's launches up to the FF1 pre-activation, with its rounding points, keeping what the backward
-    reads: the recompute of the checkpointed backward, and the front of the training forward (block_forward_saving).
-    The QKV projection runs forward_joint's fused qk-norm + RoPE epilogue and also stores the pre-norm q | k (the
-    GEMM's aux output, ABI 17) for the LayerNorm backward; with_h: FF1 runs its GELU epilogue and stores the
-    pre-activation z as the aux output (h and z from one pass: the same bits as FF1 + vp_gelu_bf16)."""
-    B, Ntok, D = x.shape
-    M = B * Ntok
-    a = block.attn1
-    H = a.heads
-    n1, n2 = block.norm1, block.norm2
-    ff0, to_out = block.ff.net[0].proj, block.attn1.to_out[0]
-    F4 = ff0.weight.shape[0]
-    dev = x.device
-    mod1 = n1.modulation(temb)
-    mod2 = n2.modulation(temb)
-    # trainable LoRA factors run unfused: the projections on K-augmented operands (lora.AugmentedProjection),
-    # which AdaLN and the attention write in place (lora.augmented_rows)
-    xn = K.adaln_modulate(x, n1.norm.weight, n1.norm.bias, mod1, T, n1.norm.eps,
-                          out=augmented_rows((a.to_q, a.to_k, a.to_v), B, Ntok, D, dev))
-    qkv = torch.empty(B, Ntok, 3 * D, device=dev, dtype=BF16)
-    qaug = AugmentedProjection.of((a.to_q, a.to_k, a.to_v))
-    oaug = AugmentedProjection.of((to_out,))
-    xq = xn.view(M, D) if qaug is None else qaug.input(xn.view(M, D))
-    resample = resample_mask is not None
-    qkp = None
-    kw = {}
-    if not resample:
-        # qkv = [norm_q(q) + RoPE | norm_k(k) + RoPE | v] and qkp = the pre-norm [q | k], one GEMM
-        qkp = torch.empty(B, Ntok, 2 * D, device=dev, dtype=BF16)
-        kw = dict(epilogue=NAT.EPI_BIAS_QKNORM_ROPE, qk_norm=(a.norm_q, a.norm_k), rope=rope, tokens_per_batch=Ntok,
-                  text_len=T, aux=qkp.view(M, 2 * D))
-    if qaug is None:
-        K.gemm(xq, [a.to_q.weight, a.to_k.weight, a.to_v.weight], [a.to_q.bias, a.to_k.bias, a.to_v.bias],
-               qkv.view(M, 3 * D), **kw)
+    """The backward's recompute: forward_joint's stages (CogVideoXBlock) up to the FF front with a keep-all dict,
+    which it returns.  attn_saved: the forward's (attention output, lse); then the attention call alone is skipped.
+    with_h: FF1 runs its GELU epilogue (h, and z as its aux output: the same bits as FF1 + vp_gelu_bf16); without,
+    it stores z alone.  Both modulations are computed up front."""
+    keep = dict(level="all", train=True)
+    keep["mod1"], keep["mod2"] = mod1, mod2 = block.norm1.modulation(temb), block.norm2.modulation(temb)
+    xn, _, _ = block._attn_input(x, T, mod1, keep=keep)
+    if resample_mask is not None:
+        _resample_attention(block.attn1, xn, T, rope, resample_mask, keep)
+    elif attn_saved is not None:
+        keep["o"], keep["lse"] = attn_saved
+        _qkv(block.attn1, xn, (T, rope), keep)
     else:
-        qaug.gemm(xq, [a.to_q.bias, a.to_k.bias, a.to_v.bias], qkv.view(M, 3 * D), **kw)
-    v = qkv[..., 2 * D:]
-    if resample:
-        # the resample processor's keys / values as one explicit 2N-key sequence: [K; K2], [V; V2] with
-        # K2 = LN(mask . k) + RoPE (masked rows: = K's rows; null rows: the norm_k bias, rotated), V2 = mask . v
-        qn = torch.empty(B, Ntok, D, device=dev, dtype=BF16)
-        kc = torch.empty(B, 2 * Ntok, D, device=dev, dtype=BF16)
-        vc = torch.empty(B, 2 * Ntok, D, device=dev, dtype=BF16)
-        kn = kc[:, :Ntok]
-        K.head_norm_rope(qkv[..., D:2 * D], kc[:, Ntok:], H, T, a.norm_k.weight, a.norm_k.bias, a.norm_k.eps, rope,
-                         tok_mask=resample_mask, pre_scale=1.0)
-        vc[:, :Ntok].copy_(v)
-        K.mask_scale_rows(v, vc[:, Ntok:], resample_mask, 1.0)
-        katt, vatt = kc, vc
-        K.head_norm_rope(qkv[..., :D], qn, H, T, a.norm_q.weight, a.norm_q.bias, a.norm_q.eps, rope)
-        K.head_norm_rope(qkv[..., D:2 * D], kn, H, T, a.norm_k.weight, a.norm_k.bias, a.norm_k.eps, rope)
-    else:
-        qn, katt, vatt = qkv[..., :D], qkv[..., D:2 * D], v
-    if attn_saved is not None and not resample:
-        o, lse = attn_saved
-    else:
-        o = augmented_rows((to_out,), B, Ntok, D, dev)
-        lse = torch.empty(B, H, Ntok, device=dev, dtype=F32)
-        K.attention(qn, katt, vatt, o, H, scale=a.scale, bounded_scores=bounded_scores(a), lse=lse)
-    x_mid = torch.empty_like(x)
-    project_out(to_out, o.view(M, D), x_mid.view(M, D), epilogue=NAT.EPI_GATED, resid=x.view(M, D), mod=mod1,
-                gate_chunk=2, gate_text_chunk=5, tokens_per_batch=Ntok, text_len=T)
-    xn2 = K.adaln_modulate(x_mid, n2.norm.weight, n2.norm.bias, mod2, T, n2.norm.eps)
-    z = torch.empty(M, F4, device=dev, dtype=BF16)
-    st = dict(mod1=mod1, mod2=mod2, xn=xn, xq=xq, qkv=qkv, o=o, lse=lse, x_mid=x_mid, xn2=xn2, z=z)
-    if with_h:
-        st["h"] = torch.empty(M, F4, device=dev, dtype=BF16)
-        K.gemm(xn2.view(M, D), [ff0.weight], [ff0.bias], st["h"], epilogue=NAT.EPI_BIAS_GELU, aux=z)
-    else:
-        K.gemm(xn2.view(M, D), [ff0.weight], [ff0.bias], z)
-    if resample:
-        st.update(qn=qn, kc=kc, vc=vc)
-    else:
-        st["qkp"] = qkp
-    return st
-
-
-def block_forward_saving(block, x: torch.Tensor, T: int, temb: torch.Tensor, rope, inject=None, inject_mask=None,
-                         keep_train: bool = False):
-    """The block's forward for a training step, keeping its intermediates for the backward (SAVE_ACTIVATIONS): the
-    launches of _block_front (the fused QKV epilogue also storing the pre-norm q | k, FF1's GELU epilogue also storing
-    its pre-activation z), then FF2 with the gated residual + injection exactly as forward_joint: the same output
-    bits.  Kept: mod1 / mod2, the normed q | k + v and the pre-norm q | k, the attention output + lse, x_mid, z (and,
-    for a block with trainable parameters or a temb that needs its gradient, the AdaLN outputs and h)."""
-    B, Ntok, D = x.shape
-    M = B * Ntok
-    ff2 = block.ff.net[2]
-    st = _block_front(block, x, T, temb, rope, None, with_h=True)
-    h = st.pop("h")
-    out = torch.empty_like(x)
-    kw = {}
-    if inject is not None:
-        kw = dict(inject=inject, inject_ld=inject.stride(1), inject_bstride=inject.stride(0), inject_mask=inject_mask)
-    K.gemm(h.view(M, -1), [ff2.weight], [ff2.bias], out.view(M, D), epilogue=NAT.EPI_GATED,
-           resid=st["x_mid"].view(M, D), mod=st["mod2"], gate_chunk=2, gate_text_chunk=5, tokens_per_batch=Ntok,
-           text_len=T, **kw)
-    if keep_train:
-        st["h"] = h
-    else:
-        del h
-        for k in ("xn", "xq", "xn2"):
-            st.pop(k)
-    return out, st
+        block._attention(xn, T, rope, keep=keep)
+    block._ff_front(block._attn_output(x, keep["o"], mod1, T, keep), mod2, T, keep, activate=with_h)
+    return keep
 
 
 def block_backward(block, x: torch.Tensor, T: int, temb: torch.Tensor, rope, inject_mask: Optional[torch.Tensor],
@@ -312,7 +255,7 @@ def block_backward(block, x: torch.Tensor, T: int, temb: torch.Tensor, rope, inj
     """Gradient-checkpointed backward of `block.forward_joint(x, T, temb, rope, resample_mask=.., inject=..,
     inject_mask=..)`.  Returns (dx [B, Ntok, D], dtemb or None, dinject [B, Nv, D] or None, _Grads).  attn_saved:
     the forward's (attention output, lse) — then the attention is not recomputed (SAVE_ATTENTION); front: the
-    training forward's kept intermediates (block_forward_saving) — then nothing is recomputed."""
+    training forward's keep-all dict (_BlockFn.forward) — then nothing is recomputed."""
     B, Ntok, D = x.shape
     M = B * Ntok
     a = block.attn1
@@ -324,8 +267,8 @@ def block_backward(block, x: torch.Tensor, T: int, temb: torch.Tensor, rope, inj
     need_dmod = train or want_dtemb
     G = _Grads()
 
-    # ---- the forward's intermediates: kept by the training forward (SAVE_ACTIVATIONS = "all", block_forward_saving)
-    # or recomputed here with forward_joint's launches and rounding points ----
+    # ---- the forward's intermediates: kept by the training forward (the `keep` level "all") or recomputed here by
+    # forward_joint's own stages ----
     if front is None:
         front = _block_front(block, x, T, temb, rope, resample_mask, attn_saved, with_h=need_dmod)
     f = front
@@ -491,9 +434,8 @@ def block_backward(block, x: torch.Tensor, T: int, temb: torch.Tensor, rope, inj
 # --gradient_checkpointing has it.  The same kernel call produces both (bit-identical to the recompute: the fused QKV
 # epilogue equals the separate norm launches).  False: recompute the attention too.
 SAVE_ATTENTION = True
-# Beyond that, while the device has room (SAVE_ACTIVATIONS = True; the budget below), the training forward runs the
-# backward's front itself (block_forward_saving) and keeps every intermediate the backward reads, so the backward
-# recomputes nothing: ~1.2 GB per frozen 5b block at B = 1, N = 17 776 (q | k | v, the normed q | k, O, x_mid, the FF1
+# Beyond that, while the device has room (SAVE_ACTIVATIONS = True; the budget below), the training forward keeps
+# every intermediate the backward reads (forward_joint's `keep` level "all"), so the backward recomputes nothing: ~1.2 GB per frozen 5b block at B = 1, N = 17 776 (q | k | v, the normed q | k, O, x_mid, the FF1
 # pre-activation z).
 # A block whose kept set would leave less than SAVE_RESERVE_BYTES free (or four times its own size) falls back to
 # the attention-only form, so a larger batch degrades to recompute instead of running out of memory.
@@ -514,18 +456,24 @@ def _room_for(x: torch.Tensor, F4: int, keep_train: bool = False, R: int = 0) ->
 class _BlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, block, T, rope, inject_mask, resample_mask, x, temb, inject, *params):
-        ctx.front = ctx.attn_saved = None
-        keep_train = any(p.requires_grad for p in params) or temb.requires_grad
-        qaug = AugmentedProjection.of((block.attn1.to_q, block.attn1.to_k, block.attn1.to_v)) if keep_train else None
-        if SAVE_ACTIVATIONS and resample_mask is None and _room_for(
-                x, block.ff.net[0].proj.weight.shape[0], keep_train, qaug.R if qaug is not None else 0):
-            out, ctx.front = block_forward_saving(block, x, T, temb, rope, inject,
-                                                  inject_mask if inject is not None else None, keep_train)
-        else:
-            save = {} if SAVE_ATTENTION and resample_mask is None else None
-            out = block.forward_joint(x, T, temb, rope, resample_mask=resample_mask, inject=inject,
-                                      inject_mask=inject_mask if inject is not None else None, attn_save=save)
-            ctx.attn_saved = (save["o"], save["lse"]) if save else None
+        """forward_joint with a `keep` dict at the level the switches and the device's room choose: "all" (then
+        nothing is recomputed; a frozen block drops xn / xq / xn2 / h, train=False), "attention", or none."""
+        a = block.attn1
+        train = any(p.requires_grad for p in params) or temb.requires_grad
+        qaug = AugmentedProjection.of((a.to_q, a.to_k, a.to_v)) if train else None
+        keep = mod1 = mod2 = None
+        if resample_mask is None:
+            if SAVE_ACTIVATIONS and _room_for(x, block.ff.net[0].proj.weight.shape[0], train,
+                                              qaug.R if qaug is not None else 0):
+                keep = dict(level="all", train=train)
+                mod1, mod2 = block.norm1.modulation(temb), block.norm2.modulation(temb)  # (as _block_front)
+            elif SAVE_ATTENTION and type(a.processor) is CogVideoXAttnProcessor2_0:
+                keep = dict(level="attention", train=train)
+        out = block.forward_joint(x, T, temb, rope, resample_mask=resample_mask, inject=inject,
+                                  inject_mask=inject_mask if inject is not None else None, keep=keep, mod1=mod1,
+                                  mod2=mod2)
+        ctx.front = keep if keeps_all(keep) else None
+        ctx.attn_saved = (keep["o"], keep["lse"]) if keep is not None and ctx.front is None else None
         ctx.block, ctx.T, ctx.rope, ctx.inject_mask, ctx.resample_mask = block, T, rope, inject_mask, resample_mask
         ctx.has_inject = inject is not None
         ctx.params = params

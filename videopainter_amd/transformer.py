@@ -15,6 +15,10 @@ video tokens, injection only on video tokens) is selected per row inside the ker
 `batched_modulations`.  With `forward(cfg_shared_video=True)` the first block computes the work its two batch rows —
 the classifier-free-guidance halves — share once, `CogVideoXBlock._attend_cfg_shared`.)
 
+The block's forward is written once, as five stages (`CogVideoXBlock._attn_input`, `_attention`, `_attn_output`,
+`_ff_front`, `_ff_back`): `forward_joint` composes them, a training forward is the same call with a `keep` dict the
+stages fill for the backward, and the backward's recompute (autograd._block_front) runs the same stages.
+
 With `return_hidden_states=True` every block writes its output into a fresh buffer that IS the returned
 `hidden_states_list[i]` (no copies).
 """
@@ -31,7 +35,7 @@ from . import kernels as K
 from . import _native as NAT
 from .attention_processor import (Attention, CogVideoXAttnProcessor2_0, CogVideoXAttnProcessor2_0_resample,
                                   CogVideoXAttnProcessor2_0_wo_text, _fusable_norms, _rope_dev, _u8,
-                                  bounded_scores, cfg_shared_attention, project_out)
+                                  bounded_scores, cfg_shared_attention, keeps_all, project_out)
 from .embeddings import joint_sincos_pos_embedding
 from .lora import AugmentedProjection, augmented_rows
 from .modules import Conv2dPatch, Dropout, LayerNorm, Linear, ModelMixin, _empty
@@ -296,10 +300,11 @@ class CogVideoXBlock(nn.Module):
           (d) merge of (a) and (b) (vp_attention_merge_bf16)               -> o's video rows of both halves."""
         B, N_, D = x.shape
         T, a, H = text_len, self.attn1, self.attn1.heads
-        n1 = self.norm1.norm
         xn = torch.empty_like(x)
-        K.adaln_modulate(x[:1], n1.weight, n1.bias, mod1[:1], T, n1.eps, out=xn[0])
-        K.adaln_modulate(x[1:, :T], n1.weight, n1.bias, mod1[1:], T, n1.eps, out=xn[1, :T])
+        self._norm1(x[:1], mod1[:1], T, out=xn[0])
+        self._norm1(x[1:, :T], mod1[1:], T, out=xn[1, :T])
+        # (the QKV GEMM on a row slice of the two halves: _qkv projects whole [B, N, D] operands, so this one call
+        # stays apart from it; _cfg_shared_ok admits no LoRA operand here)
         qkv = torch.empty(B, N_, 3 * D, device=x.device, dtype=BF16)
         M = N_ + T
         K.gemm(xn.view(B * N_, D)[:M], [a.to_q.weight, a.to_k.weight, a.to_v.weight],
@@ -312,12 +317,120 @@ class CogVideoXBlock(nn.Module):
         cfg_shared_attention(q, k, v, o, H, T, scale=a.scale, bounded_scores=bounded_scores(a))
         return o
 
+    # -- the block's forward as stages; the modulation vectors are their inputs --
+    def _norm1(self, x: torch.Tensor, mod1: torch.Tensor, text_len: int, out=None) -> torch.Tensor:
+        n = self.norm1.norm
+        return K.adaln_modulate(x, n.weight, n.bias, mod1, text_len, n.eps, out=out)
+
+    def _attn_input(self, x: torch.Tensor, text_len: int, mod1: torch.Tensor, prev_joint=None, augment: bool = True,
+                    keep: Optional[dict] = None):
+        """norm1 AdaLN -> (xn, qkv, pn): the attention's bf16 operand xn (written straight into the projection's
+        K-augmented operand under unfused LoRA, unless an `attend` hook takes it: augment=False), or with the fp8 QKV
+        projection the MX-FP8 modulate + GEMM's output qkv; pn: the previous window's states through the same norm1
+        (reference :141-146), the prev-clip K / V operand."""
+        B, Ntok, D = x.shape
+        a, n1 = self.attn1, self.norm1.norm
+        xn = qkv = pn = None
+        if self.qkv_mx is not None:
+            xq = K.adaln_modulate_mx(x, n1.weight, n1.bias, mod1, text_len, n1.eps)
+            qkv = torch.empty(B, Ntok, 3 * D, device=x.device, dtype=x.dtype)
+            K.gemm_mx(xq, list(self.qkv_mx), [a.to_q.bias, a.to_k.bias, a.to_v.bias], qkv.view(B * Ntok, 3 * D))
+        else:
+            xn = self._norm1(x, mod1, text_len,
+                             augmented_rows((a.to_q, a.to_k, a.to_v), B, Ntok, D, x.device) if augment else None)
+            if keeps_all(keep) and keep["train"]:
+                keep["xn"] = xn
+        if prev_joint is not None:
+            pn = self._norm1(_bf(prev_joint), mod1, text_len,
+                             augmented_rows((a.to_k, a.to_v), prev_joint.shape[0], prev_joint.shape[1], D, x.device))
+        return xn, qkv, pn
+
+    def _attention(self, x: torch.Tensor, text_len: int, rope, pn=None, prev_clip_weight=None, resample_mask=None,
+                   prev_resample_mask=None, qkv=None, attend=None, keep: Optional[dict] = None) -> torch.Tensor:
+        """x: the attention-input stage's xn (with an fp8 projection `qkv`: any [B, N, D] tensor, for its shape)
+        -> o [B, N, D], through the `attend` hook or the processor.  keep: handed to the processor (which fills it,
+        CogVideoXAttnProcessor2_0.attend) where the attention is the single-segment bf16 one; left as it is
+        elsewhere."""
+        a = self.attn1
+        if attend is not None:
+            return attend(a, x, text_len, rope, pn, prev_clip_weight, resample_mask, prev_resample_mask)
+        if (keep is not None and pn is None and qkv is None and getattr(a, "fp8_qk_exp", None) is None
+                and not isinstance(a.processor, CogVideoXAttnProcessor2_0_resample)):
+            return a.processor.attend(a, x, text_len, rope, keep=keep)
+        return a.processor.attend(a, x, text_len, rope, pn, prev_clip_weight, resample_mask, prev_resample_mask,
+                                  qkv=qkv)
+
+    def _attn_output(self, x: torch.Tensor, o: torch.Tensor, mod1: torch.Tensor, text_len: int,
+                     keep: Optional[dict] = None) -> torch.Tensor:
+        """to_out (bf16, or the fp8 projection of the re-quantised o) with the gated residual on x -> x_mid."""
+        B, Ntok, D = x.shape
+        M = B * Ntok
+        x_mid = torch.empty_like(x)
+        kw = dict(epilogue=NAT.EPI_GATED, resid=x.view(M, D), mod=mod1, tokens_per_batch=Ntok, text_len=text_len)
+        if self.out_mx is not None:
+            om = K.mx_quantize(o.view(M, D), out=K.MXTensor(M, D, x.device, zero=False))
+            K.gemm_mx(om, [self.out_mx], [self.attn1.to_out[0].bias], x_mid.view(M, D), **kw)
+        else:
+            project_out(self.attn1.to_out[0], o.view(M, D), x_mid.view(M, D), gate_chunk=2, gate_text_chunk=5, **kw)
+        if keeps_all(keep):
+            keep["x_mid"] = x_mid
+        return x_mid
+
+    def _ff_front(self, x_mid: torch.Tensor, mod2: torch.Tensor, text_len: int, keep: Optional[dict] = None,
+                  activate: bool = True):
+        """norm2 AdaLN + FF1 with its GELU epilogue -> h (bf16 [B, N, 4D], or MX-FP8 rows with the fp8 FeedForward).
+        keep, at the level "all", receives the pre-activation "z" — the epilogue's aux output, requested then only;
+        a backward that needs no h passes activate=False: FF1 then stores z alone, nothing is returned — and, for
+        trainable parameters, "xn2" and "h"."""
+        B, Ntok, D = x_mid.shape
+        M = B * Ntok
+        n2, ff0 = self.norm2.norm, self.ff.net[0].proj
+        if self.ff_mx is not None:
+            w1 = self.ff_mx[0]
+            xq = K.adaln_modulate_mx(x_mid, n2.weight, n2.bias, mod2, text_len, n2.eps)
+            h = K.MXTensor(M, w1.rows, x_mid.device, zero=False)
+            K.gemm_mx(xq, [w1], [ff0.bias], h, epilogue=NAT.EPI_BIAS_GELU_MXFP8)
+            return h
+        xn2 = K.adaln_modulate(x_mid, n2.weight, n2.bias, mod2, text_len, n2.eps)
+        F4 = ff0.weight.shape[0]
+        h = z = None
+        if keeps_all(keep):
+            keep["z"] = z = torch.empty(M, F4, device=x_mid.device, dtype=BF16)
+        if activate:
+            h = torch.empty(B, Ntok, F4, device=x_mid.device, dtype=BF16)
+            K.gemm(xn2.view(M, D), [ff0.weight], [ff0.bias], h.view(M, F4), epilogue=NAT.EPI_BIAS_GELU, aux=z)
+        else:
+            K.gemm(xn2.view(M, D), [ff0.weight], [ff0.bias], z)
+        if keeps_all(keep) and keep["train"]:
+            keep["xn2"] = xn2
+            if activate:
+                keep["h"] = h.view(M, F4)
+        return h
+
+    def _ff_back(self, x_mid: torch.Tensor, h, mod2: torch.Tensor, text_len: int, inject=None, inject_mask=None,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """FF2 with the gated residual on x_mid and the masked branch injection -> out."""
+        B, Ntok, D = x_mid.shape
+        M = B * Ntok
+        ff2 = self.ff.net[2]
+        if out is None:
+            out = torch.empty_like(x_mid)
+        kw = dict(epilogue=NAT.EPI_GATED, resid=x_mid.view(M, D), mod=mod2, tokens_per_batch=Ntok, text_len=text_len)
+        if self.ff_mx is not None:
+            K.gemm_mx(h, [self.ff_mx[1]], [ff2.bias], out.view(M, D), inject=inject, inject_mask=inject_mask, **kw)
+            return out
+        if inject is not None:
+            kw.update(inject=inject, inject_ld=inject.stride(1), inject_bstride=inject.stride(0),
+                      inject_mask=inject_mask)
+        K.gemm(h.view(M, -1), [ff2.weight], [ff2.bias], out.view(M, D), gate_chunk=2, gate_text_chunk=5, **kw)
+        return out
+
     # -- joint-buffer fast path used by the models --
     def forward_joint(self, x: torch.Tensor, text_len: int, temb: torch.Tensor, rope=None,
                       resample_mask: Optional[torch.Tensor] = None, prev_joint: Optional[torch.Tensor] = None,
                       prev_clip_weight: Optional[float] = None, prev_resample_mask: Optional[torch.Tensor] = None,
                       inject: Optional[torch.Tensor] = None, inject_mask: Optional[torch.Tensor] = None,
-                      out: Optional[torch.Tensor] = None, attend=None, attn_save: Optional[dict] = None,
+                      out: Optional[torch.Tensor] = None, attend=None, keep: Optional[dict] = None,
                       mod1: Optional[torch.Tensor] = None, mod2: Optional[torch.Tensor] = None,
                       cfg_shared_video: bool = False) -> torch.Tensor:
         """mod1 / mod2: the norm1 / norm2 modulation vectors [B, 6D] when the model computed every block's in one
@@ -325,101 +438,35 @@ class CogVideoXBlock(nn.Module):
         the two batch rows of x hold the same video rows (the CFG halves entering the model's first block) — the
         block then computes their shared work once (_attend_cfg_shared) where it runs the plain bf16 path.
         attend: optional replacement of the processor's attention, `attend(attn, xn, text_len, rope) -> o`
-        [B, N, D] (the Ulysses head-parallel split, videopainter_amd/ulysses.py).  attn_save: a dict that receives the
-        attention output "o" and its softmax statistics "lse" (a training forward keeps them for the backward,
-        autograd.SAVE_ATTENTION); left empty where the attention is not the single-segment bf16 one."""
-        B, Ntok, D = x.shape
-        xf = x.view(B * Ntok, D)
+        [B, N, D] (the Ulysses head-parallel split, videopainter_amd/ulysses.py).
+        keep: {"level": "attention" | "all", "train": bool}, a training forward's dict that the stages fill for its
+        backward (autograd._BlockFn) without changing a launch.  "attention": the attention output "o" and its softmax
+        statistics "lse" (where the attention is the single-segment bf16 one).  "all": also "mod1", "mod2", "qkv",
+        the pre-norm q | k "qkp", "x_mid" and the FF1 pre-activation "z" (the two GEMMs' aux outputs, requested at this
+        level only) and, with train, "xn", "xq", "xn2" and "h"."""
         processor = self.attn1.processor
         if not isinstance(processor, CogVideoXAttnProcessor2_0):
             raise ValueError(f"Unsupported processor type: {type(processor)}")
-        if mod1 is None:
-            mod1 = self.norm1.modulation(temb)
-        qkv = None
         if attend is not None and (self.qkv_mx is not None or self.out_mx is not None):
             raise NotImplementedError("the head-parallel split runs the bf16 path")
-        o = None
-        if (cfg_shared_video and attend is None and attn_save is None and prev_joint is None
+        if mod1 is None:
+            mod1 = self.norm1.modulation(temb)
+        if (cfg_shared_video and attend is None and keep is None and prev_joint is None
                 and self._cfg_shared_ok(x, text_len)):
             o = self._attend_cfg_shared(x, text_len, mod1, rope)
-            xn = None
-        elif self.qkv_mx is not None:
-            a = self.attn1
-            xq = K.adaln_modulate_mx(x, self.norm1.norm.weight, self.norm1.norm.bias, mod1, text_len,
-                                     self.norm1.norm.eps)
-            qkv = torch.empty(B, Ntok, 3 * D, device=x.device, dtype=x.dtype)
-            K.gemm_mx(xq, list(self.qkv_mx), [a.to_q.bias, a.to_k.bias, a.to_v.bias], qkv.view(B * Ntok, 3 * D))
-            del xq
-            xn = None
         else:
-            a = self.attn1  # (unfused LoRA: AdaLN writes straight into the projection's K-augmented operand)
-            xn = K.adaln_modulate(x, self.norm1.norm.weight, self.norm1.norm.bias, mod1, text_len,
-                                  self.norm1.norm.eps,
-                                  out=None if attend is not None else
-                                  augmented_rows((a.to_q, a.to_k, a.to_v), B, Ntok, D, x.device))
-        pn = None
-        if prev_joint is not None:
-            # the block normalises the previous window's states with its own norm1 (reference :141-146)
-            a = self.attn1
-            pout = augmented_rows((a.to_k, a.to_v), prev_joint.shape[0], prev_joint.shape[1], D, x.device)
-            pn = K.adaln_modulate(_bf(prev_joint), self.norm1.norm.weight, self.norm1.norm.bias, mod1, text_len,
-                                  self.norm1.norm.eps, out=pout)
-        lse = None
-        if (attn_save is not None and attend is None and type(processor) is CogVideoXAttnProcessor2_0 and pn is None
-                and qkv is None and getattr(self.attn1, "fp8_qk_exp", None) is None):
-            lse = torch.empty(B, self.attn1.heads, Ntok, device=x.device, dtype=torch.float32)
-        if o is None:  # (else: the shared path attended already)
-            if attend is not None:
-                o = attend(self.attn1, xn, text_len, rope, pn, prev_clip_weight, resample_mask, prev_resample_mask)
-            elif lse is not None:
-                o = processor.attend(self.attn1, xn, text_len, rope, lse_out=lse)
-                attn_save["o"], attn_save["lse"] = o, lse
-            else:
-                o = processor.attend(self.attn1, xn if xn is not None else x, text_len, rope, pn, prev_clip_weight,
-                                     resample_mask, prev_resample_mask, qkv=qkv)
-        del qkv
-        del xn, pn
-        x_mid = torch.empty_like(x)
-        if self.out_mx is not None:
-            om = K.mx_quantize(o.view(B * Ntok, D), out=K.MXTensor(B * Ntok, D, x.device, zero=False))
-            del o
-            K.gemm_mx(om, [self.out_mx], [self.attn1.to_out[0].bias], x_mid.view(B * Ntok, D),
-                      epilogue=NAT.EPI_GATED, resid=xf, mod=mod1, tokens_per_batch=Ntok, text_len=text_len)
-            del om
-        else:
-            project_out(self.attn1.to_out[0], o.view(B * Ntok, D), x_mid.view(B * Ntok, D), epilogue=NAT.EPI_GATED,
-                        resid=xf, mod=mod1, gate_chunk=2, gate_text_chunk=5, tokens_per_batch=Ntok,
-                        text_len=text_len)
-            del o
+            xn, qkv, pn = self._attn_input(x, text_len, mod1, prev_joint, attend is None, keep)
+            o = self._attention(xn if xn is not None else x, text_len, rope, pn, prev_clip_weight, resample_mask,
+                                prev_resample_mask, qkv, attend, keep)
+            del xn, qkv, pn
+        x_mid = self._attn_output(x, o, mod1, text_len, keep)
+        del o
         if mod2 is None:
             mod2 = self.norm2.modulation(temb)
-        ff0 = self.ff.net[0].proj
-        ff2 = self.ff.net[2]
-        if out is None:
-            out = torch.empty_like(x)
-        if self.ff_mx is not None:
-            w1, w2 = self.ff_mx
-            xq = K.adaln_modulate_mx(x_mid, self.norm2.norm.weight, self.norm2.norm.bias, mod2, text_len,
-                                     self.norm2.norm.eps)
-            h1 = K.MXTensor(B * Ntok, w1.rows, x.device, zero=False)
-            K.gemm_mx(xq, [w1], [ff0.bias], h1, epilogue=NAT.EPI_BIAS_GELU_MXFP8)
-            del xq
-            K.gemm_mx(h1, [w2], [ff2.bias], out.view(B * Ntok, D), epilogue=NAT.EPI_GATED,
-                      resid=x_mid.view(B * Ntok, D), mod=mod2, tokens_per_batch=Ntok, text_len=text_len,
-                      inject=inject, inject_mask=inject_mask)
-            return out
-        xn2 = K.adaln_modulate(x_mid, self.norm2.norm.weight, self.norm2.norm.bias, mod2, text_len,
-                               self.norm2.norm.eps)
-        h1 = K.linear(xn2, ff0.weight, ff0.bias, gelu=True)
-        del xn2
-        kw = {}
-        if inject is not None:
-            kw = dict(inject=inject, inject_ld=inject.stride(1), inject_bstride=inject.stride(0),
-                      inject_mask=inject_mask)
-        K.gemm(h1.view(B * Ntok, -1), [ff2.weight], [ff2.bias], out.view(B * Ntok, D), epilogue=NAT.EPI_GATED,
-               resid=x_mid.view(B * Ntok, D), mod=mod2, gate_chunk=2, gate_text_chunk=5, tokens_per_batch=Ntok,
-               text_len=text_len, **kw)
-        return out
+        if keeps_all(keep):
+            keep["mod1"], keep["mod2"] = mod1, mod2
+        return self._ff_back(x_mid, self._ff_front(x_mid, mod2, text_len, keep), mod2, text_len, inject, inject_mask,
+                             out)
 
     def forward(self, hidden_states: torch.Tensor, encoder_hidden_states: torch.Tensor, temb: torch.Tensor,
                 image_rotary_emb=None, attention_mask=None, resample_mask=None,
@@ -649,6 +696,31 @@ class CogVideoXTransformer3DModel(ModelMixin):
         from .autograd import time_embed_apply
         return time_embed_apply(self.time_embedding, temb0)
 
+    def _token_masks(self, masks: Optional[torch.Tensor], resample: bool, text_len: int):
+        """(tok_mask, resample_mask, its uint8 form) of a forward: the latent masks patchified to one byte per video
+        token [B, Nv] (None without masks), and with `resample` (id_pool_resample_learnable / return_resample_mask)
+        the bool joint-token mask [B, T + Nv] of the resample processor, text rows clear."""
+        tok_mask = resample_mask = None
+        if masks is not None:
+            tok_mask = K.patch_mask(masks.detach().to(self.proj_out.weight.device), self.config.patch_size)
+        if resample:
+            if tok_mask is None:
+                # the reference reads an unbound `masks` here (UnboundLocalError); we fail explicitly
+                raise ValueError("id_pool_resample needs masks")
+            resample_mask = torch.zeros(tok_mask.shape[0], text_len + tok_mask.shape[1], device=tok_mask.device,
+                                        dtype=torch.bool)
+            resample_mask[:, text_len:] = tok_mask.bool()
+        return tok_mask, resample_mask, _u8(resample_mask)
+
+    def _branch_sample(self, samples: Optional[list], i: int, add_first) -> Optional[torch.Tensor]:
+        """The branch sample injected after block i (reference :579-591): each sample serves a run of
+        ceil(L / n) consecutive blocks, or with add_first the first n blocks take one each."""
+        if not samples:
+            return None
+        if not add_first:
+            return samples[i // int(np.ceil(len(self.transformer_blocks) / len(samples)))]
+        return samples[i] if i < len(samples) else None
+
     def batched_modulations(self, emb: torch.Tensor) -> Optional[torch.Tensor]:
         """Every block's norm1 / norm2 modulation vectors in one launch: bf16 [2 L, B, 6 D], entry 2 i the norm1 and
         2 i + 1 the norm2 modulation of block i, bit-equal to the blocks' own `modulation(emb)` calls — they all read
@@ -706,24 +778,15 @@ class CogVideoXTransformer3DModel(ModelMixin):
 
         emb = self._time_embed(timestep, B, dev)
         x = self.patch_embed.embed(enc, hs)
-        # the token mask: from self_guidance_masks when given, else from branch_block_masks (reference :518-523); it
-        # is the injection mask (when branch_block_masks is given), the resample mask and the self-guidance mask
-        tok_mask = None
-        mask_src = self_guidance_masks if self_guidance_masks is not None else branch_block_masks
-        if mask_src is not None:
-            tok_mask = K.patch_mask(mask_src.to(dev), p)
-        if self_guidance_hidden_states is not None and tok_mask is None:
+        if self_guidance_hidden_states is not None and self_guidance_masks is None and branch_block_masks is None:
             # the reference reads an unbound `masks` here; we fail explicitly
             raise ValueError("self_guidance_hidden_states need self_guidance_masks or branch_block_masks")
-        resample_mask = None
-        if id_pool_resample_learnable or return_resample_mask:
-            if tok_mask is None:
-                # the reference reads an unbound `masks` here (UnboundLocalError); we fail explicitly
-                raise ValueError("id_pool_resample needs masks")
-            resample_mask = torch.zeros(B, Ntok, device=dev, dtype=torch.bool)
-            resample_mask[:, T:] = tok_mask.bool()
+        # the token mask: from self_guidance_masks when given, else from branch_block_masks (reference :518-523); it
+        # is the injection mask (when branch_block_masks is given), the resample mask and the self-guidance mask
+        tok_mask, resample_mask, rm_u8 = self._token_masks(
+            self_guidance_masks if self_guidance_masks is not None else branch_block_masks,
+            id_pool_resample_learnable or return_resample_mask, T)
         rope = _rope_dev(image_rotary_emb, dev, grid=(F, H // p, W // p))
-        rm_u8 = _u8(resample_mask)
 
         prev_states = None
         prev_w = None
@@ -736,18 +799,11 @@ class CogVideoXTransformer3DModel(ModelMixin):
         bs = None
         if branch_block_samples is not None:
             bs = [_bf(s.to(dev)) for s in branch_block_samples]
-        nl = len(self.transformer_blocks)
-        interval = int(np.ceil(nl / len(bs))) if bs else 1
         hidden_states_list: List[torch.Tensor] = []
         ping = None
         mods = self.batched_modulations(emb)
         for i, block in enumerate(self.transformer_blocks):
-            inj = None
-            if bs is not None:
-                if not add_first:
-                    inj = bs[i // interval]
-                elif i < len(bs):
-                    inj = bs[i]
+            inj = self._branch_sample(bs, i, add_first)
             pj = None
             if prev_states is not None:
                 pj = prev_states.get(i) if isinstance(prev_states, dict) else prev_states
@@ -815,31 +871,16 @@ class CogVideoXTransformer3DModel(ModelMixin):
         T = enc.shape[1]
         emb = self._time_embed(timestep, B, dev)
         x = AG.patch_embed_apply(self.patch_embed, enc, hs)
-        tok_mask = None
-        if branch_block_masks is not None:
-            tok_mask = K.patch_mask(branch_block_masks.detach().to(dev), p)
-        resample_mask = rm_u8 = None
-        if id_pool_resample_learnable or return_resample_mask:
-            # the VideoPainterID training step (train_cogvideox_inpainting_i2v_video_resample.py:1951-1961): window
-            # 0's resample processor, differentiable (autograd.block_backward)
-            if tok_mask is None:
-                raise ValueError("id_pool_resample needs masks")
-            resample_mask = torch.zeros(B, T + tok_mask.shape[1], device=dev, dtype=torch.bool)
-            resample_mask[:, T:] = tok_mask.bool()
-            rm_u8 = _u8(resample_mask)
+        # (with id_pool_resample: the VideoPainterID training step, train_cogvideox_inpainting_i2v_video_resample.py
+        # :1951-1961 — window 0's resample processor, differentiable, autograd.block_backward)
+        tok_mask, _, rm_u8 = self._token_masks(branch_block_masks, id_pool_resample_learnable or return_resample_mask,
+                                               T)
         rope = _rope_dev(image_rotary_emb, dev, grid=(F, H // p, W // p))
         bs = None
         if branch_block_samples is not None:
             bs = [s.to(dev, BF16) for s in branch_block_samples]
-        nl = len(self.transformer_blocks)
-        interval = int(np.ceil(nl / len(bs))) if bs else 1
         for i, block in enumerate(self.transformer_blocks):
-            inj = None
-            if bs is not None:
-                if not add_first:
-                    inj = bs[i // interval]
-                elif i < len(bs):
-                    inj = bs[i]
+            inj = self._branch_sample(bs, i, add_first)
             x = AG.block_apply(block, x, T, emb, rope, inj, tok_mask if inj is not None else None, rm_u8)
         output = AG.head_apply(self, x, emb, (B, F, H, W, T))
         if not return_dict:
