@@ -26,7 +26,7 @@ extern "C" {
 #define VP_ERR_UNSUPPORTED 1001
 
 /* ABI version: bump when any struct layout or signature below changes. */
-#define VP_ABI_VERSION 23
+#define VP_ABI_VERSION 24
 int vp_abi_version(void);
 /* "<sha256 of sources + flags>:<sha256 of the compiler version>" of the build (no reference counterpart) */
 const char* vp_build_digest(void);
@@ -285,18 +285,34 @@ typedef struct vp_attn_merge_desc {
 #define VP_MERGE_IN_F32 1
 int vp_attention_merge_bf16(const vp_attn_merge_desc* d, void* stream);
 
-/* fp8 attention (BASELINE config 5 "attn + FFN in fp8"; same math as vp_attention_fwd_bf16, single K/V segment).
+/* fp8 attention (BASELINE config 5 "attn + FFN in fp8"; same math as vp_attention_fwd_bf16).
  * base.Q / base.K: e4m3 [B, N, H*64] written by vp_head_norm_rope_fp8 (strides in bytes, multiples of 16), each
  * carrying one power-of-two factor undone by the E8M0 bytes in qk_scale (bits 0-7: Q, bits 8-15: K; Q's factor
  * also includes scale * log2 e, so base.scale is ignored).  base.V: V^T e4m3 [B, H, 64, npad] and vs: its scales,
  * both from vp_v_pack_fp8.  base.O / out_scale / accumulate as in the bf16 kernel.  The probabilities P enter the
  * PV product (and the row sums) as e4m3 codes of p * 2^7 made by linear mantissa interpolation of exp2 (relative
- * error 3.2 % rms; env VP_ATTN8_VARIANT=1: exp2 + round-to-nearest e4m3, 2.7 %) — DESIGN_LOG.md §3.1. */
+ * error 3.2 % rms) — DESIGN_LOG.md §3.1.  env VP_ATTN8_VARIANT (A/B): 2, 3 and 5 (the default) are the valid values;
+ * variant 1 (exp2 + round-to-nearest e4m3) and variant 4 were pruned and return VP_ERR_UNSUPPORTED.
+ *
+ * A second key segment (ABI 24; the resample processor's masked keys; base.Nk2 == 0: none, ABI 23's behaviour).  The
+ * keys of batch row b are segment 1 followed by the first min(base.k2_len[b], Nk2) keys of segment 2 (k2_len NULL: all
+ * Nk2; a row with 0 reads nothing of K2 / V2).  base.K2: e4m3 [B, Nk2, H*64] (k2_sb / k2_sn in bytes, multiples of
+ * 16) with K's static factor, so qk_scale serves both; base.V2: a second V^T pack [B, H, 64, npad2] with scales vs2
+ * (vp_v_pack_fp8_lens with the same lengths: the kernel reads whole 64-key tiles of the pack, so V rows past the
+ * length must be packed as zeros, not left as they are).  Same scores, P codes, rescale rule and order of accumulation,
+ * tile after tile over segment 1 and then segment 2, each segment's last partial tile masked against its own length.
+ * base.l_extra (score units, as in vp_attn_desc): exp2(l_extra - m) is added to the fp32 row sum once after the last
+ * tile, m the kernel's final reference; -inf adds nothing, a huge value takes the output row to 0, never NaN.
+ * base.k2_full: VP_ERR_UNSUPPORTED.  A second segment, k2_len or l_extra with VP_ATTN8_VARIANT 2 or 3:
+ * VP_ERR_UNSUPPORTED (the default kernel alone has the two-segment instance). */
 typedef struct vp_attn_fp8_desc {
   vp_attn_desc base;
   const void* vs;
   int32_t npad;     /* ceil(Nk / 64) * 64 */
   int32_t qk_scale; /* E8M0 bytes: Q | K << 8 */
+  const void* vs2;  /* scales of the V^T pack base.V2 (ABI 24; NULL with Nk2 == 0) */
+  int32_t npad2;    /* ceil(Nk2 / 64) * 64 */
+  int32_t pad0;
 } vp_attn_fp8_desc;
 
 int vp_attention_fwd_fp8(const vp_attn_fp8_desc* d, void* stream);
@@ -312,6 +328,12 @@ int vp_attention_fwd_fp8_ws(const vp_attn_fp8_desc* d, void* workspace, int64_t 
 int64_t vp_v_pack_fp8_bytes(int32_t B, int32_t H, int32_t N, int64_t* npad, int64_t* scale_bytes);
 int vp_v_pack_fp8(const void* V, int64_t v_sb, int64_t v_sn, int32_t B, int32_t N, int32_t H, void* vt, void* vs,
                   void* stream);
+/* The same with a per-row length (ABI 24): lens int32 [B] (device; NULL: vp_v_pack_fp8).  Rows n >= lens[b] of batch
+ * row b are packed as zeros and are not read (they may hold NaN bit patterns, and a zero P code times a NaN V byte is
+ * NaN on the MFMA); a 64-key tile that lies wholly at or past lens[b] is not written at all — the attention with
+ * k2_len = lens never reads it. */
+int vp_v_pack_fp8_lens(const void* V, int64_t v_sb, int64_t v_sn, int32_t B, int32_t N, int32_t H, void* vt,
+                       void* vs, const int32_t* lens, void* stream);
 
 
 /* ---------------------------------------------------------------------------------------------------------------
@@ -349,6 +371,15 @@ int vp_head_norm_rope_fp8(const void* x_in, int64_t ld_in, int64_t bs_in, void* 
                           int64_t bs_out, int32_t B, int32_t Ntok, int32_t H, int32_t text_len, const void* ln_w,
                           const void* ln_b, float eps, const float* cos, const float* sin, float out_mul,
                           void* stream);
+/* The same with the pre-mask and the row permutation of vp_head_norm_rope_bf16 (ABI 24; the fp8 attention's second
+ * key segment): the input row is first replaced by rnd(rnd(x * tok_mask[b, n]) * pre_scale) when tok_mask != NULL,
+ * and output row n of batch b is written to row dst_rows[b * Ntok + n] when dst_rows != NULL (a negative entry:
+ * neither read nor written).  Each byte is e4m3 of the bf16 value vp_head_norm_rope_bf16 writes, times out_mul. */
+int vp_head_norm_rope_fp8_rows(const void* x_in, int64_t ld_in, int64_t bs_in, void* q_out, int64_t ld_out,
+                               int64_t bs_out, int32_t B, int32_t Ntok, int32_t H, int32_t text_len,
+                               const void* ln_w, const void* ln_b, float eps, const float* cos, const float* sin,
+                               float out_mul, const uint8_t* tok_mask, int64_t mask_bstride, float pre_scale,
+                               const int32_t* dst_rows, void* stream);
 
 /* y[b, n, :] = rnd(rnd(x[b, n, :] * tok_mask[b, n]) * scale) — the masked value copy of the resample processor. */
 /* (vp_head_norm_rope_bf16 and vp_mask_scale_rows_bf16 with dst_rows != NULL: output row n of batch b is written to

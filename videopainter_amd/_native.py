@@ -11,7 +11,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VP_HIP_LIB", os.path.join(_HERE, "_lib", "libvp_hip.so"))
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 vp = C.c_void_p
 i32 = C.c_int32
@@ -65,7 +65,8 @@ class GemmMxDesc(C.Structure):
 
 
 class AttnFp8Desc(C.Structure):
-    _fields_ = [("base", AttnDesc), ("vs", vp), ("npad", i32), ("qk_scale", i32)]
+    _fields_ = [("base", AttnDesc), ("vs", vp), ("npad", i32), ("qk_scale", i32), ("vs2", vp), ("npad2", i32),
+                ("pad0", i32)]
 
 
 class DpmDesc(C.Structure):
@@ -149,7 +150,10 @@ _SIGS = {
     "vp_gemm_variant_built": (i32, [i32]),
     "vp_v_pack_fp8_bytes": (i64, [i32, i32, i32, C.POINTER(i64), C.POINTER(i64)]),
     "vp_v_pack_fp8": (i32, [vp, i64, i64, i32, i32, i32, vp, vp, vp]),
+    "vp_v_pack_fp8_lens": (i32, [vp, i64, i64, i32, i32, i32, vp, vp, vp, vp]),
     "vp_head_norm_rope_fp8": (i32, [vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, vp, vp, f32, vp, vp, f32, vp]),
+    "vp_head_norm_rope_fp8_rows": (i32, [vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, vp, vp, f32, vp, vp, f32, vp,
+                                         i64, f32, vp, vp]),
     "vp_adaln_modulate_bf16": (i32, [vp, vp, i64, i32, i32, i32, i32, vp, vp, f32, vp, i64, vp]),
     "vp_head_norm_rope_bf16": (i32, [vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, vp, vp, f32, vp, vp, vp, i64,
                                      f32, vp, vp]),
@@ -293,7 +297,8 @@ def _source_digest():
     return _b.source_digest()
 
 
-_ERRS = {1000: "VP_ERR_ARG (invalid size/stride/pointer)", 1001: "VP_ERR_UNSUPPORTED"}
+ERR_ARG, ERR_UNSUPPORTED = 1000, 1001
+_ERRS = {ERR_ARG: "VP_ERR_ARG (invalid size/stride/pointer)", ERR_UNSUPPORTED: "VP_ERR_UNSUPPORTED"}
 
 
 def check(rc: int, what: str) -> None:

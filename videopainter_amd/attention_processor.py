@@ -401,9 +401,11 @@ class CogVideoXAttnProcessor2_0_resample(CogVideoXAttnProcessor2_0):
             raise ValueError("the resample processor needs resample_mask (id_pool_resample needs masks)")
         m = _u8(prev_resample_mask if prev else resample_mask)
         plan = self.plan(attn, m, text_len, rope)
+        fp8 = self.fp8_exponents(attn, plan)
         # with the null keys in closed form segment 2 holds masked rows only, and those of window 0 are rows of the
         # normed + rotated K itself: q / k then leave the QKV GEMM through the fused norm + RoPE epilogue
-        fused = plan[3] is not None and qkv is None and _fusable_norms(attn)
+        # (the fp8 form quantises from the pre-norm q / k: no fused epilogue there)
+        fused = plan[3] is not None and qkv is None and fp8 is None and _fusable_norms(attn)
         if qkv is None:  # (the block may hand over an fp8 projection)
             qkv = _qkv(attn, x, (text_len, rope) if fused else None)
         pk = pv = None
@@ -412,7 +414,17 @@ class CogVideoXAttnProcessor2_0_resample(CogVideoXAttnProcessor2_0):
             pk, pv = pkv[..., :D], pkv[..., D:]
         o = augmented_rows((attn.to_out[0],), B, Ntok, D, x.device)
         return self.attend_heads(attn, qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:], text_len, rope, m, plan,
-                                 fused, pk, pv, float(prev_clip_weight) if prev else 0.0, o)
+                                 fused, pk, pv, float(prev_clip_weight) if prev else 0.0, o, fp8=fp8)
+
+    @staticmethod
+    def fp8_exponents(attn, plan):
+        """(q_exp, k_exp) when this call runs the fp8 two-segment attention: the block opted in
+        (enable_fp8_attention(resample=True)), its Q / K factors are set, and the null keys are summed in closed form
+        (plan[3]: grid known, RoPE separable, VP_RESAMPLE_NULLMASS not 0).  None: today's bf16 code — the k2_full
+        form, a plain rope tuple at the plug-in boundary, VP_RESAMPLE_PARTITION=0."""
+        if not getattr(attn, "fp8_resample", False) or plan[3] is None:
+            return None
+        return getattr(attn, "fp8_qk_exp", None)
 
     @staticmethod
     def plan(attn, m: torch.Tensor, text_len: int, rope):
@@ -434,14 +446,42 @@ class CogVideoXAttnProcessor2_0_resample(CogVideoXAttnProcessor2_0):
         return dst, cnt, segments, axes
 
     def attend_heads(self, attn, q, k, v, text_len: int, rope, m, plan, fused: bool, pk=None, pv=None,
-                     w: float = 0.0, o=None) -> torch.Tensor:
+                     w: float = 0.0, o=None, fp8=None) -> torch.Tensor:
         """The processor's attention on [B, N, h*64] views of every head (or of one head group: the Ulysses split,
         videopainter_amd/ulysses.py) — q / k normed + rotated already when `fused`, pre-norm otherwise; pk / pv: the
-        previous window's pre-norm K / V projections (prev-clip blend with weight w), or None."""
+        previous window's pre-norm K / V projections (prev-clip blend with weight w), or None.  fp8: `fp8_exponents`
+        (needs pre-norm q / k and the closed-form plan)."""
         B, Ntok, D = q.shape
         H = D // 64
         dst, cnt, segments, axes = plan
         grid = getattr(rope, "grid", None)
+        if fp8 is not None:
+            if fused or axes is None:
+                raise ValueError("the fp8 resample attention takes pre-norm q / k and the closed-form null-key plan")
+            # the two-segment fp8 kernel: both segments' keys as e4m3 with one static factor, both V as packed V^T;
+            # cnt stays on the device, so segment 2's buffers have N rows and the rows past cnt[b] are never read
+            q_exp, k_exp = fp8
+            nq, nk = attn.norm_q, attn.norm_k
+            q8 = K.head_norm_rope_fp8(q, H, text_len, nq.weight, nq.bias, nq.eps, rope,
+                                      attn.scale * K.LOG2E * 2.0 ** q_exp)
+            k8 = K.head_norm_rope_fp8(k, H, text_len, nk.weight, nk.bias, nk.eps, rope, 2.0 ** k_exp)
+            vp = K.v_pack_fp8(v, H)
+            # segment 2: the masked rows of k (window 0) or of the previous window's K projection x w, in partition
+            # order; its values the same rows of v / pv x w, packed with zeros from row cnt[b] on
+            k2_8 = torch.empty(B, Ntok, D, device=q.device, dtype=torch.uint8)
+            K.head_norm_rope_fp8(pk if pk is not None else k, H, text_len, nk.weight, nk.bias, nk.eps, rope,
+                                 2.0 ** k_exp, out=k2_8, tok_mask=m, pre_scale=w if pk is not None else 1.0,
+                                 dst_rows=dst)
+            v2 = torch.empty(B, Ntok, D, device=q.device, dtype=BF16)
+            K.mask_scale_rows(pv if pk is not None else v, v2, m, w if pk is not None else 1.0, dst_rows=dst)
+            vp2 = K.v_pack_fp8(v2, H, lens=cnt)
+            # the null-key mass reads the bf16 normed + rotated queries (after q8 took the pre-norm q)
+            K.head_norm_rope(q, q, H, text_len, nq.weight, nq.bias, nq.eps, rope)
+            lx = K.null_key_mass(q, H, text_len, grid, nk.bias, axes, m, segments, attn.scale)
+            if o is None:
+                o = torch.empty(B, Ntok, D, device=q.device, dtype=BF16)
+            K.attention_fp8(q8, k8, vp, o, H, q_exp, k_exp, k2=k2_8, vp2=vp2, k2_len=cnt, l_extra=lx)
+            return o
         # segment 2 with the row stride of the fused QKV output (3 D): the attention kernel then streams its full tiles
         # on the same precomputed lane offsets as segment 1 (DESIGN_LOG.md §3.R4)
         # (VP_RESAMPLE_K2_STRIDED=0: contiguous k2 / v2, the general per-lane DMA path; A/B)

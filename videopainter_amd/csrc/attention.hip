@@ -1820,7 +1820,8 @@ __global__ void mx_probe32_kernel(const uint8_t* A, const uint8_t* B, const uint
 // One 256-thread block per (b, h, 64-key tile); thread t: d = t / 4, slots 16 (t % 4) .. +15.
 __global__ __launch_bounds__(256) void v_pack_fp8_kernel(const bf16* __restrict__ V, int64_t v_sb, int64_t v_sn,
                                                          int N, int H, int ntiles, uint8_t* __restrict__ vt,
-                                                         uint8_t* __restrict__ vs) {
+                                                         uint8_t* __restrict__ vs,
+                                                         const int32_t* __restrict__ lens) {
   __shared__ bf16 tile[64][64 + 8];
   const int blk = blockIdx.x;
   const int t = blk % ntiles;
@@ -1828,12 +1829,16 @@ __global__ __launch_bounds__(256) void v_pack_fp8_kernel(const bf16* __restrict_
   const int h = bh % H, b = bh / H;
   const int tid = threadIdx.x;
   const bf16* src = V + (int64_t)b * v_sb + h * 64;
+  // lens: rows at or past lens[b] are packed as zeros without being read (they may hold anything, NaN included);
+  // a tile wholly past it is left unwritten (block-uniform exit, before the barrier)
+  const int nb = lens != nullptr ? max(0, min(lens[b], N)) : N;
+  if (t * 64 >= nb && lens != nullptr) return;
 #pragma unroll
   for (int pass = 0; pass < 2; ++pass) {
     const int key = pass * 32 + (tid >> 3);
     const int n = t * 64 + key;
     bf16x8 x = {};
-    if (n < N) x = *(const bf16x8*)(src + (int64_t)n * v_sn + (tid & 7) * 8);
+    if (n < nb) x = *(const bf16x8*)(src + (int64_t)n * v_sn + (tid & 7) * 8);
     *(bf16x8*)&tile[key][(tid & 7) * 8] = x;
   }
   __syncthreads();
@@ -2185,7 +2190,11 @@ constexpr int F8S_SLOTS = 3;
 typedef __attribute__((address_space(3))) const u32x4 lds_u32x4;
 typedef __attribute__((address_space(3))) const unsigned short lds_u16;
 // one 256-query block (logical id t) of attn_fwd_fp8s
-template <int SUB>
+// SEG2 (an instance of its own; the single-segment instances compile as before): a second key segment base.K2 /
+// base.V2 (V^T pack dd.vs2 / dd.npad2) of min(k2_len[b], Nk2) keys runs tile after tile behind segment 1 — from tile
+// nt1 on a wave's DMA takes another wave-uniform base, tile stride, row stride and scale base (its per-lane offset is
+// recomputed per issue, not kept) — and exp2(l_extra - m) joins the row sum after the last tile.
+template <int SUB, bool SEG2 = false>
 VP_DEV __attribute__((always_inline)) void fp8s_block(const vp_attn_fp8_desc& dd, const int t) {
   constexpr int NW = 8;
   constexpr int OFF = 7;
@@ -2196,7 +2205,11 @@ VP_DEV __attribute__((always_inline)) void fp8s_block(const vp_attn_fp8_desc& dd
   const vp_attn_desc& d = dd.base;
   constexpr int QB = NW * 32;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x;
+  int tid_ = threadIdx.x;
+  // (SEG2: opaque per block, so the persistent loop re-derives the lane constants for every block — a few dozen VALU
+  // — instead of keeping them all live around it, which spilled 10 more of them to scratch)
+  if constexpr (SEG2) asm volatile("" : "+v"(tid_));
+  const int tid = tid_;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 5;
@@ -2206,7 +2219,15 @@ VP_DEV __attribute__((always_inline)) void fp8s_block(const vp_attn_fp8_desc& dd
   const int qb = t - bh * nqb;
   const int b = bh / d.H;
   const int h = bh - b * d.H;
-  const int ntiles = dd.npad >> 6;
+  const int nt1 = dd.npad >> 6;
+  // segment 2 of this batch row: n2 keys in nt2 tiles (0: no tile runs and nothing of K2 / V2 is read)
+  int n2 = 0;
+  if constexpr (SEG2) {
+    n2 = d.Nk2;
+    if (d.k2_len != nullptr) n2 = max(0, min(__builtin_amdgcn_readfirstlane(d.k2_len[b]), n2));
+  }
+  const int nt2 = (n2 + 63) >> 6;
+  const int ntiles = SEG2 ? nt1 + nt2 : nt1;
 
   const int q = qb * QB + wave * 32 + (lane & 31);
   const int qc = q < d.Nq ? q : d.Nq - 1;
@@ -2233,18 +2254,40 @@ VP_DEV __attribute__((always_inline)) void fp8s_block(const vp_attn_fp8_desc& dd
   const char* src0 = kw ? kbase + (int64_t)(wave & 3) * 16 * ksn
                         : (const char*)d.V + ((int64_t)bh * 64 + (wave & 3) * 16) * dd.npad;
   const int64_t tstride = kw ? (int64_t)64 * ksn : 64;
-  const int nfull = kw ? d.Nk >> 6 : ntiles;  // tiles whose rows all lie below Nk
-  const char* vsbase = (const char*)dd.vs + (int64_t)bh * ntiles * 128;
+  const int nfull = kw ? d.Nk >> 6 : nt1;  // tiles whose rows all lie below Nk
+  const char* vsbase = (const char*)dd.vs + (int64_t)bh * nt1 * 128;
   // (the low 32 bits of a generic LDS address are the LDS offset: no address-space cast inside the persistent loop)
   const unsigned lds_smem = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)smem);
   const unsigned lds_w = lds_smem + (kw ? wave * 1024 : F8_TILE + (wave - 4) * 1024);
   const int nsup = (ntiles + SUB - 1) / SUB;
+  // the DMA source for segment 2 (SEG2 only; wave-uniform): row 0 of this (b, h) — the wave's 16 rows go into the
+  // per-lane offset, which is computed per issue — the row stride and the scale base; few scalars are kept, the rest
+  // is derived at the issue (the persistent instance is short of SGPRs)
+  const int rstride2 = !SEG2 ? 0 : kw ? (int)d.k2_sn : (int)dd.npad2;
+  const char* base2 = !SEG2 ? nullptr
+                      : kw  ? (const char*)d.K2 + (int64_t)b * d.k2_sb + h * 64
+                            : (const char*)d.V2 + (int64_t)bh * 64 * dd.npad2;
+  const char* vs2base = SEG2 ? (const char*)dd.vs2 + (int64_t)bh * (dd.npad2 >> 6) * 128 : nullptr;
   auto issue = [&](int ti, int slot) {
 #pragma unroll
     for (int sb = 0; sb < SUB; ++sb) {
       const int kt = ti * SUB + sb;
       if (SUB > 1 && kt >= ntiles) break;  // wave-uniform
       const unsigned st = lds_w + (slot * SUB + sb) * F8_STAGE;
+      if constexpr (SEG2) {
+        if (kt >= nt1) {  // wave-uniform: a tile of segment 2
+          const int k2t = kt - nt1;
+          const int ln = lane_id_opaque();
+          const int pc = ((ln & 3) ^ ((ln >> 4) & 3)) * 16;
+          const int row = (wave & 3) * 16 + (ln >> 2);
+          // K: key rows of the tile, those past n2 (its last tile) re-read key n2 - 1 (masked later); V^T: 64 slots
+          // of the wave's 16 d-rows (both offsets fit 31 bits: checked at the launch)
+          const int vo = kw ? min(k2t * 64 + row, n2 - 1) * rstride2 + pc : row * rstride2 + k2t * 64 + pc;
+          glds16_lds(base2, vo, st);
+          if (wave == 0 && lane < 8) glds16_lds(vs2base + k2t * 128, lane * 16, st + 2 * F8_TILE);
+          continue;
+        }
+      }
       if (kt < nfull) {
         glds16_lds(src0 + kt * tstride, voff, st);
       } else {  // the last K tile: rows past Nk re-read the last key (masked later)
@@ -2364,7 +2407,7 @@ VP_DEV __attribute__((always_inline)) void fp8s_block(const vp_attn_fp8_desc& dd
       thr = C0 + LS * THR;
     }
     f8_lin2_pack(s, pf);
-    const int lim = d.Nk - kt * 64;
+    const int lim = SEG2 && kt >= nt1 ? n2 - (kt - nt1) * 64 : d.Nk - kt * 64;
     if (lim < 64) {  // byte j of pf[4 hh + w] is key 32 hh + 8 w + 4 g + j (lane id opaque: nothing hoisted)
       const int kb = 4 * (lane_id_opaque() >> 5);
 #pragma unroll
@@ -2408,15 +2451,24 @@ VP_DEV __attribute__((always_inline)) void fp8s_block(const vp_attn_fp8_desc& dd
   }
   const int qq = lane & 31;
   const float v0 = __shfl(lsum[0], qq & 15, 64), v1 = __shfl(lsum[1], qq & 15, 64);
-  store_out(d, o, qq < 16 ? v0 : v1, q, b, h, g, false);
+  if constexpr (!SEG2) {
+    store_out(d, o, qq < 16 ? v0 : v1, q, b, h, g, false);
+  } else {
+    // the extra row mass, once, in the row sum's units (P = p 2^OFF relative to the final reference m_run): -inf adds
+    // 0, a huge value takes the sum to inf and the output row to 0; m_run is finite, so never NaN
+    float l_row = qq < 16 ? v0 : v1;
+    if (d.l_extra != nullptr)  // (q clamped again here, not kept through the loop)
+      l_row += __builtin_amdgcn_exp2f(d.l_extra[((int64_t)b * d.H + h) * d.Nq + min(q, d.Nq - 1)] - m_run + (float)OFF);
+    store_out(d, o, l_row, q, b, h, g, false);
+  }
 }
 
 // PERS: persistent (tickets: 8 zeroed counters) — resident workgroups take the blocks by per-XCD ticket (xcd_ticket):
 // the XCDs run at different clocks
-template <int SUB, bool PERS = false>
+template <int SUB, bool PERS = false, bool SEG2 = false>
 __global__ __launch_bounds__(512, 4) void attn_fwd_fp8s(const vp_attn_fp8_desc dd, int* tickets) {
   if constexpr (!PERS) {
-    fp8s_block<SUB>(dd, xcd_remap(blockIdx.x, gridDim.x));
+    fp8s_block<SUB, SEG2>(dd, xcd_remap(blockIdx.x, gridDim.x));
   } else {
     __shared__ int tk[1];
     const int n = dd.base.B * dd.base.H * ((dd.base.Nq + 255) / 256);
@@ -2429,7 +2481,7 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_fp8s(const vp_attn_fp8_desc d
       const int c = tk[0];
       __syncthreads();
       if (c < 0) break;
-      fp8s_block<SUB>(dd, c);
+      fp8s_block<SUB, SEG2>(dd, c);
     }
   }
 }
@@ -2737,16 +2789,21 @@ extern "C" int64_t vp_v_pack_fp8_bytes(int32_t B, int32_t H, int32_t N, int64_t*
   return (int64_t)B * H * 64 * np;
 }
 
-extern "C" int vp_v_pack_fp8(const void* V, int64_t v_sb, int64_t v_sn, int32_t B, int32_t N, int32_t H, void* vt,
-                             void* vs, void* stream) {
+extern "C" int vp_v_pack_fp8_lens(const void* V, int64_t v_sb, int64_t v_sn, int32_t B, int32_t N, int32_t H,
+                                  void* vt, void* vs, const int32_t* lens, void* stream) {
   if (!V || !vt || !vs || B <= 0 || N <= 0 || H <= 0 || (v_sn % 8) || (v_sb % 8)) return VP_ERR_ARG;
   const int ntiles = (N + 63) / 64;
   const int64_t grid = (int64_t)B * H * ntiles;
   if (grid > 0x7fffffff) return VP_ERR_ARG;
   hipLaunchKernelGGL(v_pack_fp8_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, (const bf16*)V,
-                     v_sb, v_sn, N, H, ntiles, (uint8_t*)vt, (uint8_t*)vs);
+                     v_sb, v_sn, N, H, ntiles, (uint8_t*)vt, (uint8_t*)vs, lens);
   VP_CHECK_LAUNCH();
   return VP_OK;
+}
+
+extern "C" int vp_v_pack_fp8(const void* V, int64_t v_sb, int64_t v_sn, int32_t B, int32_t N, int32_t H, void* vt,
+                             void* vs, void* stream) {
+  return vp_v_pack_fp8_lens(V, v_sb, v_sn, B, N, H, vt, vs, nullptr, stream);
 }
 
 namespace {
@@ -2791,12 +2848,21 @@ extern "C" int vp_attention_fwd_fp8_ws(const vp_attn_fp8_desc* dd, void* ws, int
                        : nullptr;
   const vp_attn_desc& d = dd->base;
   if (!d.Q || !d.K || !d.V || !d.O || !dd->vs) return VP_ERR_ARG;
-  if (d.head_dim != 64 || d.Nk2 != 0) return VP_ERR_UNSUPPORTED;
-  if (d.B <= 0 || d.H <= 0 || d.Nq <= 0 || d.Nk <= 0) return VP_ERR_ARG;
+  if (d.head_dim != 64 || d.k2_full != nullptr) return VP_ERR_UNSUPPORTED;
+  if (d.B <= 0 || d.H <= 0 || d.Nq <= 0 || d.Nk <= 0 || d.Nk2 < 0) return VP_ERR_ARG;
   if (dd->npad != (d.Nk + 63) / 64 * 64) return VP_ERR_ARG;
   if ((d.q_sn % 16) || (d.k_sn % 16) || (d.q_sb % 16) || (d.k_sb % 16) || (d.o_sn % 4) || (d.o_sb % 4))
     return VP_ERR_ARG;
   if ((int64_t)d.Nk * d.k_sn > 0x7fffffff || (int64_t)64 * dd->npad > 0x7fffffff) return VP_ERR_ARG;
+  // the two-segment instance (ABI 24): a second key segment, its per-row length, extra row mass
+  const bool seg2 = d.Nk2 != 0 || d.k2_len != nullptr || d.l_extra != nullptr;
+  if (d.Nk2 != 0) {
+    if (!d.K2 || !d.V2 || !dd->vs2) return VP_ERR_ARG;
+    if (dd->npad2 != (d.Nk2 + 63) / 64 * 64 || (d.k2_sn % 16) || (d.k2_sb % 16)) return VP_ERR_ARG;
+    if ((int64_t)d.Nk2 * d.k2_sn > 0x7fffffff || (int64_t)64 * dd->npad2 > 0x7fffffff) return VP_ERR_ARG;
+  } else if (d.k2_len != nullptr) {
+    return VP_ERR_ARG;
+  }
   constexpr int NW = 8;
   // VP_ATTN8_VARIANT (A/B): 1 = P by v_exp_f32 + RNE pack, 2 = P by linear mantissa interpolation (LIN),
   // 3 = the same codes packed two per v_cvt_pknorm_u16_f32 + a byte gather (LIN 2, default: 2.11-2.15 against
@@ -2823,10 +2889,15 @@ extern "C" int vp_attention_fwd_fp8_ws(const vp_attn_fp8_desc* dd, void* ws, int
                               F8S_SLOTS * 2 * F8_STAGE);
     (void)hipFuncSetAttribute((const void*)attn_fwd_fp8s<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               F8S_SLOTS * 2 * F8_STAGE);
+    (void)hipFuncSetAttribute((const void*)attn_fwd_fp8s<2, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              F8S_SLOTS * 2 * F8_STAGE);
+    (void)hipFuncSetAttribute((const void*)attn_fwd_fp8s<2, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              F8S_SLOTS * 2 * F8_STAGE);
   }
   const char* e = vp_knob(VPK_ATTN8_VARIANT);
   int variant = e != nullptr ? atoi(e) : 0;
   if (variant < 1 || variant > 5) variant = 5;
+  if (seg2 && variant != 5) return VP_ERR_UNSUPPORTED;  // the skewed kernel alone has the two-segment instance
   if (variant == 5) {  // the skewed loop (default)
     constexpr int sub = 2;
     const int nqb5 = (d.Nq + NW * 32 - 1) / (NW * 32);
@@ -2839,8 +2910,9 @@ extern "C" int vp_attention_fwd_fp8_ws(const vp_attn_fp8_desc* dd, void* ws, int
       hipError_t le = hipMemsetAsync(tickets, 0, 32, (hipStream_t)stream);
       if (le != hipSuccess) return (int)le;
       void* args5[] = {(void*)dd, (void*)&tickets};
-      le = hipLaunchKernel((const void*)attn_fwd_fp8s<sub, true>, dim3((unsigned)slots), dim3(NW * 64), args5,
-                           F8S_SLOTS * sub * F8_STAGE, (hipStream_t)stream);
+      le = hipLaunchKernel(seg2 ? (const void*)attn_fwd_fp8s<sub, true, true> : (const void*)attn_fwd_fp8s<sub, true>,
+                           dim3((unsigned)slots), dim3(NW * 64), args5, F8S_SLOTS * sub * F8_STAGE,
+                           (hipStream_t)stream);
       if (le != hipSuccess) return (int)le;
       VP_CHECK_LAUNCH();
       return VP_OK;
@@ -2848,7 +2920,8 @@ extern "C" int vp_attention_fwd_fp8_ws(const vp_attn_fp8_desc* dd, void* ws, int
     int* none = nullptr;
     void* args5[] = {(void*)dd, (void*)&none};
     const hipError_t le5 =
-        hipLaunchKernel((const void*)attn_fwd_fp8s<sub>, dim3((unsigned)grid5),
+        hipLaunchKernel(seg2 ? (const void*)attn_fwd_fp8s<sub, false, true> : (const void*)attn_fwd_fp8s<sub>,
+                        dim3((unsigned)grid5),
                         dim3(NW * 64), args5, F8S_SLOTS * sub * F8_STAGE, (hipStream_t)stream);
     if (le5 != hipSuccess) return (int)le5;
     VP_CHECK_LAUNCH();

@@ -447,18 +447,29 @@ extern "C" int vp_head_norm_rope_bf16(const void* x_in, int64_t ld_in, int64_t b
   return VP_OK;
 }
 
+extern "C" int vp_head_norm_rope_fp8_rows(const void* x_in, int64_t ld_in, int64_t bs_in, void* q_out, int64_t ld_out,
+                                          int64_t bs_out, int32_t B, int32_t Ntok, int32_t H, int32_t text_len,
+                                          const void* ln_w, const void* ln_b, float eps, const float* cos,
+                                          const float* sin, float out_mul, const uint8_t* tok_mask,
+                                          int64_t mask_bstride, float pre_scale, const int32_t* dst_rows,
+                                          void* stream) {
+  if (!x_in || !q_out || !ln_w || !ln_b || B <= 0 || Ntok <= 0 || H <= 0) return VP_ERR_ARG;
+  if (dst_rows != nullptr && x_in == q_out) return VP_ERR_ARG;  // a permuted write must not alias its input
+  if ((ld_in % 8) || (bs_in % 8) || (ld_out % 8) || (bs_out % 8)) return VP_ERR_ARG;
+  if ((cos == nullptr) != (sin == nullptr) || !(out_mul > 0.f)) return VP_ERR_ARG;
+  launch_head_norm_rope<true>((hipStream_t)stream, (const bf16*)x_in, ld_in, bs_in, q_out, ld_out, bs_out, B, Ntok, H,
+                              text_len, (const bf16*)ln_w, (const bf16*)ln_b, eps, cos, sin, tok_mask, mask_bstride,
+                              pre_scale, out_mul, dst_rows);
+  VP_CHECK_LAUNCH();
+  return VP_OK;
+}
+
 extern "C" int vp_head_norm_rope_fp8(const void* x_in, int64_t ld_in, int64_t bs_in, void* q_out, int64_t ld_out,
                                      int64_t bs_out, int32_t B, int32_t Ntok, int32_t H, int32_t text_len,
                                      const void* ln_w, const void* ln_b, float eps, const float* cos,
                                      const float* sin, float out_mul, void* stream) {
-  if (!x_in || !q_out || !ln_w || !ln_b || B <= 0 || Ntok <= 0 || H <= 0) return VP_ERR_ARG;
-  if ((ld_in % 8) || (bs_in % 8) || (ld_out % 8) || (bs_out % 8)) return VP_ERR_ARG;
-  if ((cos == nullptr) != (sin == nullptr) || !(out_mul > 0.f)) return VP_ERR_ARG;
-  launch_head_norm_rope<true>((hipStream_t)stream, (const bf16*)x_in, ld_in, bs_in, q_out, ld_out, bs_out, B, Ntok, H,
-                              text_len, (const bf16*)ln_w, (const bf16*)ln_b, eps, cos, sin, nullptr, 0, 1.f, out_mul,
-                              nullptr);
-  VP_CHECK_LAUNCH();
-  return VP_OK;
+  return vp_head_norm_rope_fp8_rows(x_in, ld_in, bs_in, q_out, ld_out, bs_out, B, Ntok, H, text_len, ln_w, ln_b, eps,
+                                    cos, sin, out_mul, nullptr, 0, 1.f, nullptr, stream);
 }
 
 extern "C" int vp_mask_scale_rows_bf16(const void* x_in, int64_t ld_in, int64_t bs_in, void* y, int64_t ld_out,

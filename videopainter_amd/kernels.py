@@ -571,12 +571,19 @@ def qk_fp8_exponent(ln_w: torch.Tensor, ln_b: torch.Tensor, mul: float = 1.0) ->
 
 
 def head_norm_rope_fp8(x_in: torch.Tensor, heads: int, text_len: int, ln_w, ln_b, eps: float, rope, out_mul: float,
-                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """LN(64) + RoPE as `head_norm_rope`, written as e4m3 (x * out_mul) into uint8 [B, N, heads*64]."""
+                       out: Optional[torch.Tensor] = None, *, tok_mask: Optional[torch.Tensor] = None,
+                       pre_scale: float = 1.0, dst_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """LN(64) + RoPE as `head_norm_rope`, written as e4m3 (x * out_mul) into uint8 [B, N, heads*64].  tok_mask /
+    pre_scale / dst_rows as in `head_norm_rope` (the masked, permuted rows of the fp8 attention's second segment): rows
+    whose dst_rows entry is negative are neither read nor written, so with dst_rows a fresh `out` keeps what the
+    allocator left in the rows nothing is written to."""
     _chk(x_in, "x_in")
     B, Ntok, _ = x_in.shape
     if out is None:
         out = torch.empty(B, Ntok, heads * 64, device=x_in.device, dtype=torch.uint8)
+    _chk(out, "out", torch.uint8)
+    if out.dim() != 3 or out.stride(-1) != 1 or tuple(out.shape) != (B, Ntok, heads * 64):
+        raise ValueError(f"out must be uint8 [{B}, {Ntok}, {heads * 64}] with a contiguous last dim")
     cos = sin = None
     if rope is not None:
         cos, sin = rope
@@ -584,9 +591,22 @@ def head_norm_rope_fp8(x_in: torch.Tensor, heads: int, text_len: int, ln_w, ln_b
         _chk(sin, "sin", torch.float32)
         if cos.shape[0] != Ntok - text_len or cos.shape[1] != 64 or not cos.is_contiguous() or not sin.is_contiguous():
             raise ValueError(f"rope tables must be fp32 [{Ntok - text_len}, 64], got {tuple(cos.shape)}")
-    N.check(N.lib().vp_head_norm_rope_fp8(_p(x_in), x_in.stride(1), x_in.stride(0), _p(out), out.stride(1),
-                                          out.stride(0), B, Ntok, heads, text_len, _p(ln_w), _p(ln_b), eps, _p(cos),
-                                          _p(sin), out_mul, _stream()), "vp_head_norm_rope_fp8")
+    if tok_mask is None and dst_rows is None:
+        N.check(N.lib().vp_head_norm_rope_fp8(_p(x_in), x_in.stride(1), x_in.stride(0), _p(out), out.stride(1),
+                                              out.stride(0), B, Ntok, heads, text_len, _p(ln_w), _p(ln_b), eps,
+                                              _p(cos), _p(sin), out_mul, _stream()), "vp_head_norm_rope_fp8")
+        return out
+    mb = 0
+    if tok_mask is not None:
+        _chk(tok_mask, "tok_mask", torch.uint8)
+        if tuple(tok_mask.shape) != (B, Ntok) or tok_mask.stride(1) != 1:
+            raise ValueError(f"tok_mask must be uint8 [{B}, {Ntok}] with contiguous rows")
+        mb = tok_mask.stride(0)
+    _chk_rows(dst_rows, B, Ntok)
+    N.check(N.lib().vp_head_norm_rope_fp8_rows(_p(x_in), x_in.stride(1), x_in.stride(0), _p(out), out.stride(1),
+                                               out.stride(0), B, Ntok, heads, text_len, _p(ln_w), _p(ln_b), eps,
+                                               _p(cos), _p(sin), out_mul, _p(tok_mask), mb, pre_scale, _p(dst_rows),
+                                               _stream()), "vp_head_norm_rope_fp8_rows")
     return out
 
 
@@ -597,30 +617,58 @@ class VPacked:
         self.vt, self.vs, self.npad, self.n = vt, vs, npad, n
 
 
-def v_pack_fp8(v: torch.Tensor, heads: int) -> VPacked:
+def v_pack_fp8(v: torch.Tensor, heads: int, lens: Optional[torch.Tensor] = None) -> VPacked:
+    """lens: optional int32 [B] (device): rows n >= lens[b] are packed as zeros and are not read (they may be
+    uninitialised memory); the 64-key tiles wholly past lens[b] are not written — pass the same tensor as the
+    attention's k2_len."""
     _chk(v, "v")
+    if v.dim() != 3 or v.stride(-1) != 1 or v.shape[-1] != heads * 64:
+        raise ValueError(f"v must be [B, N, heads*64] with a contiguous last dim, got {tuple(v.shape)}")
     B, Nk, _ = v.shape
+    if lens is not None:
+        _chk(lens, "lens", torch.int32)
+        if tuple(lens.shape) != (B,) or not lens.is_contiguous():
+            raise ValueError(f"lens must be contiguous int32 [{B}]")
     npad, sbytes = C.c_int64(), C.c_int64()
     nb = N.lib().vp_v_pack_fp8_bytes(B, heads, Nk, C.byref(npad), C.byref(sbytes))
     if nb <= 0:
         raise ValueError("bad V shape")
     vt = torch.empty(nb, device=v.device, dtype=torch.uint8)
     vs = torch.empty(sbytes.value, device=v.device, dtype=torch.uint8)
-    N.check(N.lib().vp_v_pack_fp8(_p(v), v.stride(0), v.stride(1), B, Nk, heads, _p(vt), _p(vs), _stream()),
-            "vp_v_pack_fp8")
+    N.check(N.lib().vp_v_pack_fp8_lens(_p(v), v.stride(0), v.stride(1), B, Nk, heads, _p(vt), _p(vs), _p(lens),
+                                       _stream()), "vp_v_pack_fp8_lens")
     return VPacked(vt, vs, npad.value, Nk)
 
 
 def attention_fp8(q8: torch.Tensor, k8: torch.Tensor, vp: VPacked, out: torch.Tensor, heads: int, q_exp: int,
-                  k_exp: int, out_scale: float = 1.0, accumulate: bool = False) -> torch.Tensor:
-    """q8 = e4m3(q * scale * log2 e * 2^q_exp), k8 = e4m3(k * 2^k_exp): uint8 [B, N, heads*64]; out bf16."""
-    for t, n in ((q8, "q8"), (k8, "k8")):
+                  k_exp: int, out_scale: float = 1.0, accumulate: bool = False, *,
+                  k2: Optional[torch.Tensor] = None, vp2: Optional[VPacked] = None,
+                  k2_len: Optional[torch.Tensor] = None, l_extra: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """q8 = e4m3(q * scale * log2 e * 2^q_exp), k8 = e4m3(k * 2^k_exp): uint8 [B, N, heads*64]; out bf16.
+    k2 / vp2: an optional second key segment, e4m3 with k8's factor and its own V^T pack (v_pack_fp8 with lens =
+    k2_len).  k2_len: optional int32 [B] (device): only the first min(k2_len[b], Nk2) keys of segment 2 exist for
+    batch row b.  l_extra: optional fp32 [B, heads, Nq]: log2 of extra row-sum mass per query in score units
+    (null_key_mass).  The default kernel (VP_ATTN8_VARIANT 5) alone takes them."""
+    if (k2 is None) != (vp2 is None):
+        raise ValueError("k2 and vp2 must be given together")
+    for t, n in ((q8, "q8"), (k8, "k8")) + (((k2, "k2"),) if k2 is not None else ()):
         _chk(t, n, torch.uint8)
         if t.dim() != 3 or t.stride(-1) != 1 or t.shape[-1] != heads * 64:
             raise ValueError(f"{n} must be [B, N, heads*64] uint8")
+        if t.shape[0] != q8.shape[0]:
+            raise ValueError(f"{n} batch {t.shape[0]} != q batch {q8.shape[0]}")
     _chk(out, "out")
-    if k8.shape[1] != vp.n:
-        raise ValueError("k and packed v lengths differ")
+    if out.dim() != 3 or out.stride(-1) != 1 or tuple(out.shape) != tuple(q8.shape):
+        raise ValueError(f"out must be bf16 {tuple(q8.shape)} with a contiguous last dim, got {tuple(out.shape)}")
+    if k8.shape[1] != vp.n or k8.shape[1] == 0:
+        raise ValueError("k and packed v lengths differ (or are empty)")
+    for pk, kk, n in ((vp, k8, "vp"),) + (((vp2, k2, "vp2"),) if k2 is not None else ()):
+        Bk, Nk_ = kk.shape[0], kk.shape[1]
+        if pk.n != Nk_ or pk.npad != (Nk_ + 63) // 64 * 64 or pk.vt.numel() != Bk * heads * 64 * pk.npad \
+                or pk.vs.numel() != Bk * heads * (pk.npad // 64) * 128:
+            raise ValueError(f"{n} is not the V^T pack of {Nk_} keys for batch {Bk}, {heads} heads")
+        _chk(pk.vt, n + ".vt", torch.uint8)
+        _chk(pk.vs, n + ".vs", torch.uint8)
     if not (-127 <= q_exp <= 127 and -127 <= k_exp <= 127):
         raise ValueError("scale exponents out of the E8M0 range")
     dd = N.AttnFp8Desc()
@@ -634,12 +682,32 @@ def attention_fp8(q8: torch.Tensor, k8: torch.Tensor, vp: VPacked, out: torch.Te
     d.scale, d.out_scale, d.accumulate = 1.0, out_scale, int(accumulate)
     dd.vs, dd.npad = _p(vp.vs), vp.npad
     dd.qk_scale = (127 - q_exp) | ((127 - k_exp) << 8)
+    if k2 is not None:
+        d.K2, d.k2_sb, d.k2_sn, d.Nk2 = _p(k2), k2.stride(0), k2.stride(1), k2.shape[1]
+        d.V2 = _p(vp2.vt)
+        dd.vs2, dd.npad2 = _p(vp2.vs), vp2.npad
+    if k2_len is not None:
+        if k2 is None:
+            raise ValueError("k2_len needs a second segment")
+        _chk(k2_len, "k2_len", torch.int32)
+        if tuple(k2_len.shape) != (q8.shape[0],) or not k2_len.is_contiguous():
+            raise ValueError(f"k2_len must be contiguous int32 [{q8.shape[0]}]")
+        d.k2_len = _p(k2_len)
+    if l_extra is not None:
+        _chk(l_extra, "l_extra", torch.float32)
+        if tuple(l_extra.shape) != (q8.shape[0], heads, q8.shape[1]) or not l_extra.is_contiguous():
+            raise ValueError(f"l_extra must be contiguous fp32 [{q8.shape[0]}, {heads}, {q8.shape[1]}]")
+        d.l_extra = _p(l_extra)
     L = N.lib()
     nb = L.vp_attention_fp8_workspace_bytes(C.byref(dd))
     # the persistent kernel's ticket counters (caching allocator, ordered on the launch stream)
     ws = torch.empty(nb, device=q8.device, dtype=torch.uint8) if nb > 0 else None
     ev = _t0("attention_fp8")
-    N.check(L.vp_attention_fwd_fp8_ws(C.byref(dd), _p(ws), nb, _stream()), "vp_attention_fwd_fp8_ws")
+    rc = L.vp_attention_fwd_fp8_ws(C.byref(dd), _p(ws), nb, _stream())
+    if rc == N.ERR_UNSUPPORTED and (k2 is not None or l_extra is not None):  # (nothing was launched)
+        raise ValueError("this fp8 attention kernel takes one key segment and no l_extra: only the default "
+                         "(VP_ATTN8_VARIANT unset or 5) has the two-segment form, and none takes k2_full")
+    N.check(rc, "vp_attention_fwd_fp8_ws")
     _t1("attention_fp8", ev)
     return out
 

@@ -263,12 +263,18 @@ class CogVideoXBlock(nn.Module):
             raise ValueError("fp8 output projection needs widths that are multiples of 256")
         self.out_mx = K.mx_quantize(lin.weight)
 
-    def enable_fp8_attention(self, enabled: bool = True) -> None:
+    def enable_fp8_attention(self, enabled: bool = True, resample: bool = False) -> None:
         """Run self-attention on the block-scaled fp8 MFMA (vp_attention_fwd_fp8): Q and K leave the qk-norm + RoPE
         kernel as e4m3 with one static power-of-two factor each, chosen from the LayerNorm's bound on its outputs
         (kernels.qk_fp8_exponent: nothing can saturate), V is packed to e4m3 with per-(channel, 32 keys) scales,
-        and P is rounded to e4m3 inside the kernel.  The resample processor (two K/V segments) stays bf16."""
+        and P is rounded to e4m3 inside the kernel.  The resample processor (two K/V segments) stays bf16 unless
+        `resample` opts in: then, when its null keys are summed in closed form (the video grid known, the RoPE table
+        separable), its masked keys run as the fp8 kernel's second segment (K rows through the masked fp8 norm, V
+        through a length-aware pack) and the null-key mass as its l_extra; every other form of that processor stays
+        bf16.  Accuracy at full length (inside the 5x block band) and speed against bf16: DESIGN.md §4.  enabled=False
+        clears both switches."""
         attn = self.attn1
+        attn.fp8_resample = bool(enabled and resample)
         if not enabled:
             attn.fp8_qk_exp = None
             return
@@ -609,11 +615,12 @@ class CogVideoXTransformer3DModel(ModelMixin):
             blk.enable_fp8_ffn(enabled)
         return self
 
-    def enable_fp8_attention(self, enabled: bool = True):
+    def enable_fp8_attention(self, enabled: bool = True, resample: bool = False):
         """fp8 self-attention in every block (BASELINE config 5; see CogVideoXBlock.enable_fp8_attention).  Call
-        after the weights are loaded (the Q/K factors come from the qk-norm affine)."""
+        after the weights are loaded (the Q/K factors come from the qk-norm affine).  resample: also the ID-resample
+        processor's two-segment attention (off by default: that processor then stays bf16)."""
         for blk in self.transformer_blocks:
-            blk.enable_fp8_attention(enabled)
+            blk.enable_fp8_attention(enabled, resample)
         return self
 
     def enable_fp8_qkv(self, enabled: bool = True):
@@ -628,13 +635,15 @@ class CogVideoXTransformer3DModel(ModelMixin):
             blk.enable_fp8_out(enabled)
         return self
 
-    def enable_fp8(self, ffn: bool = True, attention: bool = True, qkv: bool = True, out: bool = True):
+    def enable_fp8(self, ffn: bool = True, attention: bool = True, qkv: bool = True, out: bool = True,
+                   resample_attention: bool = False):
         """BASELINE config 5: "attn + FFN in fp8" (the QKV projection, the attention products, the attention's output
-        projection, the FeedForward)."""
+        projection, the FeedForward).  resample_attention: with `attention`, also the ID-resample processor's
+        attention (enable_fp8_attention(resample=True))."""
         self.enable_fp8_ffn(ffn)
         self.enable_fp8_qkv(qkv)
         self.enable_fp8_out(out)
-        return self.enable_fp8_attention(attention)
+        return self.enable_fp8_attention(attention, resample_attention)
 
     def _patch_channels(self):
         return self.config.in_channels
