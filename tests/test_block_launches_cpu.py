@@ -4,95 +4,24 @@ launches recorded from the commit BEFORE the block forward was written once as s
 (tests/golden/block_launches.json) — entry, every scalar argument, and shape / strides / dtype of every tensor
 argument (so "AdaLN wrote into the augmented operand" and "aux present" are part of the trace).
 
-The `videopainter_amd.kernels` entry points the block calls are replaced, INSIDE THIS TEST ONLY, by recorders that
-return their `out` argument (or an empty tensor of the documented shape); the product path has no such substitute.
+The `videopainter_amd.kernels` entry points the block calls are replaced, inside the launch-trace tests only, by the
+recorders of tests/launch_recorder.py; the product path has no such substitute.
 
 To record the fixture (against a checkout of the commit the traces are to be compared with, from its root):
     python -c "from tests.test_block_launches_cpu import write_fixture; write_fixture('block_launches.json')"
 """
-import contextlib
-import inspect
 import json
 import os
 
 import pytest
 import torch
 
+from tests.launch_recorder import _RETURNS, _describe, _empty, recording  # noqa: F401 (other tests take them here)
+
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "block_launches.json")
 B, T, NV, D, H = 2, 8, 288, 128, 2
 N = T + NV
 MODES = {"all": (True, True), "attention": (False, True), "recompute": (False, False)}  # (SAVE_ACTIVATIONS, _ATTENTION)
-
-
-# ------------------------------------------------------------------------------------------------------------------
-# the recorder
-# ------------------------------------------------------------------------------------------------------------------
-
-def _describe(v):
-    if isinstance(v, torch.Tensor):
-        return {"shape": list(v.shape), "stride": list(v.stride()), "dtype": str(v.dtype).replace("torch.", "")}
-    if isinstance(v, torch.nn.Module):
-        return {"module": type(v).__name__, "eps": getattr(v, "eps", None),
-                "params": [_describe(p) for p in v.parameters()]}
-    if isinstance(v, (list, tuple)):
-        d = [_describe(e) for e in v]
-        return {"rope": d, "grid": _describe(v.grid)} if hasattr(v, "grid") else d
-    if v is None or isinstance(v, (bool, int, float, str)):
-        return v
-    raise TypeError(f"recorder: unexpected argument {type(v)}")
-
-
-def _empty(*shape, like, dtype=torch.bfloat16):
-    return torch.empty(*shape, device=like.device, dtype=dtype)
-
-
-# what an entry returns when it is given no `out`: an empty tensor of the documented shape
-_RETURNS = {
-    "gemm": lambda a: a["out"],
-    "adaln_modulate": lambda a: a["out"] if a["out"] is not None else torch.empty_like(a["x"]),
-    "attention": lambda a: a["out"],
-    "attention_merge": lambda a: a["out"],
-    "linear_small": lambda a: a["out"] if a["out"] is not None else _empty(a["x"].shape[0], a["weight"].shape[0],
-                                                                          like=a["x"]),
-    "head_norm_rope": lambda a: a["x_out"],
-    "mask_scale_rows": lambda a: a["out"],
-    "partition_rows_index": lambda a: (_empty(*a["tok_mask"].shape, like=a["tok_mask"], dtype=torch.int32),
-                                       _empty(a["tok_mask"].shape[0], like=a["tok_mask"], dtype=torch.int32)),
-}
-
-
-class _Event:  # (the resample processor's mask plan orders its reuse with a device event: none on the CPU)
-    def record(self, stream=None):
-        pass
-
-
-@contextlib.contextmanager
-def recording():
-    """Replaces the kernel entry points with recorders; yields the list they append to.  Arguments are bound to the
-    real entry's signature with its defaults applied, so a default passed explicitly records like one left out."""
-    from videopainter_amd import kernels as K
-    log, saved = [], {}
-
-    def recorder(name, real):
-        sig = inspect.signature(real)
-
-        def rec(*args, **kw):
-            ba = sig.bind(*args, **kw)
-            ba.apply_defaults()
-            log.append({"entry": name, "args": {k: _describe(v) for k, v in ba.arguments.items()}})
-            return _RETURNS[name](ba.arguments)
-        return rec
-
-    patches = [(K, n, recorder(n, getattr(K, n))) for n in _RETURNS]
-    patches += [(torch.cuda, "Event", _Event), (torch.cuda, "current_stream", lambda device=None: None)]
-    try:
-        for obj, n, f in patches:
-            saved[(obj, n)] = getattr(obj, n)
-            setattr(obj, n, f)
-        yield log
-    finally:
-        for (obj, n), f in saved.items():
-            setattr(obj, n, f)
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -1,8 +1,8 @@
 """The launch sequence of one ID-resample block with the fp8 two-segment attention, on the CPU: the rehearsal of the
 host logic of `CogVideoXAttnProcessor2_0_resample.attend_heads` on a machine without a GPU.
 
-The recorder of tests/test_block_launches_cpu.py, extended INSIDE THIS TEST ONLY with recorders for the fp8 and
-closed-form null-key entries the path calls.  The rope carries the video grid and is CogVideoX's separable 3D table
+The recorder of tests/test_block_launches_cpu.py, extended INSIDE THIS TEST ONLY with recorders for the fp8
+entries the path calls.  The rope carries the video grid and is CogVideoX's separable 3D table
 (rebuilt from random per-axis factors), so the processor's plan sums the null keys in closed form — the one form the
 fp8 path takes.  With the switch off the block must issue today's launches (golden case e_resample_k2_full for a
 rope without a grid, and for the grid rope the same trace as a block that never heard of the switch)."""
@@ -40,13 +40,7 @@ _RETURNS_X = {
         a["x_in"].shape[0], a["x_in"].shape[1], a["heads"] * 64, like=a["x_in"], dtype=torch.uint8),
     "v_pack_fp8": lambda a: _VPacked(a["v"], a["heads"]),
     "attention_fp8": lambda a: a["out"],
-    "mask_null_segments": lambda a: (_empty(a["tok_mask"].shape[0] * a["grid"][0] * a["grid"][1], 16,
-                                            like=a["tok_mask"], dtype=torch.uint8),
-                                     _empty(a["tok_mask"].shape[0] * (a["grid"][0] + 1), like=a["tok_mask"],
-                                            dtype=torch.int32)),
-    "null_key_mass": lambda a: _empty(a["q"].shape[0], a["heads"], a["q"].shape[1], like=a["q"], dtype=torch.float32),
-    "null_key_mass_supported": lambda a: True,
-}
+}  # (the closed-form null-key entries are the shared recorder's, tests/launch_recorder.py)
 
 
 @contextlib.contextmanager
@@ -80,9 +74,8 @@ def recording_fp8():
                 ba = sig.bind(*args, **kw)
                 ba.apply_defaults()
                 ret = _RETURNS_X[name](ba.arguments)
-                if name != "null_key_mass_supported":  # (a host-side predicate, not a launch)
-                    log.append({"entry": name, "args": {k: _describe_x(v) for k, v in ba.arguments.items()}})
-                    raw.append((len(log) - 1, name, dict(ba.arguments), ret))
+                log.append({"entry": name, "args": {k: _describe_x(v) for k, v in ba.arguments.items()}})
+                raw.append((len(log) - 1, name, dict(ba.arguments), ret))
                 return ret
             return rec
         try:

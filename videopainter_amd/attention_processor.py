@@ -172,6 +172,16 @@ def _kv(attn, x: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _prev_kv(attn, prev_hidden_states, prev_clip_weight):
+    """(pk, pv, w) of the prev-clip blend: the previous window's pre-norm K / V projections [B, N, D] and the weight,
+    or (None, None, 0.0) — nothing projected — without previous states or with a weight of None or <= 0."""
+    if prev_hidden_states is None or prev_clip_weight is None or prev_clip_weight <= 0.0:
+        return None, None, 0.0
+    pkv = _kv(attn, _rows(prev_hidden_states))
+    D = pkv.shape[-1] // 2
+    return pkv[..., :D], pkv[..., D:], float(prev_clip_weight)
+
+
 def project_out(lin, o2d: torch.Tensor, out2d: torch.Tensor, **gemm_kw) -> torch.Tensor:
     """to_out.0 on [M, D] rows with any GEMM epilogue (the block's gated residual), its LoRA adapters applied
     unfused (lora.AugmentedProjection) when it carries any."""
@@ -261,54 +271,71 @@ class CogVideoXAttnProcessor2_0:
         if qkv is None:  # (the block may hand over an fp8 projection)
             qkv = _qkv(attn, x, (text_len, rope) if fused else None, keep)
         q, k, v = qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:]
+        if fp8 is None:
+            o = augmented_rows((attn.to_out[0],), B, Ntok, D, x.device)
+            lse = None
+            if keep is not None:
+                keep["o"], keep["lse"] = o, torch.empty(B, H, Ntok, device=x.device, dtype=torch.float32)
+                lse = keep["lse"]
+            return self.attend_heads(attn, q, k, v, text_len, rope, None, None, fused,
+                                     *_prev_kv(attn, prev_hidden_states, prev_clip_weight), o, lse=lse)
+        # fp8 attention (BASELINE config 5): qk-norm + RoPE written as e4m3 with the static power-of-two factors
+        # chosen by `CogVideoXBlock.enable_fp8_attention` (Q's includes scale * log2 e), V packed to e4m3 V^T with
+        # per-(d, 32 keys) scales, the block-scaled MFMA kernel
+        q_exp, k_exp = fp8
         nq, nk = attn.norm_q, attn.norm_k
-        if fp8 is not None:
-            # fp8 attention (BASELINE config 5): qk-norm + RoPE written as e4m3 with the static power-of-two factors
-            # chosen by `CogVideoXBlock.enable_fp8_attention` (Q's includes scale * log2 e), V packed to e4m3 V^T with
-            # per-(d, 32 keys) scales, the block-scaled MFMA kernel
-            q_exp, k_exp = fp8
 
-            def operands(k_, v_):
-                return (K.head_norm_rope_fp8(k_, H, text_len, nk.weight, nk.bias, nk.eps, rope, 2.0 ** k_exp),
-                        K.v_pack_fp8(v_, H))
+        def operands(k_, v_):
+            return (K.head_norm_rope_fp8(k_, H, text_len, nk.weight, nk.bias, nk.eps, rope, 2.0 ** k_exp),
+                    K.v_pack_fp8(v_, H))
 
-            def attention(k_, v_, **kw):
-                K.attention_fp8(q8, k_, v_, o, H, q_exp, k_exp, **kw)
-            q8 = K.head_norm_rope_fp8(q, H, text_len, nq.weight, nq.bias, nq.eps, rope,
-                                      attn.scale * K.LOG2E * 2.0 ** q_exp)
-            own = operands(k, v)
-        else:
-            if not fused:
-                K.head_norm_rope(q, q, H, text_len, nq.weight, nq.bias, nq.eps, rope)
-                K.head_norm_rope(k, k, H, text_len, nk.weight, nk.bias, nk.eps, rope)
-
-            def operands(k_, v_):
-                return K.head_norm_rope(k_, k_, H, text_len, nk.weight, nk.bias, nk.eps, rope), v_
-
-            def attention(k_, v_, **kw):
-                K.attention(q, k_, v_, o, H, scale=attn.scale, bounded_scores=bs, **kw)
-            own, bs = (k, v), bounded_scores(attn)
+        def attention(k_, v_, **kw):
+            K.attention_fp8(q8, k_, v_, o, H, q_exp, k_exp, **kw)
+        q8 = K.head_norm_rope_fp8(q, H, text_len, nq.weight, nq.bias, nq.eps, rope,
+                                  attn.scale * K.LOG2E * 2.0 ** q_exp)
+        own = operands(k, v)
         o = augmented_rows((attn.to_out[0],), B, Ntok, D, x.device)
-        alone = {}
-        if keep is not None:
-            keep["o"], keep["lse"] = o, torch.empty(B, H, Ntok, device=x.device, dtype=torch.float32)
-            alone["lse"] = keep["lse"]
-        self._blend(attn, own, prev_hidden_states, prev_clip_weight, operands, attention, **alone)
+        self._blend(own, *_prev_kv(attn, prev_hidden_states, prev_clip_weight), operands, attention)
+        return o
+
+    def head_plan(self, attn, text_len: int, rope, prev: bool, resample_mask=None, prev_resample_mask=None):
+        """(m, plan, fused) of an `attend_heads` call whose caller projects q / k / v itself (the Ulysses split): this
+        processor reads no token mask and plans nothing; q / k leave the QKV GEMM normed + rotated (`fused`) where the
+        norms fit its epilogue.  prev: the call blends the previous window in."""
+        return None, None, _fusable_norms(attn)
+
+    def attend_heads(self, attn, q, k, v, text_len: int, rope, m=None, plan=None, fused: bool = True, pk=None,
+                     pv=None, w: float = 0.0, o=None, lse=None) -> torch.Tensor:
+        """The processor's bf16 attention on [B, N, h*64] views of every head (or of one head group: the Ulysses
+        split, videopainter_amd/ulysses.py; q may then carry the padding rows of the last shard past k's N rows) —
+        q / k normed + rotated already when `fused`, pre-norm otherwise; pk / pv: the previous window's pre-norm K / V
+        projections (prev-clip blend with weight w), or None.  m / plan: the resample processor's (unused here).
+        lse: the unblended call's softmax statistics."""
+        H = k.shape[-1] // 64
+        nq, nk, bs = attn.norm_q, attn.norm_k, bounded_scores(attn)
+        if not fused:
+            qn = q[:, :k.shape[1]]  # (the RoPE table ends with the real rows; no key attends a padding query)
+            K.head_norm_rope(qn, qn, H, text_len, nq.weight, nq.bias, nq.eps, rope)
+            K.head_norm_rope(k, k, H, text_len, nk.weight, nk.bias, nk.eps, rope)
+
+        def operands(k_, v_):
+            return K.head_norm_rope(k_, k_, H, text_len, nk.weight, nk.bias, nk.eps, rope), v_
+
+        def attention(k_, v_, **kw):
+            K.attention(q, k_, v_, o, H, scale=attn.scale, bounded_scores=bs, **kw)
+        self._blend((k, v), pk, pv, w, operands, attention, **({} if lse is None else {"lse": lse}))
         return o
 
     @staticmethod
-    def _blend(attn, own, prev_hidden_states, prev_clip_weight, operands, attention, **alone) -> None:
-        """`attention(k, v, **kw)` over this window's keys `own`, or — with the previous window's states and a
-        weight w > 0 — the prev-clip blend (1 - w) x that + w x the attention over the previous window's K / V
-        (projected in bf16, then `operands(pk, pv)`): two calls into one output.  alone: the unblended call's lse."""
-        if prev_hidden_states is None or prev_clip_weight is None or prev_clip_weight <= 0.0:
+    def _blend(own, pk, pv, w: float, operands, attention, **alone) -> None:
+        """`attention(k, v, **kw)` over this window's keys `own`, or — with the previous window's K / V projections
+        pk / pv (`_prev_kv`) — the prev-clip blend (1 - w) x that + w x the attention over `operands(pk, pv)`: two
+        calls into one output.  alone: the unblended call's lse."""
+        if pk is None:
             attention(*own, **alone)
             return
-        pkv = _kv(attn, _rows(prev_hidden_states))
-        D = pkv.shape[-1] // 2
-        prev = operands(pkv[..., :D], pkv[..., D:])
-        del pkv
-        w = float(prev_clip_weight)
+        prev = operands(pk, pv)
+        del pk, pv
         attention(*own, out_scale=1.0 - w)
         attention(*prev, out_scale=w, accumulate=True)
 
@@ -397,24 +424,27 @@ class CogVideoXAttnProcessor2_0_resample(CogVideoXAttnProcessor2_0):
         B, Ntok, D = x.shape
         rope = _rope_dev(image_rotary_emb, x.device)
         prev = prev_hidden_states is not None and prev_clip_weight is not None and prev_clip_weight > 0.0
-        if not prev and resample_mask is None:
-            raise ValueError("the resample processor needs resample_mask (id_pool_resample needs masks)")
-        m = _u8(prev_resample_mask if prev else resample_mask)
-        plan = self.plan(attn, m, text_len, rope)
+        m, plan, fused = self.head_plan(attn, text_len, rope, prev, resample_mask, prev_resample_mask)
         fp8 = self.fp8_exponents(attn, plan)
-        # with the null keys in closed form segment 2 holds masked rows only, and those of window 0 are rows of the
-        # normed + rotated K itself: q / k then leave the QKV GEMM through the fused norm + RoPE epilogue
-        # (the fp8 form quantises from the pre-norm q / k: no fused epilogue there)
-        fused = plan[3] is not None and qkv is None and fp8 is None and _fusable_norms(attn)
-        if qkv is None:  # (the block may hand over an fp8 projection)
+        # (the block may hand over an fp8 projection; the fp8 form quantises from the pre-norm q / k: no fused
+        # epilogue in either case)
+        fused = fused and qkv is None and fp8 is None
+        if qkv is None:
             qkv = _qkv(attn, x, (text_len, rope) if fused else None)
-        pk = pv = None
-        if prev:
-            pkv = _kv(attn, _rows(prev_hidden_states))
-            pk, pv = pkv[..., :D], pkv[..., D:]
+        pk, pv, w = _prev_kv(attn, prev_hidden_states, prev_clip_weight)
         o = augmented_rows((attn.to_out[0],), B, Ntok, D, x.device)
         return self.attend_heads(attn, qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:], text_len, rope, m, plan,
-                                 fused, pk, pv, float(prev_clip_weight) if prev else 0.0, o, fp8=fp8)
+                                 fused, pk, pv, w, o, fp8=fp8)
+
+    def head_plan(self, attn, text_len: int, rope, prev: bool, resample_mask=None, prev_resample_mask=None):
+        """(m, plan, fused): the token mask of the call (the previous window's when it blends that window in) as
+        uint8, its `plan`, and whether q / k leave the QKV GEMM normed + rotated — with the null keys in closed form
+        segment 2 holds masked rows only, and those of window 0 are rows of the normed + rotated K itself."""
+        m = _u8(prev_resample_mask if prev else resample_mask)
+        if m is None:
+            raise ValueError("the resample processor needs resample_mask (id_pool_resample needs masks)")
+        plan = self.plan(attn, m, text_len, rope)
+        return m, plan, plan[3] is not None and _fusable_norms(attn)
 
     @staticmethod
     def fp8_exponents(attn, plan):
@@ -451,8 +481,10 @@ class CogVideoXAttnProcessor2_0_resample(CogVideoXAttnProcessor2_0):
         videopainter_amd/ulysses.py) — q / k normed + rotated already when `fused`, pre-norm otherwise; pk / pv: the
         previous window's pre-norm K / V projections (prev-clip blend with weight w), or None.  fp8: `fp8_exponents`
         (needs pre-norm q / k and the closed-form plan)."""
-        B, Ntok, D = q.shape
+        B, Ntok, D = k.shape
         H = D // 64
+        # (the Ulysses split's padded last shard: q / o rows past the N the mask covers are padding, left alone)
+        q, o = q[:, :Ntok], (o[:, :Ntok] if o is not None else None)
         dst, cnt, segments, axes = plan
         grid = getattr(rope, "grid", None)
         if fp8 is not None:

@@ -510,18 +510,9 @@ def block_apply(block, x: torch.Tensor, T: int, temb: torch.Tensor, rope, inject
 class _HeadFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, dims, x, emb):
-        B, F, H, W, T = dims
-        cfg = model.config
-        p = cfg.patch_size
-        D = x.shape[-1]
-        Nv = x.shape[1] - T
-        mod = K.linear_small(emb, model.norm_out.linear.weight, model.norm_out.linear.bias, act_in=K.ACT_SILU)
-        y = K.final_norm(x, T, model.norm_final.weight, model.norm_final.bias, model.norm_out.norm.weight,
-                         model.norm_out.norm.bias, model.norm_out.norm.eps, mod)
-        proj = K.linear(y.view(B * Nv, D), model.proj_out.weight, model.proj_out.bias)
         ctx.model, ctx.dims = model, dims
         ctx.save_for_backward(x, emb)
-        return K.unpatchify(proj, B, F, cfg.out_channels, H, W, p)
+        return model._head(x, emb, dims[4], dims[:4])  # (the inference forward's head)
 
     @staticmethod
     def backward(ctx, dout):

@@ -135,16 +135,9 @@ class CogvideoXBranchModel(CogVideoXTransformer3DModel):
                                       "attention_processor.py:2349-2358) is inference-only")
         if timestep_cond is not None:
             raise ValueError("timestep_cond requires a cond_proj, which CogVideoX's TimestepEmbedding does not have")
-        dev = self.proj_out.weight.device
-        B, F, C, H, W = hidden_states.shape
-        cfg = self.config
-        hs = _bf(hidden_states.to(dev))
-        bc = _bf(branch_cond.to(dev))
-        enc = _bf(encoder_hidden_states.to(dev))
+        enc, hs, bc, emb, rope = self._inputs(hidden_states, encoder_hidden_states, branch_cond, timestep,
+                                              image_rotary_emb)
         T = enc.shape[1]
-        D = cfg.num_attention_heads * cfg.attention_head_dim
-        emb = self._time_embed(timestep, B, dev)
-        rope = _rope_dev(image_rotary_emb, dev, grid=(F, H // cfg.patch_size, W // cfg.patch_size))
         scale = float(conditioning_scale)
         if train:
             # the training step's branch call (train_cogvideox_inpainting_i2v_video.py:1856-1865): differentiable
@@ -157,24 +150,54 @@ class CogvideoXBranchModel(CogVideoXTransformer3DModel):
                 outs.append(AG.row_linear_apply(x, lin, scale)[:, T:])
             outs = None if len(outs) == 0 else outs
             return (outs,) if not return_dict else CogvideoxBranchOutput(branch_block_samples=outs)
-        x = self.patch_embed.embed(enc, hs, bc)
-        if wo_text:  # the video rows alone (one copy per forward); the blocks see no text
-            x, T = x[:, T:].contiguous(), 0
-        Ntok = x.shape[1]
-        samples = []
-        mods = self.batched_modulations(emb)
-        for i, block in enumerate(self.transformer_blocks):
-            x = block.forward_joint(x, T, emb, rope, mod1=mods[2 * i] if mods is not None else None,
-                                    mod2=mods[2 * i + 1] if mods is not None else None,
-                                    cfg_shared_video=bool(cfg_shared_video) and i == 0)
-            samples.append(x)
-        outs = []
-        for s, lin in zip(samples, self.branch_blocks):
-            o = torch.empty(B, Ntok, D, device=dev, dtype=BF16)
-            epi = NAT.EPI_BIAS if scale == 1.0 else NAT.EPI_BIAS_SCALE
-            K.gemm(s.view(B * Ntok, D), [lin.weight], [lin.bias], o.view(B * Ntok, D), epilogue=epi, alpha=scale)
-            outs.append(o[:, T:])
+        outs = self._forward_infer(enc, hs, bc, emb, rope, scale, bool(wo_text), cfg_shared_video)
         outs = None if len(outs) == 0 else outs
         if not return_dict:
             return (outs,)
         return CogvideoxBranchOutput(branch_block_samples=outs)
+
+    def _inputs(self, hidden_states, encoder_hidden_states, branch_cond, timestep, image_rotary_emb):
+        """(enc, hs, bc, emb, rope): a forward's inputs as bf16 on the device, the time embedding, the RoPE tables."""
+        dev = self.proj_out.weight.device
+        B, F, C, H, W = hidden_states.shape
+        p = self.config.patch_size
+        hs, bc, enc = (_bf(t.to(dev)) for t in (hidden_states, branch_cond, encoder_hidden_states))
+        return (enc, hs, bc, self._time_embed(timestep, B, dev),
+                _rope_dev(image_rotary_emb, dev, grid=(F, H // p, W // p)))
+
+    def _forward_infer(self, enc, hs, bc, emb, rope, scale: float, wo_text: bool = False, cfg_shared_video=False,
+                       split=None) -> List[torch.Tensor]:
+        """The inference forward after the time embedding, written once -> the samples.  split: one rank's context of
+        the Ulysses head-parallel split, as in CogVideoXTransformer3DModel._forward_infer: the forward runs on the
+        rank's rows and returns the samples' video rows of that shard [B, nv, D].  What differs under the split, each
+        marked `split is None` below: no batched modulations, and each output linear runs right after its block (the
+        single-GPU forward runs them after all blocks)."""
+        x = self.patch_embed.embed(enc, hs, bc)
+        T = enc.shape[1]
+        if wo_text:  # the video rows alone (one copy per forward); the blocks see no text
+            x, T = x[:, T:].contiguous(), 0
+        attend = None
+        if split is not None:
+            x = split.shard(x, T)  # (the whole buffer is freed here)
+            split.rope_full = rope
+            rope, T, attend = split.sh.rope(rope), split.sh.tl, split.attend
+        outs = []
+        mods = self.batched_modulations(emb) if split is None else None
+        for i, (block, lin) in enumerate(zip(self.transformer_blocks, self.branch_blocks)):
+            x = block.forward_joint(x, T, emb, rope, attend=attend, mod1=mods[2 * i] if mods is not None else None,
+                                    mod2=mods[2 * i + 1] if mods is not None else None,
+                                    cfg_shared_video=bool(cfg_shared_video) and i == 0)
+            outs.append(x if split is None else self._sample_out(lin, x, T, scale))
+        if split is None:
+            outs = [self._sample_out(lin, s, T, scale) for s, lin in zip(outs, self.branch_blocks)]
+        return outs
+
+    @staticmethod
+    def _sample_out(lin, x: torch.Tensor, text_len: int, scale: float) -> torch.Tensor:
+        """A block's zero-init output linear over every row of x, x conditioning_scale in the epilogue -> the video
+        rows (a view of the [B, N, D] result)."""
+        B, Ntok, D = x.shape
+        o = torch.empty(B, Ntok, D, device=x.device, dtype=BF16)
+        epi = NAT.EPI_BIAS if scale == 1.0 else NAT.EPI_BIAS_SCALE
+        K.gemm(x.view(B * Ntok, D), [lin.weight], [lin.bias], o.view(B * Ntok, D), epilogue=epi, alpha=scale)
+        return o[:, text_len:]

@@ -19,6 +19,11 @@ The block's forward is written once, as five stages (`CogVideoXBlock._attn_input
 `_ff_front`, `_ff_back`): `forward_joint` composes them, a training forward is the same call with a `keep` dict the
 stages fill for the backward, and the backward's recompute (autograd._block_front) runs the same stages.
 
+A model's inference forward is written once too (`_forward_infer`, the head `_head`): `forward` parses the call and
+shapes the return; the Ulysses head-parallel split (ulysses.py) runs the same body on a rank's row shard by passing a
+split context — a handful of `split is not None` lines shard x, cut the row-local operands at the shard's first video
+row and gather the head's rows; the training forward's head (autograd._HeadFn) is `_head` as well.
+
 With `return_hidden_states=True` every block writes its output into a fresh buffer that IS the returned
 `hidden_states_list[i]` (no copies).
 """
@@ -443,8 +448,9 @@ class CogVideoXBlock(nn.Module):
         launch (batched_modulations); absent, the block computes its own.  cfg_shared_video: the caller's promise that
         the two batch rows of x hold the same video rows (the CFG halves entering the model's first block) — the
         block then computes their shared work once (_attend_cfg_shared) where it runs the plain bf16 path.
-        attend: optional replacement of the processor's attention, `attend(attn, xn, text_len, rope) -> o`
-        [B, N, D] (the Ulysses head-parallel split, videopainter_amd/ulysses.py).
+        attend: optional replacement of the processor's attention, `attend(attn, xn, text_len, rope, pn,
+        prev_clip_weight, resample_mask, prev_resample_mask) -> o` [B, N, D] (the Ulysses head-parallel split,
+        ulysses._Ctx.attend: x and rope are then a rank's rows, the masks the whole ones).
         keep: {"level": "attention" | "all", "train": bool}, a training forward's dict that the stages fill for its
         backward (autograd._BlockFn) without changing a launch.  "attention": the attention output "o" and its softmax
         statistics "lse" (where the attention is the single-segment bf16 one).  "all": also "mod1", "mod2", "qkv",
@@ -769,11 +775,41 @@ class CogVideoXTransformer3DModel(ModelMixin):
                                        id_pool_resample_learnable, timestep_cond, return_dict)
         if timestep_cond is not None:
             raise ValueError("timestep_cond requires a cond_proj, which CogVideoX's TimestepEmbedding does not have")
-        attention_kwargs = dict(attention_kwargs) if attention_kwargs is not None else None
         # LoRA scale per call, default 1.0 (reference :490-499): the folded adapters are re-folded when it changes
         self._call_lora_scale(attention_kwargs)
-        if attention_kwargs is not None:
-            attention_kwargs.pop("scale", None)
+        prev = (None, None, None)
+        if attention_kwargs and "prev_hidden_states" in attention_kwargs:
+            prev = (attention_kwargs["prev_hidden_states"], attention_kwargs.get("prev_clip_weight"),
+                    attention_kwargs.get("prev_resample_mask"))
+        output, hidden_states_list, resample_mask = self._forward_infer(
+            hidden_states, encoder_hidden_states, timestep, image_rotary_emb, prev, branch_block_samples,
+            branch_block_masks, add_first, self_guidance_hidden_states, self_guidance_masks, return_hidden_states,
+            return_resample_mask, id_pool_resample_learnable, cfg_shared_video)
+        if not return_dict:
+            if return_hidden_states:
+                if return_resample_mask:
+                    return (output, hidden_states_list, resample_mask)
+                return (output, hidden_states_list)
+            return (output,)
+        return Transformer2DModelOutput(sample=output)
+
+    def _forward_infer(self, hidden_states, encoder_hidden_states, timestep, image_rotary_emb=None,
+                       prev=(None, None, None), branch_block_samples=None, branch_block_masks=None, add_first=False,
+                       self_guidance_hidden_states=None, self_guidance_masks=None, return_hidden_states=False,
+                       return_resample_mask=False, id_pool_resample_learnable=False, cfg_shared_video=False,
+                       split=None):
+        """The inference forward, written once -> (output, hidden_states_list, resample_mask).  prev: (states, weight,
+        resample mask) of the any-length pipeline's previous window (anyl.py:962-988), the states one tensor or
+        {layer: tensor}.
+
+        split: one rank's context of the Ulysses head-parallel split (ulysses._Ctx: the shard geometry `sh`, the
+        `attend` hook, `gather_rows`).  The forward then runs on the rank's rows of the joint buffer: the row-local
+        operands (RoPE table, injection mask; branch_block_samples and prev states are the rank's own) are cut at the
+        shard's first video row, the text length is the shard's, the attention goes through the hook — which keeps the
+        whole RoPE table and gets the whole masks — and the head gathers every rank's proj_out rows, so each rank
+        returns the whole prediction (and its shard's hidden states).  What the split does not do, each marked
+        `split is None` below: the batched modulations, the ping-pong output buffers and the bf16 / contiguous copy of
+        the branch samples; the callers in ulysses.py pass no self-guidance and no cfg_shared_video."""
         dev = self.proj_out.weight.device
         B, F, C, H, W = hidden_states.shape
         cfg = self.config
@@ -781,12 +817,11 @@ class CogVideoXTransformer3DModel(ModelMixin):
         hs = _bf(hidden_states.to(dev))
         enc = _bf(encoder_hidden_states.to(dev))
         T = enc.shape[1]
-        Nv = F * (H // p) * (W // p)
-        Ntok = T + Nv
-        D = cfg.num_attention_heads * cfg.attention_head_dim
 
         emb = self._time_embed(timestep, B, dev)
         x = self.patch_embed.embed(enc, hs)
+        if split is not None:
+            x = split.shard(x, T)  # (the whole buffer is freed here)
         if self_guidance_hidden_states is not None and self_guidance_masks is None and branch_block_masks is None:
             # the reference reads an unbound `masks` here; we fail explicitly
             raise ValueError("self_guidance_hidden_states need self_guidance_masks or branch_block_masks")
@@ -796,29 +831,29 @@ class CogVideoXTransformer3DModel(ModelMixin):
             self_guidance_masks if self_guidance_masks is not None else branch_block_masks,
             id_pool_resample_learnable or return_resample_mask, T)
         rope = _rope_dev(image_rotary_emb, dev, grid=(F, H // p, W // p))
+        tl, attend = T, None
+        if split is not None:
+            split.rope_full = rope
+            rope, tl, attend = split.sh.rope(rope), split.sh.tl, split.attend
+            if tok_mask is not None:
+                tok_mask = split.sh.video_rows(tok_mask).contiguous()
 
-        prev_states = None
-        prev_w = None
-        prev_mask = None
-        if attention_kwargs and "prev_hidden_states" in attention_kwargs:
-            prev_states = attention_kwargs["prev_hidden_states"]
-            prev_w = attention_kwargs.get("prev_clip_weight")
-            prev_mask = _u8(attention_kwargs.get("prev_resample_mask"))
-
+        prev_states, prev_w, prev_mask = prev[0], prev[1], _u8(prev[2])
         bs = None
         if branch_block_samples is not None:
-            bs = [_bf(s.to(dev)) for s in branch_block_samples]
+            bs = [_bf(s.to(dev)) for s in branch_block_samples] if split is None else list(branch_block_samples)
         hidden_states_list: List[torch.Tensor] = []
         ping = None
-        mods = self.batched_modulations(emb)
+        mods = self.batched_modulations(emb) if split is None else None
         for i, block in enumerate(self.transformer_blocks):
             inj = self._branch_sample(bs, i, add_first)
             pj = None
             if prev_states is not None:
                 pj = prev_states.get(i) if isinstance(prev_states, dict) else prev_states
-            if return_hidden_states:
-                out = torch.empty(B, Ntok, D, device=dev, dtype=BF16)
-            else:
+            out = None  # (split: the block allocates its own output)
+            if split is None and return_hidden_states:
+                out = torch.empty_like(x)
+            elif split is None:
                 out = ping if (ping is not None and ping.data_ptr() != x.data_ptr()) else torch.empty_like(x)
                 ping = x
             guide = None
@@ -826,34 +861,35 @@ class CogVideoXTransformer3DModel(ModelMixin):
                 guide = _bf(self_guidance_hidden_states[i].to(dev))
             # (self-guidance replaces the unmasked video rows BEFORE the injection, reference :593-608: the block then
             # runs without its fused injection, and vp_guide_rows_bf16 applies both)
-            x = block.forward_joint(x, T, emb, rope, rm_u8, pj, prev_w if pj is not None else None,
+            x = block.forward_joint(x, tl, emb, rope, rm_u8, pj, prev_w if pj is not None else None,
                                     prev_mask if pj is not None else None, inj if guide is None else None,
                                     tok_mask if (inj is not None and branch_block_masks is not None) else None, out,
-                                    mod1=mods[2 * i] if mods is not None else None,
+                                    attend, mod1=mods[2 * i] if mods is not None else None,
                                     mod2=mods[2 * i + 1] if mods is not None else None,
                                     cfg_shared_video=bool(cfg_shared_video) and i == 0)
             if guide is not None:
-                xv = x[:, T:]
+                xv = x[:, tl:]
                 K.guide_rows(xv, guide.expand_as(xv), tok_mask, inj, inject_all=branch_block_masks is None)
             if return_hidden_states:
                 hidden_states_list.append(x)
+        output = self._head(x, emb, tl, (B, F, H, W), split.gather_rows if split is not None else None)
+        return output, hidden_states_list, resample_mask
 
-        mod = K.linear_small(emb, self.norm_out.linear.weight, self.norm_out.linear.bias, act_in=K.ACT_SILU)
+    def _head(self, x: torch.Tensor, emb: torch.Tensor, text_len: int, dims, gather=None) -> torch.Tensor:
+        """norm_final + norm_out (AdaLN on silu(emb): shift | scale) on the video rows of x, proj_out, then the
+        patches back to [B, F, C, H, W] (reference :613-637).  gather: the split's exchange from this rank's proj_out
+        rows [B * nv, pc] to every video row [B * Nv, pc]."""
+        B, F, H, W = dims
+        cfg = self.config
         if not cfg.use_rotary_positional_embeddings:
             raise NotImplementedError("CogVideoX-2B head (norm_final on video rows only) is not on the 5B-I2V path")
-        y = K.final_norm(x, T, self.norm_final.weight, self.norm_final.bias, self.norm_out.norm.weight,
+        mod = K.linear_small(emb, self.norm_out.linear.weight, self.norm_out.linear.bias, act_in=K.ACT_SILU)
+        y = K.final_norm(x, text_len, self.norm_final.weight, self.norm_final.bias, self.norm_out.norm.weight,
                          self.norm_out.norm.bias, self.norm_out.norm.eps, mod)
-        proj = K.linear(y.view(B * Nv, D), self.proj_out.weight, self.proj_out.bias)
-        output = K.unpatchify(proj, B, F, cfg.out_channels, H, W, p)
-
-        if not return_dict:
-            if return_hidden_states:
-                if return_resample_mask:
-                    return (output, hidden_states_list, resample_mask)
-                return (output, hidden_states_list)
-            return (output,)
-        return Transformer2DModelOutput(sample=output)
-
+        proj = K.linear(y.view(-1, y.shape[-1]), self.proj_out.weight, self.proj_out.bias)
+        if gather is not None:
+            proj = gather(proj, B)
+        return K.unpatchify(proj, B, F, cfg.out_channels, H, W, cfg.patch_size)
 
     def _forward_train(self, hidden_states, encoder_hidden_states, timestep, image_rotary_emb, attention_kwargs,
                        branch_block_samples, branch_block_masks, add_first, self_guidance_hidden_states,

@@ -20,6 +20,13 @@ Communicators: `DistComm` (torch.distributed; backend "nccl" = RCCL over xGMI) a
 ranks as P threads of one process on one GPU (same launches in the same order per rank; the exchanges are local
 copies) — the single-GPU rehearsal the GPU tests use to check the split against the unsplit forward.
 
+This module holds the communicators, the shard geometry, the two layout exchanges, the split context (`_Ctx`: the
+blocks' `attend` hook and the head's row gather) and the harness views.  It holds no model forward: `branch_forward` /
+`transformer_forward` call the models' own inference forwards (`_forward_infer(split=_Ctx(...))`, transformer.py /
+branch.py), which shard x, slice the row-local operands and name there what the split leaves out (batched
+modulations, ping-pong buffers, self-guidance, cfg_shared_video); the hook's attention is the processor's
+`attend_heads` on the rank's head group.
+
 Scope: the bf16 path with both processors of the any-length pipeline — the standard one (config 2, the headline;
 with the previous-clip blend) and the ID-resample one (config 4: window 0's masked second K / V segment, later
 windows' masked previous-window K / V): the projections stay row-local, the masks and the RoPE table of the
@@ -31,15 +38,11 @@ import threading
 from dataclasses import dataclass
 from typing import List, Optional
 
-import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import _native as NAT
-from . import kernels as K
-from .attention_processor import (CogVideoXAttnProcessor2_0, CogVideoXAttnProcessor2_0_resample, _fusable_norms,
-                                  _kv, _qkv, _rope_dev, _u8, bounded_scores)
-from .transformer import BF16, Transformer2DModelOutput, _bf
+from .attention_processor import CogVideoXAttnProcessor2_0, CogVideoXAttnProcessor2_0_resample, _kv, _qkv
+from .transformer import BF16, Transformer2DModelOutput
 
 # ------------------------------------------------------------------------------------------------------------------
 # communicators
@@ -163,70 +166,58 @@ class Shard:
 
 
 class _Ctx:
-    """One rank's attention of the split forward.  rope_full: the whole RoPE table (with its grid) for the head-group
-    rows; mask / prev_mask: the resample processor's full token masks [B, N] (this window's, the previous one's)."""
+    """One rank's split context of a model forward (`_forward_infer(split=...)`): the shard geometry `sh` (fixed by
+    `shard` from the embedded joint buffer), the head-parallel `attend` hook of the blocks, and the head's
+    `gather_rows`.  rope_full: the whole RoPE table (with its grid) for the head-group rows, set by the forward."""
 
-    def __init__(self, comm, rank: int, shard: Shard, rope_full=None, mask=None, prev_mask=None):
-        self.comm, self.rank, self.sh = comm, rank, shard
-        self.rope_full, self.mask, self.prev_mask = rope_full, mask, prev_mask
+    def __init__(self, comm, rank: int):
+        self.comm, self.rank = comm, rank
+        self.sh = self.rope_full = None
+
+    def shard(self, x: torch.Tensor, T: int) -> torch.Tensor:
+        """This rank's rows of the whole joint buffer x [B, N, D] with T text rows (zero-padded)."""
+        self.sh = Shard(x.shape[1], T, self.comm.P, self.rank)
+        return self.sh.rows(x)
 
     def attend(self, attn, xn: torch.Tensor, text_len: int, rope, pn: Optional[torch.Tensor] = None,
                prev_clip_weight=None, resample_mask=None, prev_resample_mask=None) -> torch.Tensor:
-        """Head-parallel attention of the shard's rows with the semantics of the block's processor:
-        CogVideoXAttnProcessor2_0 (with the previous-clip blend when pn, the previous window's normed shard rows,
-        is given) or CogVideoXAttnProcessor2_0_resample (window 0's masked second segment, or the previous window's
-        masked K / V).  The row-local projections run on the shard; the masks and the RoPE table of the head-group
-        attention are the full ones of the context (resample_mask / prev_resample_mask, the shard-level arguments
-        of forward_joint, are not used)."""
+        """Head-parallel attention of the shard's rows with the semantics of the block's processor (its
+        `attend_heads` on this rank's head group): the row-local projections run on the shard — text_len / rope are
+        the shard's —, q | k | v (and the previous window's k | v, projected from pn, its normed shard rows) are
+        exchanged to every row of the head group, and the attention there takes the whole RoPE table and the whole
+        token masks resample_mask / prev_resample_mask [B, N]."""
         B, n, D = xn.shape
         P = self.comm.P
-        H = attn.heads
-        if H % P:
-            raise ValueError(f"{H} heads do not split {P} ways")
-        Hp = H // P
-        Dp = Hp * 64
+        if attn.heads % P:
+            raise ValueError(f"{attn.heads} heads do not split {P} ways")
+        Dp = D // P
         N, T = self.sh.N, self.sh.T
         prev = pn is not None and prev_clip_weight is not None and prev_clip_weight > 0.0
-        resample = isinstance(attn.processor, CogVideoXAttnProcessor2_0_resample)
-        m = plan = None
-        if resample:
-            m = _u8(self.prev_mask if prev else self.mask)
-            if m is None:
-                raise ValueError("the resample processor needs resample_mask (id_pool_resample needs masks)")
-            plan = attn.processor.plan(attn, m, T, self.rope_full)
-            fused = plan[3] is not None and _fusable_norms(attn)
-        else:
-            fused = _fusable_norms(attn)
-        qkv = _qkv(attn, xn, (text_len, rope) if fused else None)
-        if not fused and not resample:
-            K.head_norm_rope(qkv[..., :D], qkv[..., :D], H, text_len, attn.norm_q.weight, attn.norm_q.bias,
-                             attn.norm_q.eps, rope)
-            K.head_norm_rope(qkv[..., D:2 * D], qkv[..., D:2 * D], H, text_len, attn.norm_k.weight, attn.norm_k.bias,
-                             attn.norm_k.eps, rope)
-        full = qkv_to_heads(self.comm, self.rank, qkv)
-        del qkv
+        m, plan, fused = attn.processor.head_plan(attn, T, self.rope_full, prev, resample_mask, prev_resample_mask)
+        full = qkv_to_heads(self.comm, self.rank, _qkv(attn, xn, (text_len, rope) if fused else None))
         pk = pv = None
         if prev:  # the previous window's K / V of this shard's rows (pre-norm) -> every row of the head group
             pkv = qkv_to_heads(self.comm, self.rank, _kv(attn, pn), parts=2)
             pk, pv = pkv[:, :N, :Dp], pkv[:, :N, Dp:]
         o_full = torch.zeros(B, P * n, Dp, device=xn.device, dtype=BF16)
-        if resample:
-            q, k, v = full[:, :N, :Dp], full[:, :N, Dp:2 * Dp], full[:, :N, 2 * Dp:]
-            attn.processor.attend_heads(attn, q, k, v, T, self.rope_full, m, plan, fused, pk, pv,
-                                        float(prev_clip_weight) if prev else 0.0, o_full[:, :N])
-        else:
-            q, k, v = full[..., :Dp], full[:, :N, Dp:2 * Dp], full[:, :N, 2 * Dp:]
-            bs = bounded_scores(attn)
-            if prev:  # (attention_processor.py:2156-2189: (1 - w) self + w previous clip, one blended output)
-                w = float(prev_clip_weight)
-                K.head_norm_rope(pk, pk, Hp, T, attn.norm_k.weight, attn.norm_k.bias, attn.norm_k.eps,
-                                 self.rope_full)
-                K.attention(q, k, v, o_full, Hp, scale=attn.scale, out_scale=1.0 - w, bounded_scores=bs)
-                K.attention(q, pk, pv, o_full, Hp, scale=attn.scale, out_scale=w, accumulate=True, bounded_scores=bs)
-            else:
-                K.attention(q, k, v, o_full, Hp, scale=attn.scale, bounded_scores=bs)
+        # (q and o with the last shard's padding rows: the standard processor attends them too, the resample one
+        # leaves them alone; the keys are the N real rows)
+        attn.processor.attend_heads(attn, full[..., :Dp], full[:, :N, Dp:2 * Dp], full[:, :N, 2 * Dp:], T,
+                                    self.rope_full, m, plan, fused, pk, pv, float(prev_clip_weight) if prev else 0.0,
+                                    o_full)
         del full
         return heads_to_rows(self.comm, self.rank, o_full)
+
+    def gather_rows(self, proj: torch.Tensor, B: int) -> torch.Tensor:
+        """The head's exchange: this rank's proj_out rows [B * nv, pc] -> every video row [B * Nv, pc], on every
+        rank."""
+        sh, P = self.sh, self.comm.P
+        pc = proj.shape[-1]
+        pad = torch.zeros(B, sh.n, pc, device=proj.device, dtype=BF16)
+        pad[:, :sh.nv] = proj.view(B, sh.nv, pc)
+        allp = self.comm.all_gather(self.rank, pad)                                   # [P, B, n, pc]
+        rows = [allp[j, :, :Shard(sh.N, sh.T, P, j).nv] for j in range(P)]
+        return torch.cat(rows, 1)[:, :sh.N - sh.T].reshape(-1, pc).contiguous()
 
 
 def qkv_to_heads(comm, rank: int, qkv: torch.Tensor, parts: int = 3) -> torch.Tensor:
@@ -260,105 +251,38 @@ def _check(model, fp8_attrs=("ff_mx", "qkv_mx", "out_mx")):
 
 
 # ------------------------------------------------------------------------------------------------------------------
-# sharded forwards (the models' forward semantics, one rank's shard)
+# sharded forwards: the models' own inference forwards (`_forward_infer`) with this rank's split context
 # ------------------------------------------------------------------------------------------------------------------
 
 def branch_forward(branch, comm, rank: int, hidden_states, encoder_hidden_states, branch_cond, timestep,
                    image_rotary_emb=None, conditioning_scale: float = 1.0) -> List[torch.Tensor]:
     """CogvideoXBranchModel.forward on one shard: returns the samples as this shard's video rows [B, nv, D]."""
     _check(branch)
-    dev = branch.proj_out.weight.device
-    B = hidden_states.shape[0]
-    hs, bc, enc = (_bf(t.to(dev)) for t in (hidden_states, branch_cond, encoder_hidden_states))
-    T = enc.shape[1]
-    emb = branch._time_embed(timestep, B, dev)
-    x_full = branch.patch_embed.embed(enc, hs, bc)
-    sh = Shard(x_full.shape[1], T, comm.P, rank)
-    x = sh.rows(x_full)
-    del x_full
-    ctx = _Ctx(comm, rank, sh)
-    rope = sh.rope(_rope_dev(image_rotary_emb, dev))
-    D = x.shape[-1]
-    outs = []
-    scale = float(conditioning_scale)
-    for block, lin in zip(branch.transformer_blocks, branch.branch_blocks):
-        x = block.forward_joint(x, sh.tl, emb, rope, attend=ctx.attend)
-        o = torch.empty(B, sh.n, D, device=dev, dtype=BF16)
-        epi = NAT.EPI_BIAS if scale == 1.0 else NAT.EPI_BIAS_SCALE
-        K.gemm(x.view(B * sh.n, D), [lin.weight], [lin.bias], o.view(B * sh.n, D), epilogue=epi, alpha=scale)
-        outs.append(o[:, sh.tl:])
-    return outs
+    inputs = branch._inputs(hidden_states, encoder_hidden_states, branch_cond, timestep, image_rotary_emb)
+    return branch._forward_infer(*inputs, float(conditioning_scale), split=_Ctx(comm, rank))
 
 
 def transformer_forward(model, comm, rank: int, hidden_states, encoder_hidden_states, timestep,
                         image_rotary_emb=None, branch_block_samples=None, branch_block_masks=None,
                         add_first: bool = False, return_hidden_states: bool = False,
                         id_pool_resample_learnable: bool = False, prev_hidden_states=None,
-                        prev_clip_weight: Optional[float] = None, prev_resample_mask=None):
+                        prev_clip_weight: Optional[float] = None, prev_resample_mask=None,
+                        return_resample_mask: bool = False):
     """CogVideoXTransformer3DModel.forward on one shard.  `branch_block_samples` are the branch's shard samples
     (`branch_forward` on the same rank).  Returns the full noise prediction on every rank (and this shard's hidden
-    states when asked: [B, n, D] each).  The any-length pipeline's window hand-off (anyl.py:962-988):
-    prev_hidden_states = the previous window's shard hidden states ({layer: [B, n, D]}, what this function returned
-    for it), prev_clip_weight, and prev_resample_mask = the full [B, N] mask the previous window returned."""
+    states when asked: [B, n, D] each; with return_resample_mask too, the full bool [B, N] mask).  The any-length
+    pipeline's window hand-off (anyl.py:962-988): prev_hidden_states = the previous window's shard hidden states
+    ({layer: [B, n, D]}, what this function returned for it), prev_clip_weight, and prev_resample_mask = the full
+    [B, N] mask the previous window returned.  No self-guidance and no cfg_shared_video under the split."""
     _check(model)
-    dev = model.proj_out.weight.device
-    cfg = model.config
-    B, F, C, H, W = hidden_states.shape
-    p = cfg.patch_size
-    hs, enc = _bf(hidden_states.to(dev)), _bf(encoder_hidden_states.to(dev))
-    T = enc.shape[1]
-    Nv = F * (H // p) * (W // p)
-    emb = model._time_embed(timestep, B, dev)
-    x_full = model.patch_embed.embed(enc, hs)
-    sh = Shard(x_full.shape[1], T, comm.P, rank)
-    x = sh.rows(x_full)
-    del x_full
-    rope_full = _rope_dev(image_rotary_emb, dev, grid=(F, H // p, W // p))
-    rope = sh.rope(rope_full)
-    tok_mask = full_mask = None
-    if branch_block_masks is not None:
-        tm = K.patch_mask(branch_block_masks.to(dev), p)
-        tok_mask = sh.video_rows(tm).contiguous()
-        if id_pool_resample_learnable:
-            full_mask = torch.zeros(B, T + tm.shape[1], device=dev, dtype=torch.bool)
-            full_mask[:, T:] = tm.bool()
-    if id_pool_resample_learnable and full_mask is None:
-        raise ValueError("id_pool_resample needs masks")
-    ctx = _Ctx(comm, rank, sh, rope_full, _u8(full_mask), _u8(prev_resample_mask))
-    bs = list(branch_block_samples) if branch_block_samples is not None else None
-    nl = len(model.transformer_blocks)
-    interval = int(np.ceil(nl / len(bs))) if bs else 1
-    hs_list = []
-    for i, block in enumerate(model.transformer_blocks):
-        inj = None
-        if bs is not None:
-            if not add_first:
-                inj = bs[i // interval]
-            elif i < len(bs):
-                inj = bs[i]
-        pj = None
-        if prev_hidden_states is not None:
-            pj = prev_hidden_states.get(i) if isinstance(prev_hidden_states, dict) else prev_hidden_states
-        x = block.forward_joint(x, sh.tl, emb, rope, prev_joint=pj,
-                                prev_clip_weight=prev_clip_weight if pj is not None else None,
-                                inject=inj, inject_mask=tok_mask if inj is not None else None, attend=ctx.attend)
-        if return_hidden_states:
-            hs_list.append(x)
-    D = x.shape[-1]
-    mod = K.linear_small(emb, model.norm_out.linear.weight, model.norm_out.linear.bias, act_in=K.ACT_SILU)
-    y = K.final_norm(x, sh.tl, model.norm_final.weight, model.norm_final.bias, model.norm_out.norm.weight,
-                     model.norm_out.norm.bias, model.norm_out.norm.eps, mod)
-    pc = model.proj_out.weight.shape[0]
-    proj = torch.zeros(B, sh.n, pc, device=dev, dtype=BF16)
-    proj[:, :sh.nv] = K.linear(y.view(B * sh.nv, D), model.proj_out.weight, model.proj_out.bias).view(B, sh.nv, pc)
-    allp = comm.all_gather(rank, proj)                                            # [P, B, n, pc]
-    rows = []
-    for j in range(comm.P):
-        sj = Shard(sh.N, T, comm.P, j)
-        rows.append(allp[j, :, :sj.nv])
-    full = torch.cat(rows, 1)[:, :Nv].reshape(B * Nv, pc).contiguous()
-    out = K.unpatchify(full, B, F, cfg.out_channels, H, W, p)
-    return (out, hs_list) if return_hidden_states else (out,)
+    out, hs_list, mask = model._forward_infer(
+        hidden_states, encoder_hidden_states, timestep, image_rotary_emb,
+        (prev_hidden_states, prev_clip_weight, prev_resample_mask), branch_block_samples, branch_block_masks, add_first,
+        return_hidden_states=return_hidden_states, return_resample_mask=return_resample_mask,
+        id_pool_resample_learnable=id_pool_resample_learnable, split=_Ctx(comm, rank))
+    if not return_hidden_states:
+        return (out,)
+    return (out, hs_list, mask) if return_resample_mask else (out, hs_list)
 
 
 class UlyssesModels:
@@ -402,18 +326,8 @@ class _TransformerView:
         res = transformer_forward(self.model, self.o.comm, self.o.rank, hidden_states, encoder_hidden_states,
                                   timestep, image_rotary_emb, branch_block_samples, branch_block_masks, add_first,
                                   return_hidden_states, id_pool_resample_learnable, akw.get("prev_hidden_states"),
-                                  akw.get("prev_clip_weight"), akw.get("prev_resample_mask"))
-        out = res[0]
-        if not return_hidden_states:
-            return (out,) if not return_dict else Transformer2DModelOutput(sample=out)
-        rm = None
-        if return_resample_mask:
-            if branch_block_masks is None:
-                raise ValueError("id_pool_resample needs masks")
-            p = self.config.patch_size
-            tm = K.patch_mask(branch_block_masks.to(out.device), p)
-            T = encoder_hidden_states.shape[1]
-            rm = torch.zeros(tm.shape[0], T + tm.shape[1], device=out.device, dtype=torch.bool)
-            rm[:, T:] = tm.bool()
-            return (out, res[1], rm)
-        return (out, res[1])
+                                  akw.get("prev_clip_weight"), akw.get("prev_resample_mask"),
+                                  return_resample_mask=return_resample_mask)
+        if not return_hidden_states and return_dict:
+            return Transformer2DModelOutput(sample=res[0])
+        return res
