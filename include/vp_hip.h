@@ -8,6 +8,13 @@
  *   - Threading: stateless and re-entrant; each call is asynchronous on `stream` and may be captured in a graph.
  *   - Storage dtype: bf16 (`__bf16` / torch.bfloat16) unless stated; accumulation is fp32.
  *
+ *   - Multi-GPU: the library launches no collective.  The head-parallel (Ulysses) split of one clip
+ *     (videopainter_amd/ulysses.py) exchanges buffers these kernels write and read in place: in bf16 the pre-norm
+ *     q | k | v, and on the fp8 path (ABI 25) vp_qkv_heads_pack_fp8's send buffer [P, n, B, 4 Dp] — q and k as the
+ *     e4m3 operands of vp_attention_fwd_fp8, v in bf16 — whose received form is that kernel's and vp_v_pack_fp8's
+ *     operands through strides, and an attention output [P, n, B, Dp] that vp_mx_quantize_heads_bf16 gathers into the
+ *     fp8 output projection's MX operand.
+ *
  * Each entry point cites the reference interface it replaces (paths relative to
  * /root/reference/diffusers/src/diffusers/, abbreviated DF/).  The Python host mirror that binds them by ctypes is
  * videopainter_amd/_native.py; the reference-side binding a maintainer would add is shown in INTEGRATION.md.
@@ -26,7 +33,7 @@ extern "C" {
 #define VP_ERR_UNSUPPORTED 1001
 
 /* ABI version: bump when any struct layout or signature below changes. */
-#define VP_ABI_VERSION 24
+#define VP_ABI_VERSION 25
 int vp_abi_version(void);
 /* "<sha256 of sources + flags>:<sha256 of the compiler version>" of the build (no reference counterpart) */
 const char* vp_build_digest(void);
@@ -174,6 +181,14 @@ int64_t vp_mx_scale_bytes(int64_t rows, int64_t K);
 /* rows x K bf16 (row stride ld_in elements) -> MX e4m3 (row stride ld_out bytes) + scales (layout above) */
 int vp_mx_quantize_bf16(const void* x, int64_t ld_in, void* q, int64_t ld_out, void* scales, int32_t rows, int32_t K,
                         void* stream);
+
+/* The same quantiser reading the head-parallel (Ulysses) split's second receive buffer (ABI 25): x bf16
+ * [P, n, B, Dp] contiguous (head group, row, batch; 16-byte aligned) -> the MX tensor of B * n rows and K = P * Dp
+ * columns whose row b * n + i, columns [j * Dp, (j + 1) * Dp) are x[j, i, b, :] — the fp8 output projection's operand
+ * without the re-layout copy; byte for byte vp_mx_quantize_bf16 of the re-laid-out [B * n, K] tensor.  Dp % 64 == 0
+ * (whole heads: a 32-element block never straddles two head groups), K % 128 == 0, ld_out >= K bytes. */
+int vp_mx_quantize_heads_bf16(const void* x, void* q, int64_t ld_out, void* scales, int32_t B, int32_t n, int32_t P,
+                              int32_t Dp, void* stream);
 
 /* out = epilogue(A · Wᵀ) with A and W in MX-FP8.  base: as vp_gemm_desc with A / W[] pointing at the e4m3
  * elements (lda in BYTES; W rows are K bytes), epilogues VP_EPI_BIAS .. VP_EPI_BIAS_ADDROWS writing bf16 C, or
@@ -380,6 +395,23 @@ int vp_head_norm_rope_fp8_rows(const void* x_in, int64_t ld_in, int64_t bs_in, v
                                const void* ln_w, const void* ln_b, float eps, const float* cos, const float* sin,
                                float out_mul, const uint8_t* tok_mask, int64_t mask_bstride, float pre_scale,
                                const int32_t* dst_rows, void* stream);
+
+/* The send packer of the head-parallel (Ulysses) split's fp8 path (ABI 25; no reference counterpart): one launch that
+ * reads a row shard's pre-norm fused projection qkv bf16 [B, n, 3 * H * 64] (row stride ld_in, batch stride bs_in,
+ * elements; 16-byte aligned, multiples of 8) once and writes the first all-to-all's send buffer, uint8
+ * [P, n, B, 4 * Dp] contiguous with Dp = (H / P) * 64 (H % P == 0): for head group j, row i, batch b
+ *   bytes [0, Dp)       q of the group's heads as e4m3 — the bytes vp_head_norm_rope_fp8 writes for those columns with
+ *                       q_ln_w / q_ln_b / q_eps and out_mul = q_mul (scale * log2 e * 2^q_exp),
+ *   bytes [Dp, 2 Dp)    k likewise with k_ln_w / k_ln_b / k_eps and k_mul (2^k_exp),
+ *   bytes [2 Dp, 4 Dp)  v of the group's heads, bf16, unchanged.
+ * text_len (0 .. n) and cos / sin (fp32 [n - text_len, 64], zero rows for padding; NULL: no RoPE) are the shard's.
+ * Chunk j is what rank j receives; the [n, B] order inside a chunk makes the received [P, n, B, 4 Dp] buffer the
+ * attention's operands as it stands: q8 / k8 / v of every row of the head group are strided views of it (row stride
+ * B * 4 Dp bytes, batch stride 4 Dp bytes) for vp_attention_fwd_fp8 and vp_v_pack_fp8. */
+int vp_qkv_heads_pack_fp8(const void* qkv, int64_t ld_in, int64_t bs_in, void* send, int32_t B, int32_t n, int32_t H,
+                          int32_t P, int32_t text_len, const void* q_ln_w, const void* q_ln_b, float q_eps,
+                          const void* k_ln_w, const void* k_ln_b, float k_eps, const float* cos, const float* sin,
+                          float q_mul, float k_mul, void* stream);
 
 /* y[b, n, :] = rnd(rnd(x[b, n, :] * tok_mask[b, n]) * scale) — the masked value copy of the resample processor. */
 /* (vp_head_norm_rope_bf16 and vp_mask_scale_rows_bf16 with dst_rows != NULL: output row n of batch b is written to

@@ -11,7 +11,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VP_HIP_LIB", os.path.join(_HERE, "_lib", "libvp_hip.so"))
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 vp = C.c_void_p
 i32 = C.c_int32
@@ -138,6 +138,9 @@ _SIGS = {
     "vp_gemm_mx_fp8": (i32, [C.POINTER(GemmMxDesc), vp]),
     "vp_mx_scale_bytes": (i64, [i64, i64]),
     "vp_mx_quantize_bf16": (i32, [vp, i64, vp, i64, vp, i32, i32, vp]),
+    "vp_mx_quantize_heads_bf16": (i32, [vp, vp, i64, vp, i32, i32, i32, i32, vp]),
+    "vp_qkv_heads_pack_fp8": (i32, [vp, i64, i64, vp, i32, i32, i32, i32, i32, vp, vp, f32, vp, vp, f32, vp, vp, f32,
+                                    f32, vp]),
     "vp_adaln_modulate_mx_fp8": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, f32, vp, i64, vp]),
     "vp_attention_fwd_bf16": (i32, [C.POINTER(AttnDesc), vp]),
     "vp_attention_fwd_fp8": (i32, [C.POINTER(AttnFp8Desc), vp]),

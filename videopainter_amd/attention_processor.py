@@ -284,6 +284,25 @@ class CogVideoXAttnProcessor2_0:
         # per-(d, 32 keys) scales, the block-scaled MFMA kernel
         q_exp, k_exp = fp8
         nq, nk = attn.norm_q, attn.norm_k
+        q8 = K.head_norm_rope_fp8(q, H, text_len, nq.weight, nq.bias, nq.eps, rope,
+                                  attn.scale * K.LOG2E * 2.0 ** q_exp)
+        k8 = K.head_norm_rope_fp8(k, H, text_len, nk.weight, nk.bias, nk.eps, rope, 2.0 ** k_exp)
+        return self.attend_heads_fp8(attn, q8, k8, v, text_len, rope,
+                                     lambda: _prev_kv(attn, prev_hidden_states, prev_clip_weight),
+                                     augmented_rows((attn.to_out[0],), B, Ntok, D, x.device))
+
+    def attend_heads_fp8(self, attn, q8, k8, v, text_len: int, rope, prev, o) -> torch.Tensor:
+        """The fp8 attention on operands quantised already: q8 / k8 e4m3 [B, Nq, h*64] / [B, N, h*64] (the bytes of
+        `head_norm_rope_fp8` with the factors of `attn.fp8_qk_exp`), v bf16 [B, N, h*64] — views at any row and batch
+        stride of every head, or of one head group (the Ulysses split, ulysses.py: views of its receive buffer; q8 may
+        carry the last shard's padding rows past k8's N).  prev() -> (pk, pv, w): the previous window's pre-norm K / V
+        projections on the same heads and the blend weight (`_prev_kv`'s return), asked for after this window's V is
+        packed (the unsplit launch order: the pack, then the previous window's projection); o: the bf16 output
+        [B, Nq, h*64], at any strides too.  text_len / rope: of the N rows (the previous window's keys are quantised
+        here)."""
+        H = k8.shape[-1] // 64
+        q_exp, k_exp = attn.fp8_qk_exp
+        nk = attn.norm_k
 
         def operands(k_, v_):
             return (K.head_norm_rope_fp8(k_, H, text_len, nk.weight, nk.bias, nk.eps, rope, 2.0 ** k_exp),
@@ -291,11 +310,8 @@ class CogVideoXAttnProcessor2_0:
 
         def attention(k_, v_, **kw):
             K.attention_fp8(q8, k_, v_, o, H, q_exp, k_exp, **kw)
-        q8 = K.head_norm_rope_fp8(q, H, text_len, nq.weight, nq.bias, nq.eps, rope,
-                                  attn.scale * K.LOG2E * 2.0 ** q_exp)
-        own = operands(k, v)
-        o = augmented_rows((attn.to_out[0],), B, Ntok, D, x.device)
-        self._blend(own, *_prev_kv(attn, prev_hidden_states, prev_clip_weight), operands, attention)
+        own = (k8, K.v_pack_fp8(v, H))
+        self._blend(own, *prev(), operands, attention)
         return o
 
     def head_plan(self, attn, text_len: int, rope, prev: bool, resample_mask=None, prev_resample_mask=None):

@@ -1503,6 +1503,19 @@ extern "C" int vp_gemm_mx_fp8(const vp_gemm_mx_desc* x, void* stream) {
 }
 
 // ---- MX quantiser: 8 elements per thread, 4 threads per 32-element block ----
+// chunk c (8 columns) of output row r, read at src: the thread's 8 e4m3 bytes and, from the block's first lane, its scale
+VP_DEV void mx_quantize_chunk(const bf16* __restrict__ src, uint8_t* __restrict__ q, int64_t ld_out,
+                              uint8_t* __restrict__ scales, int64_t r, int c, int K) {
+  const bf16x8 v = *(const bf16x8*)src;
+  float f[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) f[e] = bf2f(v[e]);
+  uint8_t sb;
+  const u32x2 pk = mx_quantize_quarter(f, sb);
+  *(u32x2*)(q + r * ld_out + c * 8) = pk;
+  if ((c & 3) == 0) scales[mx_scale_off(r, c >> 2, K)] = sb;
+}
+
 __global__ __launch_bounds__(256) void mx_quantize_kernel(const bf16* __restrict__ x, int64_t ld_in,
                                                           uint8_t* __restrict__ q, int64_t ld_out,
                                                           uint8_t* __restrict__ scales, int rows, int K) {
@@ -1511,14 +1524,25 @@ __global__ __launch_bounds__(256) void mx_quantize_kernel(const bf16* __restrict
   const int64_t r = i / cpr;
   const int c = (int)(i - r * cpr);
   if (r >= rows) return;  // whole 4-lane groups leave together (cpr % 4 == 0)
-  const bf16x8 v = *(const bf16x8*)(x + r * ld_in + c * 8);
-  float f[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) f[e] = bf2f(v[e]);
-  uint8_t sb;
-  const u32x2 pk = mx_quantize_quarter(f, sb);
-  *(u32x2*)(q + r * ld_out + c * 8) = pk;
-  if ((c & 3) == 0) scales[mx_scale_off(r, c >> 2, K)] = sb;
+  mx_quantize_chunk(x + r * ld_in + c * 8, q, ld_out, scales, r, c, K);
+}
+
+// the Ulysses split's receive side (vp_mx_quantize_heads_bf16): output row b n + i, columns [j Dp, (j + 1) Dp) are
+// row (j, i, b) of the second all-to-all's receive buffer [P, n, B, Dp] — the gather and the quantiser in one pass;
+// Dp % 64 == 0, so a 32-column block (4 consecutive lanes) never straddles two head groups and a head group's Dp / 8
+// lanes read one contiguous 2 Dp-byte row
+__global__ __launch_bounds__(256) void mx_quantize_heads_kernel(const bf16* __restrict__ x, uint8_t* __restrict__ q,
+                                                                int64_t ld_out, uint8_t* __restrict__ scales, int B,
+                                                                int n, int Dp, int K) {
+  const int cpr = K / 8;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t r = i / cpr;
+  const int c = (int)(i - r * cpr);
+  if (r >= (int64_t)B * n) return;  // whole 4-lane groups leave together (cpr % 4 == 0)
+  const int b = (int)(r / n);
+  const int row = (int)(r - (int64_t)b * n);
+  const int j = c * 8 / Dp;
+  mx_quantize_chunk(x + (((int64_t)j * n + row) * B + b) * Dp + (c * 8 - j * Dp), q, ld_out, scales, r, c, K);
 }
 
 extern "C" int64_t vp_mx_scale_bytes(int64_t rows, int64_t K) { return ((rows + 255) / 256) * (K / 128) * 1024; }
@@ -1531,6 +1555,21 @@ extern "C" int vp_mx_quantize_bf16(const void* x, int64_t ld_in, void* q, int64_
   const int64_t n = (int64_t)rows * (K / 8);
   hipLaunchKernelGGL(mx_quantize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (const bf16*)x, ld_in, (uint8_t*)q, ld_out, (uint8_t*)scales, rows, K);
+  VP_CHECK_LAUNCH();
+  return VP_OK;
+}
+
+extern "C" int vp_mx_quantize_heads_bf16(const void* x, void* q, int64_t ld_out, void* scales, int32_t B, int32_t n,
+                                         int32_t P, int32_t Dp, void* stream) {
+  if (!x || !q || !scales || B <= 0 || n <= 0 || P <= 0 || Dp <= 0 || (Dp % 64)) return VP_ERR_ARG;
+  const int64_t K = (int64_t)P * Dp;
+  if ((K % 128) || K > 0x7fffffff || (int64_t)B * n > 0x7fffffff || ld_out < K || (ld_out % 8) ||
+      ((uintptr_t)x % 16) || ((uintptr_t)q % 8))
+    return VP_ERR_ARG;
+  const int64_t grid = ((int64_t)B * n * (K / 8) + 255) / 256;
+  if (grid > 0x7fffffff) return VP_ERR_ARG;
+  hipLaunchKernelGGL(mx_quantize_heads_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream,
+                     (const bf16*)x, (uint8_t*)q, ld_out, (uint8_t*)scales, B, n, Dp, (int)K);
   VP_CHECK_LAUNCH();
   return VP_OK;
 }

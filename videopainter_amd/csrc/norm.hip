@@ -221,6 +221,18 @@ __global__ __launch_bounds__(ROW_THREADS) void final_norm_kernel(const bf16* __r
 // HPG vectors' loads are in flight together (one vector per group: 16 of the 20 loads were the shared operands, and
 // one HBM load chain per thread left the stream at 3 TB/s).  64 groups per 256-thread block.  FP8: the bf16 value
 // the bf16 kernel writes, times out_mul, as e4m3 (strides then in bytes)
+// four normed + rotated values -> one dword of e4m3: the bf16 value the bf16 kernel writes, times out_mul, clamped
+// to +-448, RNE (shared by the fp8 form below and the Ulysses send packer: the same bytes)
+VP_DEV uint32_t e4m3_quad(const float* x, float out_mul) {
+  int wd = 0;
+  float y[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) y[r] = __builtin_amdgcn_fmed3f(rbf(x[r]) * out_mul, 448.f, -448.f);
+  wd = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], wd, false);
+  wd = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], wd, true);
+  return (uint32_t)wd;
+}
+
 template <bool FP8, int HPG>
 __global__ __launch_bounds__(256) void head_norm_rope_kernel(const bf16* __restrict__ xin, int64_t ld_in,
                                                             int64_t bs_in, void* __restrict__ xout, int64_t ld_out,
@@ -282,13 +294,7 @@ __global__ __launch_bounds__(256) void head_norm_rope_kernel(const bf16* __restr
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         if constexpr (FP8) {
-          int wd = 0;
-          float y[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) y[r] = __builtin_amdgcn_fmed3f(rbf(x[4 * j + r]) * out_mul, 448.f, -448.f);
-          wd = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], wd, false);
-          wd = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], wd, true);
-          *(uint32_t*)((uint8_t*)xout + o + 16 * j) = (uint32_t)wd;
+          *(uint32_t*)((uint8_t*)xout + o + 16 * j) = e4m3_quad(x + 4 * j, out_mul);
         } else {
           bf16x4 ov;
 #pragma unroll
@@ -320,6 +326,119 @@ void launch_head_norm_rope(hipStream_t s, const bf16* xin, int64_t ld_in, int64_
     hipLaunchKernelGGL((head_norm_rope_kernel<FP8, 1>), grid, dim3(256), 0, s, xin, ld_in, bs_in, xout, ld_out,
                        bs_out, ngroups, Ntok, H, text_len, lw, lb, eps, cosp, sinp, tok_mask, mask_bs, pre_scale,
                        out_mul, dst_rows);
+}
+
+// ---- the Ulysses split's send packer (vp_qkv_heads_pack_fp8): a shard's pre-norm q | k | v rows [B, n, 3 D] ->
+// the first all-to-all's send buffer uint8 [P, n, B, 4 Dp], per (head group, row, batch) q e4m3 | k e4m3 | v bf16 ----
+// The lane layout of head_norm_rope_kernel (4 lanes per head vector, HPG heads of one token per lane group, the
+// token's cos / sin quads loaded once for q and k), its arithmetic (ln64_rope16_regs) and its conversion (e4m3_quad):
+// the same bytes as vp_head_norm_rope_fp8 on the head group's columns.  A lane's four e4m3 dwords (bytes 16 j + 4 g)
+// are transposed inside the quad, so lane g stores bytes [16 g, 16 g + 16) of the head: one 16-byte store per lane,
+// 64 contiguous bytes per head; v is copied as 16-byte chunks (two per lane and head).
+template <int X>
+VP_DEV uint32_t quad_xor(uint32_t v) {  // the value of lane ^ X (X = 1, 2, 3) of the lane's quad (DPP quad_perm)
+  constexpr int ctrl = X == 1 ? 0xB1 : X == 2 ? 0x4E : 0x1B;
+  return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, ctrl, 0xf, 0xf, true);
+}
+
+// wd[j] = this lane's dword at byte 16 j + 4 g of a 64-byte vector -> the 16 bytes [16 g, 16 g + 16)
+VP_DEV u32x4 quad_gather16(const uint32_t (&wd)[4], int g) {
+  uint32_t o[4] = {0, 0, 0, 0};
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    const int p = g ^ s;  // the partner: it wants this lane's dword p, and sends its dword g, which is o[p] here
+    const uint32_t snd = p == 0 ? wd[0] : p == 1 ? wd[1] : p == 2 ? wd[2] : wd[3];
+    const uint32_t rcv = s == 0 ? snd : s == 1 ? quad_xor<1>(snd) : s == 2 ? quad_xor<2>(snd) : quad_xor<3>(snd);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o[i] = p == i ? rcv : o[i];
+  }
+  return (u32x4){o[0], o[1], o[2], o[3]};
+}
+
+template <int HPG>
+__global__ __launch_bounds__(256) void qkv_heads_pack_fp8_kernel(
+    const bf16* __restrict__ qkv, int64_t ld_in, int64_t bs_in, uint8_t* __restrict__ send, int64_t ngroups, int B,
+    int n, int H, int P, int text_len, const bf16* __restrict__ lwq, const bf16* __restrict__ lbq, float eps_q,
+    const bf16* __restrict__ lwk, const bf16* __restrict__ lbk, float eps_k, const float* __restrict__ cosp,
+    const float* __restrict__ sinp, float q_mul, float k_mul) {
+  const int64_t grp = (int64_t)blockIdx.x * 64 + (threadIdx.x >> 2);
+  const int g = threadIdx.x & 3;
+  const bool valid = grp < ngroups;  // (every lane runs to the end: the quad exchange needs its four lanes)
+  const int64_t gg = valid ? grp : ngroups - 1;
+  const int Hg = H / HPG;
+  const int hg = (int)(gg % Hg);
+  const int64_t bn = gg / Hg;
+  const int i = (int)(bn % n);
+  const int b = (int)(bn / n);
+  const int D = H * 64, hp = H / P, Dp = hp * 64;
+  const bf16* src = qkv + (int64_t)b * bs_in + (int64_t)i * ld_in + hg * 64;
+  // v first (its loads return first, its stores leave before the norms), then q and k, all in flight together
+  bf16x8 vr[HPG][2];
+#pragma unroll
+  for (int k = 0; k < HPG; ++k)
+#pragma unroll
+    for (int t = 0; t < 2; ++t) vr[k][t] = *(const bf16x8*)(src + 2 * D + k * Hg * 64 + g * 8 + 32 * t);
+  bf16x4 xr[2][HPG][4];
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+#pragma unroll
+    for (int k = 0; k < HPG; ++k)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) xr[s][k][j] = *(const bf16x4*)(src + s * D + k * Hg * 64 + g * 4 + 16 * j);
+  const bool rot = cosp != nullptr && i >= text_len;
+  const float* cr = rot ? cosp + (int64_t)(i - text_len) * 64 : nullptr;
+  const float* sr = rot ? sinp + (int64_t)(i - text_len) * 64 : nullptr;
+  f32x4 cs[4], sn[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int c = 16 * j + 4 * g;
+    cs[j] = rot ? *(const f32x4*)(cr + c) : (f32x4){1.f, 1.f, 1.f, 1.f};
+    sn[j] = rot ? *(const f32x4*)(sr + c) : (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
+  // byte offset of head h's chunk row: head group h / hp, this row, this batch
+  int64_t o0[HPG];
+  int hh[HPG];
+#pragma unroll
+  for (int k = 0; k < HPG; ++k) {
+    const int h = hg + k * Hg;
+    const int grp_h = h / hp;
+    hh[k] = h - grp_h * hp;
+    o0[k] = (((int64_t)grp_h * n + i) * B + b) * (4 * (int64_t)Dp);
+  }
+  if (valid) {
+#pragma unroll
+    for (int k = 0; k < HPG; ++k)
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+        *(bf16x8*)(send + o0[k] + 2 * Dp + hh[k] * 128 + g * 16 + 64 * t) = vr[k][t];
+  }
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    const bf16* lw = s == 0 ? lwq : lwk;
+    const bf16* lb = s == 0 ? lbq : lbk;
+    const float eps = s == 0 ? eps_q : eps_k;
+    const float mul = s == 0 ? q_mul : k_mul;
+    bf16x4 w[4], bb[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      w[j] = *(const bf16x4*)(lw + 16 * j + 4 * g);
+      bb[j] = *(const bf16x4*)(lb + 16 * j + 4 * g);
+    }
+#pragma unroll
+    for (int k = 0; k < HPG; ++k) {
+      float x[16];
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) x[4 * j + r] = bf2f(xr[s][k][j][r]);
+      ln64_rope16_regs<1, 2>(x, w, bb, eps, cs, sn, rot);
+      uint32_t wd[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) wd[j] = e4m3_quad(x + 4 * j, mul);
+      const u32x4 row16 = quad_gather16(wd, g);
+      if (valid) *(u32x4*)(send + o0[k] + s * Dp + hh[k] * 64 + g * 16) = row16;
+    }
+  }
 }
 
 __global__ __launch_bounds__(256) void mask_scale_rows_kernel(const bf16* __restrict__ xin, int64_t ld_in,
@@ -470,6 +589,32 @@ extern "C" int vp_head_norm_rope_fp8(const void* x_in, int64_t ld_in, int64_t bs
                                      const float* sin, float out_mul, void* stream) {
   return vp_head_norm_rope_fp8_rows(x_in, ld_in, bs_in, q_out, ld_out, bs_out, B, Ntok, H, text_len, ln_w, ln_b, eps,
                                     cos, sin, out_mul, nullptr, 0, 1.f, nullptr, stream);
+}
+
+extern "C" int vp_qkv_heads_pack_fp8(const void* qkv, int64_t ld_in, int64_t bs_in, void* send, int32_t B, int32_t n,
+                                     int32_t H, int32_t P, int32_t text_len, const void* q_ln_w, const void* q_ln_b,
+                                     float q_eps, const void* k_ln_w, const void* k_ln_b, float k_eps,
+                                     const float* cos, const float* sin, float q_mul, float k_mul, void* stream) {
+  if (!qkv || !send || !q_ln_w || !q_ln_b || !k_ln_w || !k_ln_b || B <= 0 || n <= 0 || H <= 0 || P <= 0)
+    return VP_ERR_ARG;
+  if ((H % P) || text_len < 0 || text_len > n) return VP_ERR_ARG;
+  if (((uintptr_t)qkv % 16) || ((uintptr_t)send % 16) || (ld_in % 8) || (bs_in % 8) || ld_in < (int64_t)3 * H * 64)
+    return VP_ERR_ARG;
+  if ((cos == nullptr) != (sin == nullptr) || !(q_mul > 0.f) || !(k_mul > 0.f)) return VP_ERR_ARG;
+  const int hpg = H % VP_HNR_HPG == 0 ? VP_HNR_HPG : 1;
+  const int64_t ngroups = (int64_t)B * n * (H / hpg);
+  const int64_t grid = (ngroups + 63) / 64;
+  if (grid > 0x7fffffff) return VP_ERR_ARG;
+#define VP_PACK(N)                                                                                                  \
+  hipLaunchKernelGGL((qkv_heads_pack_fp8_kernel<N>), dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream,       \
+                     (const bf16*)qkv, ld_in, bs_in, (uint8_t*)send, ngroups, B, n, H, P, text_len,                 \
+                     (const bf16*)q_ln_w, (const bf16*)q_ln_b, q_eps, (const bf16*)k_ln_w, (const bf16*)k_ln_b,     \
+                     k_eps, cos, sin, q_mul, k_mul)
+  if (hpg == 4) VP_PACK(4);
+  else VP_PACK(1);
+#undef VP_PACK
+  VP_CHECK_LAUNCH();
+  return VP_OK;
 }
 
 extern "C" int vp_mask_scale_rows_bf16(const void* x_in, int64_t ld_in, int64_t bs_in, void* y, int64_t ld_out,

@@ -255,6 +255,24 @@ def mx_quantize(x: torch.Tensor, out: Optional["MXTensor"] = None) -> "MXTensor"
     return out
 
 
+def mx_quantize_heads(recv: torch.Tensor, out: Optional["MXTensor"] = None) -> "MXTensor":
+    """The head-parallel split's second receive buffer, bf16 [P, n, B, Dp] contiguous (head group, row, batch) ->
+    MXTensor [B * n, P * Dp], row b * n + i = the heads of row i of batch b in head order: `mx_quantize` of the
+    re-laid-out tensor, byte for byte, without the copy."""
+    _chk(recv, "recv")
+    if recv.dim() != 4 or not recv.is_contiguous():
+        raise ValueError(f"recv must be contiguous bf16 [P, n, B, Dp], got {tuple(recv.shape)}")
+    P, n, B, Dp = recv.shape
+    if Dp % 64 or (P * Dp) % 128:
+        raise ValueError(f"mx_quantize_heads needs Dp % 64 == 0 and P * Dp % 128 == 0, got P = {P}, Dp = {Dp}")
+    out = MXTensor(B * n, P * Dp, recv.device) if out is None else out
+    if out.rows != B * n or out.K != P * Dp:
+        raise ValueError(f"out must be MXTensor [{B * n}, {P * Dp}], got {out}")
+    N.check(N.lib().vp_mx_quantize_heads_bf16(_p(recv), _p(out.q), out.q.stride(0), _p(out.scales), B, n, P, Dp,
+                                              _stream()), "vp_mx_quantize_heads_bf16")
+    return out
+
+
 def gemm_mx(a: "MXTensor", weights: Sequence["MXTensor"], biases: Sequence[Optional[torch.Tensor]], out, *,
             epilogue: int = N.EPI_BIAS, alpha: float = 1.0, resid: Optional[torch.Tensor] = None,
             mod: Optional[torch.Tensor] = None, gate_chunk: int = 2, gate_text_chunk: int = 5,
@@ -607,6 +625,45 @@ def head_norm_rope_fp8(x_in: torch.Tensor, heads: int, text_len: int, ln_w, ln_b
                                                out.stride(0), B, Ntok, heads, text_len, _p(ln_w), _p(ln_b), eps,
                                                _p(cos), _p(sin), out_mul, _p(tok_mask), mb, pre_scale, _p(dst_rows),
                                                _stream()), "vp_head_norm_rope_fp8_rows")
+    return out
+
+
+def qkv_heads_pack_fp8(qkv: torch.Tensor, heads: int, P: int, text_len: int, norm_q, norm_k, rope, q_mul: float,
+                       k_mul: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The head-parallel split's send buffer of the fp8 attention: a shard's pre-norm qkv bf16 [B, n, 3 * heads * 64]
+    (any row / batch stride) -> uint8 [P, n, B, 4 * Dp], per (head group, row, batch) q e4m3 | k e4m3 | v bf16 — q / k
+    the bytes of `head_norm_rope_fp8` on the group's columns (norm_q / norm_k: the LayerNorm(64) modules; text_len /
+    rope: the shard's; q_mul / k_mul: its out_mul).  One launch (vp_qkv_heads_pack_fp8)."""
+    _chk(qkv, "qkv")
+    D = heads * 64
+    if qkv.dim() != 3 or qkv.stride(-1) != 1 or qkv.shape[-1] != 3 * D:
+        raise ValueError(f"qkv must be [B, n, {3 * D}] with a contiguous last dim, got {tuple(qkv.shape)}")
+    if P <= 0 or heads % P:
+        raise ValueError(f"{heads} heads do not split {P} ways")
+    B, n, _ = qkv.shape
+    Dp = D // P
+    if out is None:
+        out = torch.empty(P, n, B, 4 * Dp, device=qkv.device, dtype=torch.uint8)
+    _chk(out, "out", torch.uint8)
+    if tuple(out.shape) != (P, n, B, 4 * Dp) or not out.is_contiguous():
+        raise ValueError(f"out must be contiguous uint8 [{P}, {n}, {B}, {4 * Dp}]")
+    for ln in (norm_q, norm_k):
+        _chk(ln.weight, "ln weight")
+        _chk(ln.bias, "ln bias")
+        if ln.weight.numel() != 64 or ln.bias.numel() != 64:
+            raise ValueError("the qk-norm is LayerNorm over head_dim 64")
+    cos = sin = None
+    if rope is not None:
+        cos, sin = rope
+        _chk(cos, "cos", torch.float32)
+        _chk(sin, "sin", torch.float32)
+        if cos.shape[0] != n - text_len or cos.shape[1] != 64 or not cos.is_contiguous() or not sin.is_contiguous() \
+                or sin.shape != cos.shape:
+            raise ValueError(f"rope tables must be fp32 [{n - text_len}, 64], got {tuple(cos.shape)}")
+    N.check(N.lib().vp_qkv_heads_pack_fp8(_p(qkv), qkv.stride(1), qkv.stride(0), _p(out), B, n, heads, P, text_len,
+                                          _p(norm_q.weight), _p(norm_q.bias), norm_q.eps, _p(norm_k.weight),
+                                          _p(norm_k.bias), norm_k.eps, _p(cos), _p(sin), q_mul, k_mul, _stream()),
+            "vp_qkv_heads_pack_fp8")
     return out
 
 

@@ -359,27 +359,32 @@ class CogVideoXBlock(nn.Module):
     def _attention(self, x: torch.Tensor, text_len: int, rope, pn=None, prev_clip_weight=None, resample_mask=None,
                    prev_resample_mask=None, qkv=None, attend=None, keep: Optional[dict] = None) -> torch.Tensor:
         """x: the attention-input stage's xn (with an fp8 projection `qkv`: any [B, N, D] tensor, for its shape)
-        -> o [B, N, D], through the `attend` hook or the processor.  keep: handed to the processor (which fills it,
-        CogVideoXAttnProcessor2_0.attend) where the attention is the single-segment bf16 one; left as it is
-        elsewhere."""
+        -> o [B, N, D], through the `attend` hook or the processor.  The hook also gets the fp8 projection's `qkv` and
+        whether the output projection is the fp8 one (it may then return o as the MXTensor `_attn_output` takes).
+        keep: handed to the processor (which fills it, CogVideoXAttnProcessor2_0.attend) where the attention is the
+        single-segment bf16 one; left as it is elsewhere."""
         a = self.attn1
         if attend is not None:
-            return attend(a, x, text_len, rope, pn, prev_clip_weight, resample_mask, prev_resample_mask)
+            return attend(a, x, text_len, rope, pn, prev_clip_weight, resample_mask, prev_resample_mask, qkv,
+                          self.out_mx is not None)
         if (keep is not None and pn is None and qkv is None and getattr(a, "fp8_qk_exp", None) is None
                 and not isinstance(a.processor, CogVideoXAttnProcessor2_0_resample)):
             return a.processor.attend(a, x, text_len, rope, keep=keep)
         return a.processor.attend(a, x, text_len, rope, pn, prev_clip_weight, resample_mask, prev_resample_mask,
                                   qkv=qkv)
 
-    def _attn_output(self, x: torch.Tensor, o: torch.Tensor, mod1: torch.Tensor, text_len: int,
+    def _attn_output(self, x: torch.Tensor, o, mod1: torch.Tensor, text_len: int,
                      keep: Optional[dict] = None) -> torch.Tensor:
-        """to_out (bf16, or the fp8 projection of the re-quantised o) with the gated residual on x -> x_mid."""
+        """to_out (bf16, or the fp8 projection of the re-quantised o) with the gated residual on x -> x_mid.  o: bf16
+        [B, N, D], or with the fp8 projection its MX-FP8 operand already (an MXTensor [B N, D]: the head-parallel
+        split quantises while it gathers the heads, kernels.mx_quantize_heads)."""
         B, Ntok, D = x.shape
         M = B * Ntok
         x_mid = torch.empty_like(x)
         kw = dict(epilogue=NAT.EPI_GATED, resid=x.view(M, D), mod=mod1, tokens_per_batch=Ntok, text_len=text_len)
         if self.out_mx is not None:
-            om = K.mx_quantize(o.view(M, D), out=K.MXTensor(M, D, x.device, zero=False))
+            om = o if isinstance(o, K.MXTensor) else \
+                K.mx_quantize(o.view(M, D), out=K.MXTensor(M, D, x.device, zero=False))
             K.gemm_mx(om, [self.out_mx], [self.attn1.to_out[0].bias], x_mid.view(M, D), **kw)
         else:
             project_out(self.attn1.to_out[0], o.view(M, D), x_mid.view(M, D), gate_chunk=2, gate_text_chunk=5, **kw)
@@ -449,8 +454,10 @@ class CogVideoXBlock(nn.Module):
         the two batch rows of x hold the same video rows (the CFG halves entering the model's first block) — the
         block then computes their shared work once (_attend_cfg_shared) where it runs the plain bf16 path.
         attend: optional replacement of the processor's attention, `attend(attn, xn, text_len, rope, pn,
-        prev_clip_weight, resample_mask, prev_resample_mask) -> o` [B, N, D] (the Ulysses head-parallel split,
-        ulysses._Ctx.attend: x and rope are then a rank's rows, the masks the whole ones).
+        prev_clip_weight, resample_mask, prev_resample_mask, qkv, mx_out) -> o` [B, N, D] (the Ulysses head-parallel
+        split, ulysses._Ctx.attend: x and rope are then a rank's rows, the masks the whole ones; qkv: the fp8 QKV
+        projection's pre-norm output in place of xn, or None; mx_out: the output projection is the fp8 one, o may come
+        back as its MX-FP8 operand).
         keep: {"level": "attention" | "all", "train": bool}, a training forward's dict that the stages fill for its
         backward (autograd._BlockFn) without changing a launch.  "attention": the attention output "o" and its softmax
         statistics "lse" (where the attention is the single-segment bf16 one).  "all": also "mod1", "mod2", "qkv",
@@ -459,8 +466,6 @@ class CogVideoXBlock(nn.Module):
         processor = self.attn1.processor
         if not isinstance(processor, CogVideoXAttnProcessor2_0):
             raise ValueError(f"Unsupported processor type: {type(processor)}")
-        if attend is not None and (self.qkv_mx is not None or self.out_mx is not None):
-            raise NotImplementedError("the head-parallel split runs the bf16 path")
         if mod1 is None:
             mod1 = self.norm1.modulation(temb)
         if (cfg_shared_video and attend is None and keep is None and prev_joint is None

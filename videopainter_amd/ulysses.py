@@ -27,10 +27,28 @@ branch.py), which shard x, slice the row-local operands and name there what the 
 modulations, ping-pong buffers, self-guidance, cfg_shared_video); the hook's attention is the processor's
 `attend_heads` on the rank's head group.
 
-Scope: the bf16 path with both processors of the any-length pipeline — the standard one (config 2, the headline;
-with the previous-clip blend) and the ID-resample one (config 4: window 0's masked second K / V segment, later
-windows' masked previous-window K / V): the projections stay row-local, the masks and the RoPE table of the
-head-group attention are the full ones.  The fp8 modes raise NotImplementedError under the split.
+Scope: both processors of the any-length pipeline — the standard one (config 2, the headline; with the
+previous-clip blend) and the ID-resample one (config 4: window 0's masked second K / V segment, later windows' masked
+previous-window K / V): the projections stay row-local, the masks and the RoPE table of the head-group attention are
+the full ones — in bf16 and with any combination of the fp8 switches (`enable_fp8`, config 5), each behaving as it
+does unsplit: the MX-FP8 AdaLN, projections and FeedForward are row-local and run on the shard as they are, and the
+fp8 attention runs one workgroup per (batch, head, query block) over all keys, so a head group's launch computes the
+bits of the whole launch.
+
+The fp8 attention of the standard processor has an exchange of its own (`_Ctx._attend_fp8`):
+
+    qkv [B, n, 3D] pre-norm --vp_qkv_heads_pack_fp8--> uint8 [P, n, B, 4 Dp]   (q e4m3 | k e4m3 | v bf16 per row)
+    --all-to-all--> [P, n, B, 4 Dp] = q8 [B, P n, Dp], k8 / v [B, N, Dp] as strided views (`heads_fp8_views`)
+    v pack + fp8 attention for H/P heads, written into the send buffer [P, n, B, Dp] through a [B, P n, Dp] view
+    --all-to-all--> [P, n, B, Dp] --vp_mx_quantize_heads_bf16--> the fp8 output projection's operand [B n, D]
+    (without the fp8 output projection: one re-layout to [B, n, D])
+
+q and k are quantised on the shard with the norm kernel's own arithmetic, so the first exchange carries 4 B per
+element instead of 6 (the second 2: 6 B against 8 per block), and the [n, B] order inside a chunk makes both receive
+buffers the next kernel's operand as they stand — no `permute().contiguous()` on either side of either exchange.  The
+previous window's K | V (prev-clip blend) and the ID-resample processor keep the bf16 pre-norm exchange: the first is
+quantised on the head group, the second quantises there with the whole token masks and row permutation, which a shard
+does not have (its two-segment fp8 kernel runs per head group with `enable_fp8(resample_attention=True)`).
 """
 from __future__ import annotations
 
@@ -41,6 +59,7 @@ from typing import List, Optional
 import torch
 import torch.distributed as dist
 
+from . import kernels as K
 from .attention_processor import CogVideoXAttnProcessor2_0, CogVideoXAttnProcessor2_0_resample, _kv, _qkv
 from .transformer import BF16, Transformer2DModelOutput
 
@@ -180,12 +199,15 @@ class _Ctx:
         return self.sh.rows(x)
 
     def attend(self, attn, xn: torch.Tensor, text_len: int, rope, pn: Optional[torch.Tensor] = None,
-               prev_clip_weight=None, resample_mask=None, prev_resample_mask=None) -> torch.Tensor:
+               prev_clip_weight=None, resample_mask=None, prev_resample_mask=None, qkv: Optional[torch.Tensor] = None,
+               mx_out: bool = False):
         """Head-parallel attention of the shard's rows with the semantics of the block's processor (its
         `attend_heads` on this rank's head group): the row-local projections run on the shard — text_len / rope are
         the shard's —, q | k | v (and the previous window's k | v, projected from pn, its normed shard rows) are
         exchanged to every row of the head group, and the attention there takes the whole RoPE table and the whole
-        token masks resample_mask / prev_resample_mask [B, N]."""
+        token masks resample_mask / prev_resample_mask [B, N].  qkv: the block's fp8 QKV projection of the shard
+        (bf16, pre-norm; xn then only gives the shape); mx_out: the block's output projection is the fp8 one — the
+        fp8 exchange then returns its MX-FP8 operand (an MXTensor) instead of bf16 [B, n, D]."""
         B, n, D = xn.shape
         P = self.comm.P
         if attn.heads % P:
@@ -193,20 +215,65 @@ class _Ctx:
         Dp = D // P
         N, T = self.sh.N, self.sh.T
         prev = pn is not None and prev_clip_weight is not None and prev_clip_weight > 0.0
+        w = float(prev_clip_weight) if prev else 0.0
+        resample = isinstance(attn.processor, CogVideoXAttnProcessor2_0_resample)
+        if not resample and getattr(attn, "fp8_qk_exp", None) is not None:
+            return self._attend_fp8(attn, xn if qkv is None else qkv, qkv is None, text_len, rope, pn if prev else None,
+                                    w, mx_out)
         m, plan, fused = attn.processor.head_plan(attn, T, self.rope_full, prev, resample_mask, prev_resample_mask)
-        full = qkv_to_heads(self.comm, self.rank, _qkv(attn, xn, (text_len, rope) if fused else None))
-        pk = pv = None
-        if prev:  # the previous window's K / V of this shard's rows (pre-norm) -> every row of the head group
-            pkv = qkv_to_heads(self.comm, self.rank, _kv(attn, pn), parts=2)
-            pk, pv = pkv[:, :N, :Dp], pkv[:, :N, Dp:]
+        # the resample processor's fp8 form (fp8_exponents: opted in, closed-form plan) quantises on the head group,
+        # from the whole masks and the row permutation: it takes pre-norm q / k, like an fp8 projection's output
+        kw = dict(fp8=attn.processor.fp8_exponents(attn, plan)) if resample else {}
+        fused = fused and qkv is None and kw.get("fp8") is None
+        if qkv is None:
+            qkv = _qkv(attn, xn, (text_len, rope) if fused else None)
+        full = qkv_to_heads(self.comm, self.rank, qkv)
+        del qkv
+        pk, pv = self._prev_heads(attn, pn if prev else None)
         o_full = torch.zeros(B, P * n, Dp, device=xn.device, dtype=BF16)
         # (q and o with the last shard's padding rows: the standard processor attends them too, the resample one
         # leaves them alone; the keys are the N real rows)
         attn.processor.attend_heads(attn, full[..., :Dp], full[:, :N, Dp:2 * Dp], full[:, :N, 2 * Dp:], T,
-                                    self.rope_full, m, plan, fused, pk, pv, float(prev_clip_weight) if prev else 0.0,
-                                    o_full)
+                                    self.rope_full, m, plan, fused, pk, pv, w, o_full, **kw)
         del full
         return heads_to_rows(self.comm, self.rank, o_full)
+
+    def _prev_heads(self, attn, pn: Optional[torch.Tensor]):
+        """(pk, pv): the previous window's K / V of this shard's rows pn (projected here, pre-norm, bf16) -> the N
+        real rows of the head group; (None, None) without pn."""
+        if pn is None:
+            return None, None
+        Dp, N = pn.shape[-1] // self.comm.P, self.sh.N
+        pkv = qkv_to_heads(self.comm, self.rank, _kv(attn, pn), parts=2)
+        return pkv[:, :N, :Dp], pkv[:, :N, Dp:]
+
+    def _attend_fp8(self, attn, x: torch.Tensor, project: bool, text_len: int, rope, pn, w: float, mx_out: bool):
+        """The standard processor's fp8 attention under the split.  q and k cross the first exchange as the e4m3
+        operands the kernel wants (quantised on the shard, vp_qkv_heads_pack_fp8: 4 B per element on the wire instead
+        of 6) in the layout [P, n, B, 4 Dp], so the received buffer is q8 / k8 / v of every row as it stands
+        (`heads_fp8_views`), the attention writes straight into the second exchange's send buffer [P, n, B, Dp], and
+        with the fp8 output projection the received heads are gathered by the quantiser (vp_mx_quantize_heads_bf16):
+        no re-layout copy on either side of either exchange.  x: the shard's xn (project) or its pre-norm qkv.  The
+        previous window's K | V keep the bf16 exchange and are quantised on the head group."""
+        comm, rank, sh = self.comm, self.rank, self.sh
+        P, N, T = comm.P, sh.N, sh.T
+        qkv = _qkv(attn, x, None) if project else x
+        B, n, D = qkv.shape[0], qkv.shape[1], qkv.shape[2] // 3
+        Dp = D // P
+        q_exp, k_exp = attn.fp8_qk_exp
+        send = K.qkv_heads_pack_fp8(qkv, attn.heads, P, text_len, attn.norm_q, attn.norm_k, rope,
+                                    attn.scale * K.LOG2E * 2.0 ** q_exp, 2.0 ** k_exp)
+        del qkv, x
+        q8, k8, v = heads_fp8_views(comm.all_to_all(rank, send), N)
+        del send
+        o_send = torch.zeros(P, n, B, Dp, device=q8.device, dtype=BF16)
+        attn.processor.attend_heads_fp8(attn, q8, k8, v, T, self.rope_full, lambda: self._prev_heads(attn, pn) + (w,),
+                                        o_send.view(P * n, B, Dp).transpose(0, 1))
+        del q8, k8, v
+        recv = comm.all_to_all(rank, o_send)                                          # [P(head group), n, B, Dp]
+        if mx_out:
+            return K.mx_quantize_heads(recv, out=K.MXTensor(B * n, D, recv.device, zero=False))
+        return recv.permute(2, 1, 0, 3).reshape(B, n, D)
 
     def gather_rows(self, proj: torch.Tensor, B: int) -> torch.Tensor:
         """The head's exchange: this rank's proj_out rows [B * nv, pc] -> every video row [B * Nv, pc], on every
@@ -241,11 +308,21 @@ def heads_to_rows(comm, rank: int, o_full: torch.Tensor) -> torch.Tensor:
     return recv.permute(1, 2, 0, 3).reshape(B, n, P * Dp)
 
 
-def _check(model, fp8_attrs=("ff_mx", "qkv_mx", "out_mx")):
+def heads_fp8_views(recv: torch.Tensor, N: int):
+    """The fp8 exchange's receive buffer uint8 [P, n, B, 4 Dp] (row shard, row, batch; per row q e4m3 | k e4m3 |
+    v bf16 of this rank's head group, kernels.qkv_heads_pack_fp8) as the attention's operands, without a copy:
+    q8 uint8 [B, P n, Dp] (every row, the last shard's padding included), k8 uint8 [B, N, Dp] and v bf16 [B, N, Dp]
+    (the N real rows) — views with a row stride of B * 4 Dp bytes and a batch stride of 4 Dp bytes."""
+    P, n, B, W = recv.shape
+    if recv.dtype != torch.uint8 or not recv.is_contiguous() or W % 256:
+        raise ValueError(f"recv must be contiguous uint8 [P, n, B, 4 Dp] with whole heads, got {tuple(recv.shape)}")
+    Dp = W // 4
+    rows = recv.view(P * n, B, W).transpose(0, 1)
+    return rows[..., :Dp], rows[:, :N, Dp:2 * Dp], rows[:, :N, 2 * Dp:].view(BF16)
+
+
+def _check(model):
     for blk in model.transformer_blocks:
-        if any(getattr(blk, a, None) is not None for a in fp8_attrs) or \
-                getattr(blk.attn1, "fp8_qk_exp", None) is not None:
-            raise NotImplementedError("the head-parallel split runs the bf16 path (disable the fp8 modes)")
         if type(blk.attn1.processor) not in (CogVideoXAttnProcessor2_0, CogVideoXAttnProcessor2_0_resample):
             raise NotImplementedError("the head-parallel split runs the standard and ID-resample processors")
 
