@@ -33,7 +33,7 @@ extern "C" {
 #define VP_ERR_UNSUPPORTED 1001
 
 /* ABI version: bump when any struct layout or signature below changes. */
-#define VP_ABI_VERSION 25
+#define VP_ABI_VERSION 26
 int vp_abi_version(void);
 /* "<sha256 of sources + flags>:<sha256 of the compiler version>" of the build (no reference counterpart) */
 const char* vp_build_digest(void);
@@ -452,6 +452,33 @@ int vp_mask_scale_rows_bf16(const void* x_in, int64_t ld_in, int64_t bs_in, void
                             int32_t B, int32_t Ntok, int32_t D, const uint8_t* tok_mask, int64_t mask_bstride,
                             float scale, const int32_t* dst_rows, void* stream);
 
+/* The training backward of the closed-form null keys (ABI 26).  A null key has value 0, so dP = 0 and its
+ * dS = -P D; its share of the query gradient is
+ *   dq[b, n, h] += -scale * delta[b, h, n] * G,   G = sum over the null keys j of exp2(c q.k_j - lse[b, h, n]) k_j
+ * (c = scale * log2 e), summed over the grid like the mass: G's dims 0-15 = sum_t w_t(t) K_t(t), 16-39 =
+ * sum_y w_y(y) K_y(y), 40-63 = sum_x w_x(x) K_x(x), where w_a(p) is the probability mass of the null cells with
+ * coordinate p on axis a (two difference arrays over the segment records per query), plus
+ * count * exp2(c q.beta - lse) beta for the null text rows.  The gradient towards the null keys themselves reaches
+ * only the norm_k bias and is not built: the caller keeps that bias frozen.
+ * q, beta, the tables, mask, segs, meta: exactly vp_null_key_mass's; lse / delta fp32 [B, H, N] (the forward's
+ * vp_attn_desc.lse, which includes l_extra, and vp_attn_bwd_desc.delta); dq bf16 [B, N, H*64]-strided, read, added to
+ * in fp32 and rounded once by the one thread that owns the (b, h, n) row; a batch row without a null key is left
+ * untouched.  vp_null_key_mass_bwd_lds_bytes <= 160 KiB. */
+int64_t vp_null_key_mass_bwd_lds_bytes(int32_t F, int32_t Hh, int32_t Ww);
+int vp_null_key_mass_bwd(const void* q, int64_t q_sb, int64_t q_sn, int32_t B, int32_t H, int32_t N, int32_t T,
+                         int32_t F, int32_t Hh, int32_t Ww, const void* beta, const float* cos_t, const float* sin_t,
+                         const float* cos_y, const float* sin_y, const float* cos_x, const float* sin_x,
+                         const uint8_t* mask, int64_t mask_bstride, const void* segs, const int32_t* meta, float scale,
+                         const float* lse, const float* delta, void* dq, int64_t dq_sb, int64_t dq_sn, void* stream);
+
+/* y[b, n, :] = rnd(y[b, n, :] + x[b, rows[b * Ntok + n], :]) for the rows n with tok_mask[b, n] != 0 and
+ * 0 <= rows[b * Ntok + n] < x_rows; every other row of y is left as it is.  The gradient of a compact row copy
+ * (vp_mask_scale_rows_bf16 / vp_head_norm_rope_bf16 with dst_rows) added back onto its source rows: one writer per
+ * row, no atomics.  x must not overlap the rows of y that are written. */
+int vp_gather_add_rows_bf16(const void* x, int64_t ld_x, int64_t bs_x, int32_t x_rows, void* y, int64_t ld_y,
+                            int64_t bs_y, int32_t B, int32_t Ntok, int32_t D, const uint8_t* tok_mask,
+                            int64_t mask_bstride, const int32_t* rows, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * Output head norms — norm_final (cogvideox_transformer_3d.py:617-620) then AdaLayerNorm(chunk_dim=1)
  * (DF/models/normalization.py:73-85, shift|scale order): for video rows only,
@@ -655,9 +682,15 @@ int vp_denormalize_bf16(const void* x, void* y, int64_t n, void* stream);
 
 
 /* ---- backward (train/train_cogvideox_inpainting_i2v_video.py:1892 accelerator.backward) ---- */
-/* Flash-attention backward of vp_attention_fwd_bf16 (one K/V segment, no blend): with P = exp2(c q.k - lse),
- * c = scale * log2 e, lse from the forward's vp_attn_desc.lse: dQ = scale dS K, dK = scale dS^T Q, dV = P^T dO with
- * dS = P (dO V^T - rowsum(dO O)).  delta: fp32 workspace [B, H, Nq].  All tensors [B, N, H*64]-strided bf16. */
+/* Flash-attention backward of vp_attention_fwd_bf16 (no blend): with P = exp2(c q.k - lse), c = scale * log2 e, lse
+ * from the forward's vp_attn_desc.lse: dQ = scale dS K, dK = scale dS^T Q, dV = P^T dO with
+ * dS = P (dO V^T - rowsum(dO O)).  delta: fp32 [B, H, Nq], written here (D = rowsum(dO O)) and left to the caller
+ * (vp_null_key_mass_bwd reads it).  All tensors [B, N, H*64]-strided bf16.
+ * The keys are one buffer of Nk rows; a forward over two segments is differentiated over their concatenation.
+ * k_len (ABI 26): device int32 [B] or NULL — batch row b has min(k_len[b], Nk) keys (the resample processor's compact
+ * second segment behind the N own keys, vp_attn_desc.k2_len): K / V rows at or past the length are never read, and
+ * rows at or past it of dK / dV are written as zeros.  lse may hold more mass than these keys give (the closed-form
+ * null keys, vp_attn_desc.l_extra).  The default kernels only (VP_ATTN_BWD_VARIANT=0 with k_len: VP_ERR_UNSUPPORTED). */
 typedef struct vp_attn_bwd_desc {
   int32_t B, H, Nq, Nk, head_dim, pad0;
   const void* Q;
@@ -680,6 +713,7 @@ typedef struct vp_attn_bwd_desc {
   int64_t dv_sb, dv_sn;
   float scale;
   int32_t pad1;
+  const int32_t* k_len;
 } vp_attn_bwd_desc;
 int vp_attention_bwd_bf16(const vp_attn_bwd_desc* d, void* stream);
 /* The same with a workspace for the grid-tail split (ABI 19): the blocks of each kernel's last partial round run as

@@ -11,7 +11,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VP_HIP_LIB", os.path.join(_HERE, "_lib", "libvp_hip.so"))
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 vp = C.c_void_p
 i32 = C.c_int32
@@ -96,7 +96,7 @@ class AttnBwdDesc(C.Structure):
                 ("V", vp), ("v_sb", i64), ("v_sn", i64), ("O", vp), ("o_sb", i64), ("o_sn", i64),
                 ("dO", vp), ("do_sb", i64), ("do_sn", i64), ("lse", vp), ("delta", vp),
                 ("dQ", vp), ("dq_sb", i64), ("dq_sn", i64), ("dK", vp), ("dk_sb", i64), ("dk_sn", i64),
-                ("dV", vp), ("dv_sb", i64), ("dv_sn", i64), ("scale", f32), ("pad1", i32)]
+                ("dV", vp), ("dv_sb", i64), ("dv_sn", i64), ("scale", f32), ("pad1", i32), ("k_len", vp)]
 
 
 MT_CHUNK = 16384  # VP_MT_CHUNK: elements of one multi-tensor chunk (one workgroup's work)
@@ -166,6 +166,10 @@ _SIGS = {
     "vp_null_key_mass_lds_bytes": (i64, [i32, i32, i32]),
     "vp_null_key_mass": (i32, [vp, i64, i64, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64,
                                vp, vp, f32, vp, vp]),
+    "vp_null_key_mass_bwd_lds_bytes": (i64, [i32, i32, i32]),
+    "vp_null_key_mass_bwd": (i32, [vp, i64, i64, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp,
+                                   i64, vp, vp, f32, vp, vp, vp, i64, i64, vp]),
+    "vp_gather_add_rows_bf16": (i32, [vp, i64, i64, i32, vp, i64, i64, i32, i32, i32, vp, i64, vp, vp]),
     "vp_final_norm_bf16": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, f32, vp, i64, vp]),
     "vp_linear_small_bf16": (i32, [vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp]),
     "vp_linear_small_batched_bf16": (i32, [vp, i64, vp, i32, vp, i64, i64, i32, i32, i32, i32, i32, vp]),

@@ -436,12 +436,17 @@ class CogVideoXAttnProcessor2_0_resample(CogVideoXAttnProcessor2_0):
 
     def attend(self, attn, x: torch.Tensor, text_len: int, image_rotary_emb=None, prev_hidden_states=None,
                prev_clip_weight=None, resample_mask=None, prev_resample_mask=None,
-               qkv: Optional[torch.Tensor] = None) -> torch.Tensor:
+               qkv: Optional[torch.Tensor] = None, keep: Optional[dict] = None) -> torch.Tensor:
+        """keep: a training forward's dict (autograd._BlockFn with the closed-form resample backward on): receives
+        the attention output "o" and the statistics "lse" of the two-segment launch (the null-key mass included) —
+        the same launches as without it; window 0's bf16 closed-form plan only."""
         B, Ntok, D = x.shape
         rope = _rope_dev(image_rotary_emb, x.device)
         prev = prev_hidden_states is not None and prev_clip_weight is not None and prev_clip_weight > 0.0
         m, plan, fused = self.head_plan(attn, text_len, rope, prev, resample_mask, prev_resample_mask)
         fp8 = self.fp8_exponents(attn, plan)
+        if keep is not None and (prev or qkv is not None or fp8 is not None or plan[3] is None):
+            raise ValueError("keep: window 0's bf16 attention with the null keys in closed form only")
         # (the block may hand over an fp8 projection; the fp8 form quantises from the pre-norm q / k: no fused
         # epilogue in either case)
         fused = fused and qkv is None and fp8 is None
@@ -449,8 +454,12 @@ class CogVideoXAttnProcessor2_0_resample(CogVideoXAttnProcessor2_0):
             qkv = _qkv(attn, x, (text_len, rope) if fused else None)
         pk, pv, w = _prev_kv(attn, prev_hidden_states, prev_clip_weight)
         o = augmented_rows((attn.to_out[0],), B, Ntok, D, x.device)
+        lse = None
+        if keep is not None:
+            keep["o"], keep["lse"] = o, torch.empty(B, attn.heads, Ntok, device=x.device, dtype=torch.float32)
+            lse = keep["lse"]
         return self.attend_heads(attn, qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:], text_len, rope, m, plan,
-                                 fused, pk, pv, w, o, fp8=fp8)
+                                 fused, pk, pv, w, o, fp8=fp8, lse=lse)
 
     def head_plan(self, attn, text_len: int, rope, prev: bool, resample_mask=None, prev_resample_mask=None):
         """(m, plan, fused): the token mask of the call (the previous window's when it blends that window in) as
@@ -484,19 +493,29 @@ class CogVideoXAttnProcessor2_0_resample(CogVideoXAttnProcessor2_0):
         dst = cnt = segments = axes = None
         grid = getattr(rope, "grid", None)
         if _sw("VP_RESAMPLE_PARTITION", "1") != "0":
-            if (grid is not None and _sw("VP_RESAMPLE_NULLMASS", "1") != "0"
-                    and attn.norm_k.bias is not None and attn.norm_k.bias.dtype == BF16
-                    and K.null_key_mass_supported(grid)):
-                axes = K.rope_axis_tables(rope, grid)
+            axes = CogVideoXAttnProcessor2_0_resample.closed_form_axes(attn, rope)
             dst, cnt, segments = _mask_plan(m, text_len, grid if axes is not None else None)
         return dst, cnt, segments, axes
 
+    @staticmethod
+    def closed_form_axes(attn, rope):
+        """The per-axis RoPE tables when `plan` sums the null keys in closed form for this rope (the grid known and
+        taken by vp_null_key_mass, the table separable, a bf16 norm_k bias, neither A/B switch at 0), else None.
+        Host-side only: no launch, the mask plan is not built."""
+        grid = getattr(rope, "grid", None)
+        if (_sw("VP_RESAMPLE_PARTITION", "1") != "0" and grid is not None and _sw("VP_RESAMPLE_NULLMASS", "1") != "0"
+                and attn.norm_k.bias is not None and attn.norm_k.bias.dtype == BF16
+                and K.null_key_mass_supported(grid)):
+            return K.rope_axis_tables(rope, grid)
+        return None
+
     def attend_heads(self, attn, q, k, v, text_len: int, rope, m, plan, fused: bool, pk=None, pv=None,
-                     w: float = 0.0, o=None, fp8=None) -> torch.Tensor:
+                     w: float = 0.0, o=None, fp8=None, lse=None) -> torch.Tensor:
         """The processor's attention on [B, N, h*64] views of every head (or of one head group: the Ulysses split,
         videopainter_amd/ulysses.py) — q / k normed + rotated already when `fused`, pre-norm otherwise; pk / pv: the
         previous window's pre-norm K / V projections (prev-clip blend with weight w), or None.  fp8: `fp8_exponents`
-        (needs pre-norm q / k and the closed-form plan)."""
+        (needs pre-norm q / k and the closed-form plan).  lse: fp32 [B, h, N] receiving the bf16 launch's softmax
+        statistics (with the closed-form plan they include the null-key mass)."""
         B, Ntok, D = k.shape
         H = D // 64
         # (the Ulysses split's padded last shard: q / o rows past the N the mask covers are padding, left alone)
@@ -558,8 +577,8 @@ class CogVideoXAttnProcessor2_0_resample(CogVideoXAttnProcessor2_0):
         if axes is not None:
             lx = K.null_key_mass(q, H, text_len, grid, attn.norm_k.bias, axes, m, segments, attn.scale)
             K.attention(q, k, v, o, H, k2=k2, v2=v2, scale=attn.scale, bounded_scores=bounded_scores(attn),
-                        k2_len=cnt, l_extra=lx)
+                        k2_len=cnt, l_extra=lx, lse=lse)
         else:
             K.attention(q, k, v, o, H, k2=k2, v2=v2, scale=attn.scale, bounded_scores=bounded_scores(attn),
-                        k2_full=cnt)
+                        k2_full=cnt, lse=lse)
         return o

@@ -33,6 +33,15 @@ flash backward over all 2N keys and routes the second segment's gradients back t
 to k / v, the null keys' to the norm_k affine) — and trainable LoRA factors on to_q / to_k / to_v / to_out.0
 (`transformer.add_adapter`, lora.py) run unfused like PEFT's, on K-augmented operands (lora.AugmentedProjection):
 dA = dT^T x and dB = s dy^T T from the augmented projection's gradients (dT = s dy B, T = x A^T).
+With `enable_closed_form_resample_backward` (opt-in, norm_k.bias frozen) the backward differentiates the forward's
+compact plan instead: the forward keeps o / lse of its two-segment launch, and with c = scale log2 e,
+lse_i = log2(sum_real 2^s_ij + 2^lx_i) (lx: the null keys' closed-form mass), D_i = rowsum(dO_i o O_i):
+  real keys (K's N rows + the cnt[b] masked rows behind them, attention_bwd's k_len): dS_ij = P_ij (dP_ij - D_i);
+  null keys (V = 0, so dP = 0): dS_ij = -P_ij D_i, which reaches only dq — dq_i += -scale D_i G_i with
+  G_i = sum_{j null} 2^(c q_i.k_j - lse_i) k_j, summed over the grid (kernels.null_key_mass_bwd) — and the norm_k
+  bias, which is not built;
+  dK_normed[n] = dK1[n] + dK2c[dst[n]] and dV[n] += dV2c[dst[n]] on the masked rows (kernels.gather_add_rows: a
+  masked row's K2 / V2 row is the same function of the same k / v row), then ONE (LN + RoPE)' for k.
 Out of scope for the backward (NotImplementedError): the fp8 modes, the previous-clip blend (windows > 0) and
 `return_hidden_states` — inference-only in the reference.
 """
@@ -188,7 +197,37 @@ def _small_linear_bwd(G: _Grads, lin, x_in: torch.Tensor, dy: torch.Tensor) -> t
 # the block
 # ------------------------------------------------------------------------------------------------------------------
 
-def _check_block_trainable_path(block, resample_mask=None) -> None:
+def closed_form_resample(a) -> bool:
+    """The attention runs the resample processor and opted in to its closed-form backward
+    (CogVideoXBlock.enable_closed_form_resample_backward)."""
+    return (isinstance(a.processor, CogVideoXAttnProcessor2_0_resample)
+            and bool(getattr(a, "closed_form_resample_backward", False)))
+
+
+def _check_closed_form_plan(a, rope) -> None:
+    """ValueError naming what keeps the forward's plan from being the closed-form one: the opt-in does not fall back
+    to the explicit form.  Host-side only (no launch: the forward's trace stays the inference plan's)."""
+    grid = getattr(rope, "grid", None)
+    if grid is None:
+        raise ValueError("the closed-form resample backward needs the video grid on the rope tables "
+                         "(attention_processor._rope_dev(rope, device, grid)); the model's training forward sets it")
+    if a.processor.closed_form_axes(a, rope) is None:
+        raise ValueError("the closed-form resample backward needs the closed-form null-key plan: a separable RoPE "
+                         "table, a grid vp_null_key_mass takes, a bf16 norm_k bias, and VP_RESAMPLE_PARTITION / "
+                         "VP_RESAMPLE_NULLMASS not 0")
+    if not K.null_key_mass_bwd_supported(grid):
+        raise ValueError(f"the closed-form resample backward does not take the grid {tuple(grid)}")
+
+
+def _closed_form_plan(a, T: int, rope, resample_mask):
+    """(m, dst_rows, counts, segments, axes, grid) of the forward's compact plan (cached per mask: no launch when
+    the forward built it)."""
+    _check_closed_form_plan(a, rope)
+    m, (dst, cnt, segments, axes), _ = a.processor.head_plan(a, T, rope, False, resample_mask)
+    return m, dst, cnt, segments, axes, rope.grid
+
+
+def _check_block_trainable_path(block, resample_mask=None, rope=None) -> None:
     a = block.attn1
     if (block.ff_mx is not None or block.qkv_mx is not None or getattr(block, "out_mx", None) is not None
             or getattr(a, "fp8_qk_exp", None) is not None):
@@ -196,6 +235,12 @@ def _check_block_trainable_path(block, resample_mask=None) -> None:
     if isinstance(a.processor, CogVideoXAttnProcessor2_0_resample):
         if resample_mask is None:
             raise ValueError("the resample processor needs resample_mask (id_pool_resample needs masks)")
+        if closed_form_resample(a):
+            # the null keys' dS reaches only the norm_k bias (the mask cancels the path into k): not built
+            if a.norm_k.bias is not None and a.norm_k.bias.requires_grad:
+                raise NotImplementedError("the closed-form resample backward builds no norm_k bias gradient: freeze "
+                                          "norm_k.bias or disable it (enable_closed_form_resample_backward(False))")
+            _check_closed_form_plan(a, rope)
     elif resample_mask is not None:
         # (such a block's forward ignores the mask, while the backward would differentiate the resample attention)
         raise NotImplementedError("resample_mask on a block without the resample processor has no backward")
@@ -229,6 +274,28 @@ def _resample_attention(a, xn: torch.Tensor, T: int, rope, resample_mask: torch.
     keep.update(qn=qn, kc=kc, vc=vc, o=o, lse=lse)
 
 
+def _resample_operands(a, xn: torch.Tensor, T: int, rope, resample_mask: torch.Tensor, keep: dict) -> None:
+    """The closed-form backward's operands, without an attention launch (its o / lse were kept by the forward): the
+    pre-norm projections "qkv", the normed queries "qn", and one key / value buffer each, "kc" / "vc" [B, 2N, D] —
+    K / V in rows [0, N), the forward's compact second segment behind them (the masked rows of K / V in partition
+    order, `cnt[b]` of them; the rows past N + cnt[b] are never read: attention_bwd's k_len) — and the plan "rplan"."""
+    B, Ntok, D = xn.shape
+    H, dev, nq, nk = a.heads, xn.device, a.norm_q, a.norm_k
+    rplan = m, dst, _, _, _, _ = _closed_form_plan(a, T, rope, resample_mask)
+    qkv = _qkv(a, xn, None, keep)
+    q, k, v = qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:]
+    qn = torch.empty(B, Ntok, D, device=dev, dtype=BF16)
+    kc = torch.empty(B, 2 * Ntok, D, device=dev, dtype=BF16)
+    vc = torch.empty(B, 2 * Ntok, D, device=dev, dtype=BF16)
+    K.head_norm_rope(q, qn, H, T, nq.weight, nq.bias, nq.eps, rope)
+    K.head_norm_rope(k, kc[:, :Ntok], H, T, nk.weight, nk.bias, nk.eps, rope)
+    # LN(1 . k) + RoPE of a masked row is K's row, and V2 = v there: compact copies, as the fused forward makes them
+    K.mask_scale_rows(kc[:, :Ntok], kc[:, Ntok:], m, 1.0, dst_rows=dst)
+    vc[:, :Ntok].copy_(v)
+    K.mask_scale_rows(v, vc[:, Ntok:], m, 1.0, dst_rows=dst)
+    keep.update(qn=qn, kc=kc, vc=vc, rplan=rplan)
+
+
 def _block_front(block, x: torch.Tensor, T: int, temb: torch.Tensor, rope, resample_mask, attn_saved=None,
                  with_h: bool = False) -> dict:
     """The backward's recompute: forward_joint's stages (CogVideoXBlock) up to the FF front with a keep-all dict,
@@ -238,7 +305,10 @@ def _block_front(block, x: torch.Tensor, T: int, temb: torch.Tensor, rope, resam
     keep = dict(level="all", train=True)
     keep["mod1"], keep["mod2"] = mod1, mod2 = block.norm1.modulation(temb), block.norm2.modulation(temb)
     xn, _, _ = block._attn_input(x, T, mod1, keep=keep)
-    if resample_mask is not None:
+    if resample_mask is not None and attn_saved is not None:  # (kept by the closed-form forward only)
+        keep["o"], keep["lse"] = attn_saved
+        _resample_operands(block.attn1, xn, T, rope, resample_mask, keep)
+    elif resample_mask is not None:
         _resample_attention(block.attn1, xn, T, rope, resample_mask, keep)
     elif attn_saved is not None:
         keep["o"], keep["lse"] = attn_saved
@@ -279,6 +349,7 @@ def block_backward(block, x: torch.Tensor, T: int, temb: torch.Tensor, rope, inj
     resample = resample_mask is not None
     v = qkv[..., 2 * D:]
     kc = vc = None
+    rplan = f.pop("rplan", None)  # the closed-form plan (_resample_operands), else the explicit 2N-key form
     if resample:  # qkv: the pre-norm projections
         qn, kc, vc = f.pop("qn"), f.pop("kc"), f.pop("vc")
         qpre, kpre = qkv[..., :D], qkv[..., D:2 * D]
@@ -354,7 +425,24 @@ def block_backward(block, x: torch.Tensor, T: int, temb: torch.Tensor, rope, inj
     del dao, o_aug
     dqkv = torch.empty(B, Ntok, 3 * D, device=dev, dtype=BF16)
     dk2 = None
-    if resample:
+    kgrad = dqkv[..., D:2 * D]  # d (normed + rotated K), the k norm backward's input
+    if rplan is not None:
+        # the closed-form plan: keys = K's N rows + the cnt[b] masked rows behind them (k_len, on the device); the
+        # null keys (value 0: dS = -P D) reach only dq, in closed form; a masked row's K2 / V2 row is the same
+        # function of the same k / v row as its K / V row, so their gradients add up before the one norm backward
+        m, dst, cnt, segments, axes, grid = rplan
+        dkc = torch.empty(B, 2 * Ntok, D, device=dev, dtype=BF16)
+        dvc = torch.empty(B, 2 * Ntok, D, device=dev, dtype=BF16)
+        delta = torch.empty(B, H, Ntok, device=dev, dtype=F32)
+        K.attention_bwd(qn, kc, vc, o, do, lse, H, scale=a.scale, dq=dqkv[..., :D], dk=dkc, dv=dvc,
+                        k_len=cnt + Ntok, delta=delta)
+        K.null_key_mass_bwd(qn, H, T, grid, a.norm_k.bias, axes, m, segments, a.scale, lse, delta, dqkv[..., :D])
+        K.gather_add_rows(dkc[:, Ntok:], dkc[:, :Ntok], m, dst)
+        K.gather_add_rows(dvc[:, Ntok:], dvc[:, :Ntok], m, dst)
+        dqkv[..., 2 * D:].copy_(dvc[:, :Ntok])
+        kgrad = dkc[:, :Ntok]
+        del dvc, kc, vc, delta
+    elif resample:
         dkc = torch.empty(B, 2 * Ntok, D, device=dev, dtype=BF16)
         dvc = torch.empty(B, 2 * Ntok, D, device=dev, dtype=BF16)
         K.attention_bwd(qn, kc, vc, o, do, lse, H, scale=a.scale, dq=dqkv[..., :D], dk=dkc, dv=dvc)
@@ -375,7 +463,8 @@ def block_backward(block, x: torch.Tensor, T: int, temb: torch.Tensor, rope, inj
         dlnq = (torch.zeros(64, device=dev, dtype=F32), torch.zeros(64, device=dev, dtype=F32))
         dlnk = (torch.zeros(64, device=dev, dtype=F32), torch.zeros(64, device=dev, dtype=F32))
     K.head_norm_rope_bwd(qpre, dqkv[..., :D], dqkv[..., :D], H, T, a.norm_q, rope, dlnq)
-    K.head_norm_rope_bwd(kpre, dqkv[..., D:2 * D], dqkv[..., D:2 * D], H, T, a.norm_k, rope, dlnk)
+    K.head_norm_rope_bwd(kpre, kgrad, dqkv[..., D:2 * D], H, T, a.norm_k, rope, dlnk)
+    del kgrad
     if dk2 is not None:
         # K2 = LN(mask . k) + RoPE: (LN + RoPE)' at the masked input, then x mask (null rows: LN of a zero row,
         # whose input gradient the mask cancels; their d beta stays in dlnk)
@@ -462,7 +551,11 @@ class _BlockFn(torch.autograd.Function):
         train = any(p.requires_grad for p in params) or temb.requires_grad
         qaug = AugmentedProjection.of((a.to_q, a.to_k, a.to_v)) if train else None
         keep = mod1 = mod2 = None
-        if resample_mask is None:
+        if resample_mask is not None:
+            # (the explicit 2N-key backward recomputes its attention; the closed-form one keeps the forward's)
+            if closed_form_resample(a):
+                keep = dict(level="attention", train=train)
+        else:
             if SAVE_ACTIVATIONS and _room_for(x, block.ff.net[0].proj.weight.shape[0], train,
                                               qaug.R if qaug is not None else 0):
                 keep = dict(level="all", train=train)
@@ -498,7 +591,7 @@ def block_apply(block, x: torch.Tensor, T: int, temb: torch.Tensor, rope, inject
                 resample_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Differentiable `block.forward_joint` (gradient-checkpointed).  resample_mask: the uint8 token mask of the
     blocks' resample processor (window 0 of VideoPainterID training)."""
-    _check_block_trainable_path(block, resample_mask)
+    _check_block_trainable_path(block, resample_mask, rope)
     params = [p for p in block.parameters()]
     return _BlockFn.apply(block, T, rope, inject_mask, resample_mask, x, temb, inject, *params)
 

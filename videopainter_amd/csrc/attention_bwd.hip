@@ -221,7 +221,11 @@ __global__ __launch_bounds__(256) void bwd_delta_kernel(const vp_attn_bwd_desc d
 #ifndef VP_DQ_WAVES
 #define VP_DQ_WAVES 2  // waves per SIMD the dQ kernel is register-budgeted for (A/B: -DVP_DQ_WAVES=3)
 #endif
-template <int V>
+// KL (V = 1 only): batch row b has nk = min(d.k_len[b], d.Nk) keys (the resample processor's compact second
+// segment); the tile count, the peeled partial tile and a tail piece's tile range come from nk, read once into a
+// scalar register.  A piece whose range is empty (the host plans the pieces from Nk) stages nothing and leaves a zero
+// record.  KL = false compiles to the code without the field.
+template <int V, bool KL = false>
 __global__ __launch_bounds__(BW * 64, VP_DQ_WAVES) void bwd_dq_kernel(const vp_attn_bwd_desc d, const BwdSplit sp) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, hl = lane >> 5;
@@ -235,6 +239,7 @@ __global__ __launch_bounds__(BW * 64, VP_DQ_WAVES) void bwd_dq_kernel(const vp_a
   const int b = bh / d.H, h = bh - b * d.H;
   const int q = qb * BW * 32 + wave * 32 + (lane & 31);
   const int qc = min(q, d.Nq - 1);
+  const int nk = KL ? max(0, min(__builtin_amdgcn_readfirstlane(d.k_len[b]), d.Nk)) : d.Nk;
   const float c = d.scale * 1.4426950408889634f;
   // B operands: Q^T pre-scaled by c (the forward's rounding) and dO^T, from this lane's query row
   bf16x8 qf[4], gf[4];
@@ -256,17 +261,17 @@ __global__ __launch_bounds__(BW * 64, VP_DQ_WAVES) void bwd_dq_kernel(const vp_a
   const TrAddr ta = tr_addr<V>(lane);
   f32x16 dqt[2] = {zero16(), zero16()};
   const bool active = qb * BW * 32 + wave * 32 < d.Nq;  // wave-uniform
-  const int ntiles = (d.Nk + BT - 1) / BT;
+  const int ntiles = (nk + BT - 1) / BT;
   const int tbeg = piece ? ntiles * split / sp.nsplit : 0, tend = piece ? ntiles * (split + 1) / sp.nsplit : ntiles;
   const TileOffs ko = tile_offs(d.k_sn, wave, lane), vo = tile_offs(d.v_sn, wave, lane);
   auto issue = [&](int ti) {
     char* st = smem + (ti & 1) * STAGE;
     if (V) {
-      stage_tile_fast(kb, d.k_sn, ti * BT, d.Nk, st, wave, lane, ko);
-      stage_tile_fast(vb, d.v_sn, ti * BT, d.Nk, st + TILE, wave, lane, vo);
+      stage_tile_fast(kb, d.k_sn, ti * BT, nk, st, wave, lane, ko);
+      stage_tile_fast(vb, d.v_sn, ti * BT, nk, st + TILE, wave, lane, vo);
     } else {
-      stage_tile<V>(kb, d.k_sn, ti * BT, d.Nk, st, wave, lane);
-      stage_tile<V>(vb, d.v_sn, ti * BT, d.Nk, st + TILE, wave, lane);
+      stage_tile<V>(kb, d.k_sn, ti * BT, nk, st, wave, lane);
+      stage_tile<V>(vb, d.v_sn, ti * BT, nk, st + TILE, wave, lane);
     }
   };
   // one 32-key half of a staged tile.  The accumulators start at -lse / -D (C-init), so P = exp2(S) and dS = P * dP
@@ -313,14 +318,16 @@ __global__ __launch_bounds__(BW * 64, VP_DQ_WAVES) void bwd_dq_kernel(const vp_a
       for (int dh = 0; dh < 2; ++dh)
         dqt[dh] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(read_tr(Kt, kh * 2 + j, ta, dh), pf[j], dqt[dh], 0, 0, 0);
   };
-  issue(tbeg);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
+  if (!KL || tbeg < tend) {  // (block-uniform; KL: an empty tile range stages nothing)
+    issue(tbeg);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
   if (V == 0) {
     for (int ti = 0; ti < ntiles; ++ti) {
       if (ti + 1 < ntiles) issue(ti + 1);
       const char* Kt = smem + (ti & 1) * STAGE;
-      const int lim = d.Nk - ti * BT;
+      const int lim = nk - ti * BT;
 #pragma unroll
       for (int kh = 0; kh < 2; ++kh) {
         if (!active) break;
@@ -330,7 +337,7 @@ __global__ __launch_bounds__(BW * 64, VP_DQ_WAVES) void bwd_dq_kernel(const vp_a
       __syncthreads();
     }
   } else {
-    const int nfull = d.Nk / BT;
+    const int nfull = nk / BT;
     const int fend = min(tend, nfull);
     for (int ti = tbeg; ti < fend; ++ti) {
       if (ti + 1 < tend) issue(ti + 1);
@@ -344,7 +351,7 @@ __global__ __launch_bounds__(BW * 64, VP_DQ_WAVES) void bwd_dq_kernel(const vp_a
     }
     if (nfull < tend && active) {  // the partial last tile (staged by the last loop iteration, or the prologue)
       const char* Kt = smem + (nfull & 1) * STAGE;
-      const int lim = d.Nk - nfull * BT;
+      const int lim = nk - nfull * BT;
       half(Kt, Kt + TILE, 0, true, lim);
       if (lim > 32) half(Kt, Kt + TILE, 1, true, lim);
     }
@@ -362,7 +369,10 @@ __global__ __launch_bounds__(BW * 64, VP_DQ_WAVES) void bwd_dq_kernel(const vp_a
 // skip the compute as one block.
 // (round 6, measured and dropped: 2 waves per SIMD, +4-7 %; the four A fragments of a chain read before its first
 // MFMA and kept live together, +14 % — the extra registers spill at 3 waves per SIMD; profiles/r06_attn_bwd_variants_ab.log)
-template <int V>
+// KL (V = 1 only): batch row b has nk = min(d.k_len[b], d.Nk) keys.  A workgroup wholly past nk stages and computes
+// nothing, waves past it skip the compute (`active`), and every row in [nk, Nk) of dK / dV is written as zeros (a
+// piece leaves zeros in its record): the caller reads the rows behind a short segment without clearing them first.
+template <int V, bool KL = false>
 __global__ __launch_bounds__(BW * 64, V ? 3 : 2) void bwd_dkdv_kernel(const vp_attn_bwd_desc d, const BwdSplit sp) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, hl = lane >> 5;
@@ -375,7 +385,8 @@ __global__ __launch_bounds__(BW * 64, V ? 3 : 2) void bwd_dkdv_kernel(const vp_a
   const int bh = t / nkb, kb = t - bh * nkb;
   const int b = bh / d.H, h = bh - b * d.H;
   const int key = kb * BW * 32 + wave * 32 + (lane & 31);
-  const int kc = min(key, d.Nk - 1);
+  const int nk = KL ? max(0, min(__builtin_amdgcn_readfirstlane(d.k_len[b]), d.Nk)) : d.Nk;
+  const int kc = KL ? max(min(key, nk - 1), 0) : min(key, d.Nk - 1);
   const float c = d.scale * 1.4426950408889634f;
   // B operands: K^T pre-scaled by c (so S comes out in log2 units) and V^T, from this lane's key row
   bf16x8 kf[4], vf[4];
@@ -401,9 +412,11 @@ __global__ __launch_bounds__(BW * 64, V ? 3 : 2) void bwd_dkdv_kernel(const vp_a
   const float* stat_row = wave == 0 ? lse_row : d_row;  // (BT = 64: wave 0 holds the lse, wave 1 the D; scalar)
   const TrAddr ta = tr_addr<V>(lane);
   f32x16 dkt[2] = {zero16(), zero16()}, dvt[2] = {zero16(), zero16()};
-  const bool active = kb * BW * 32 + wave * 32 < d.Nk;  // wave-uniform
+  const bool active = kb * BW * 32 + wave * 32 < nk;  // wave-uniform
   const int ntiles = (d.Nq + BT - 1) / BT;
-  const int tbeg = piece ? ntiles * split / sp.nsplit : 0, tend = piece ? ntiles * (split + 1) / sp.nsplit : ntiles;
+  const bool past = KL && kb * BW * 32 >= nk;  // block-uniform: no key of this workgroup exists
+  const int tbeg = piece ? ntiles * split / sp.nsplit : 0;
+  const int tend = past ? tbeg : (piece ? ntiles * (split + 1) / sp.nsplit : ntiles);
   // per-query statistics of a tile: thread tid < 64 holds lse, 64 <= tid < 128 D (plain loads, written to LDS after
   // the tile's compute, before the barrier that publishes the stage).  Rows past Nq: lse = +inf, so their S
   // accumulators start at -inf and P = 0 there (no per-score mask); stored negated: they are the C-init of the S / dP
@@ -478,11 +491,13 @@ __global__ __launch_bounds__(BW * 64, V ? 3 : 2) void bwd_dkdv_kernel(const vp_a
         dkt[dh] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(read_tr(Qt, qh * 2 + j, ta, dh), pd[j], dkt[dh], 0, 0, 0);
       }
   };
-  issue(tbeg);
-  load_stat(tbeg);
-  put_stat(tbeg);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
+  if (!past) {
+    issue(tbeg);
+    load_stat(tbeg);
+    put_stat(tbeg);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
   for (int ti = tbeg; ti < tend; ++ti) {
     if (ti + 1 < tend) {
       issue(ti + 1);
@@ -504,6 +519,10 @@ __global__ __launch_bounds__(BW * 64, V ? 3 : 2) void bwd_dkdv_kernel(const vp_a
     if (ti + 1 < tend) put_stat(ti + 1);
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __syncthreads();
+  }
+  if (KL && key >= nk) {  // a row past the length (its lane ran on the clamped last key): zeros
+    dkt[0] = dkt[1] = zero16();
+    dvt[0] = dvt[1] = zero16();
   }
   if (piece) {
     float* rec = sp.ws + ((int64_t)pj * (BW * 32) + wave * 32 + (lane & 31)) * 128;
@@ -568,6 +587,7 @@ int bwd_check(const vp_attn_bwd_desc* d) {
     return VP_ERR_ARG;
   if (d->head_dim != 64) return VP_ERR_UNSUPPORTED;
   if (d->B <= 0 || d->H <= 0 || d->Nq <= 0 || d->Nk <= 0) return VP_ERR_ARG;
+  if (d->k_len != nullptr && ((uintptr_t)d->k_len & 3) != 0) return VP_ERR_ARG;
   const int64_t strides[] = {d->q_sn, d->k_sn, d->v_sn, d->o_sn, d->do_sn, d->dq_sn, d->dk_sn, d->dv_sn,
                              d->q_sb, d->k_sb, d->v_sb, d->o_sb, d->do_sb, d->dq_sb, d->dk_sb, d->dv_sb};
   for (int64_t s : strides)
@@ -599,7 +619,8 @@ void bwd_attr() {
   if (attr) return;
   attr = true;
   for (const void* f : {(const void*)bwd_dq_kernel<0>, (const void*)bwd_dkdv_kernel<0>, (const void*)bwd_dq_kernel<1>,
-                        (const void*)bwd_dkdv_kernel<1>})
+                        (const void*)bwd_dkdv_kernel<1>, (const void*)bwd_dq_kernel<1, true>,
+                        (const void*)bwd_dkdv_kernel<1, true>})
     (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BWD);
 }
 
@@ -654,6 +675,8 @@ extern "C" int vp_attention_bwd_bf16_ws(const vp_attn_bwd_desc* d, void* workspa
   const char* kv = vp_knob(VPK_ATTN_BWD_VARIANT);
   const int var = kv ? atoi(kv) : 1;
   if (var != 0 && var != 1) return VP_ERR_UNSUPPORTED;
+  const bool kl = d->k_len != nullptr;
+  if (kl && var != 1) return VP_ERR_UNSUPPORTED;  // the per-batch key length: the default kernels only
   bwd_attr();
   // the tail split needs the workspace (vp_attention_bwd_workspace_bytes) and the default kernels
   BwdPlan pl = bwd_plan(d, var == 1);
@@ -669,10 +692,12 @@ extern "C" int vp_attention_bwd_bf16_ws(const vp_attn_bwd_desc* d, void* workspa
   // whole blocks first, then the tail pieces, in one grid per kernel; then the pieces' sums
   const BwdSplit spq = {(int)(pl.nq - pl.tq), pl.sq, (float*)workspace};
   const BwdSplit spk = {(int)(pl.nk - pl.tk), pl.sk, (float*)((char*)workspace + pl.wq)};
-  void (*dq)(const vp_attn_bwd_desc, const BwdSplit) = var ? bwd_dq_kernel<1> : bwd_dq_kernel<0>;
+  void (*dq)(const vp_attn_bwd_desc, const BwdSplit) =
+      kl ? bwd_dq_kernel<1, true> : (var ? bwd_dq_kernel<1> : bwd_dq_kernel<0>);
   hipLaunchKernelGGL(dq, dim3((unsigned)(pl.nq - pl.tq + (int64_t)pl.tq * pl.sq)), dim3(BW * 64), LDS_BWD, s, *d, spq);
   VP_CHECK_LAUNCH();
-  void (*dkdv)(const vp_attn_bwd_desc, const BwdSplit) = var ? bwd_dkdv_kernel<1> : bwd_dkdv_kernel<0>;
+  void (*dkdv)(const vp_attn_bwd_desc, const BwdSplit) =
+      kl ? bwd_dkdv_kernel<1, true> : (var ? bwd_dkdv_kernel<1> : bwd_dkdv_kernel<0>);
   hipLaunchKernelGGL(dkdv, dim3((unsigned)(pl.nk - pl.tk + (int64_t)pl.tk * pl.sk)), dim3(BW * 64), LDS_BWD, s, *d,
                      spk);
   VP_CHECK_LAUNCH();

@@ -508,9 +508,12 @@ def gemm_variant_built(variant) -> bool:
 
 def attention_bwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Tensor, do: torch.Tensor,
                   lse: torch.Tensor, heads: int, scale: float = 0.125, dq: Optional[torch.Tensor] = None,
-                  dk: Optional[torch.Tensor] = None, dv: Optional[torch.Tensor] = None):
+                  dk: Optional[torch.Tensor] = None, dv: Optional[torch.Tensor] = None,
+                  k_len: Optional[torch.Tensor] = None, delta: Optional[torch.Tensor] = None):
     """Flash-attention backward (vp_attention_bwd_bf16) of `attention(q, k, v, o, heads, lse=lse)`: returns
-    (dq, dk, dv), each [B, N, heads*64] bf16 (new contiguous tensors unless given)."""
+    (dq, dk, dv), each [B, N, heads*64] bf16 (new contiguous tensors unless given).  k_len: optional int32 [B]
+    (device): batch row b has min(k_len[b], Nk) keys — k / v rows past it are not read, dk / dv rows past it come back
+    zero.  delta: optional fp32 [B, heads, Nq] receiving D = rowsum(dO * O) (null_key_mass_bwd reads it)."""
     for t, n in ((q, "q"), (k, "k"), (v, "v"), (o, "o"), (do, "do")):
         _chk(t, n)
         if t.dim() != 3 or t.stride(-1) != 1 or t.shape[-1] != heads * 64 or t.shape[0] != q.shape[0]:
@@ -528,7 +531,11 @@ def attention_bwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Te
         _chk(t, n)
         if t.shape != (B, L, heads * 64) or t.stride(-1) != 1:
             raise ValueError(f"{n} must be [B, {L}, heads*64]")
-    delta = torch.empty(B, heads, Nq, device=q.device, dtype=torch.float32)
+    if delta is None:
+        delta = torch.empty(B, heads, Nq, device=q.device, dtype=torch.float32)
+    _chk(delta, "delta", torch.float32)
+    if delta.shape != (B, heads, Nq) or not delta.is_contiguous():
+        raise ValueError("delta must be contiguous fp32 [B, heads, Nq]")
     d = N.AttnBwdDesc()
     d.B, d.H, d.Nq, d.Nk, d.head_dim = B, heads, Nq, Nk, 64
     for name, t in (("q", q), ("k", k), ("v", v), ("o", o), ("do", do), ("dq", dq), ("dk", dk), ("dv", dv)):
@@ -537,6 +544,11 @@ def attention_bwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Te
         setattr(d, f"{name}_sb", t.stride(0))
         setattr(d, f"{name}_sn", t.stride(1))
     d.lse, d.delta, d.scale = _p(lse), _p(delta), scale
+    if k_len is not None:
+        _chk(k_len, "k_len", torch.int32)
+        if tuple(k_len.shape) != (B,) or not k_len.is_contiguous():
+            raise ValueError(f"k_len must be contiguous int32 [{B}]")
+        d.k_len = _p(k_len)
     L = N.lib()
     nb = L.vp_attention_bwd_workspace_bytes(C.byref(d))
     if nb < 0:
@@ -929,6 +941,78 @@ def null_key_mass(q: torch.Tensor, heads: int, text_len: int, grid, beta: torch.
                                      *[_p(t) for t in tabs], _p(tok_mask), tok_mask.stride(0), _p(segs), _p(meta),
                                      scale, _p(out), _stream()), "vp_null_key_mass")
     return out
+
+
+def null_key_mass_bwd_supported(grid) -> bool:
+    """The grid fits `null_key_mass_bwd` (its LDS holds two more per-query columns than the forward's)."""
+    F_, Hh, Ww = (int(g) for g in grid)
+    return (0 < F_ <= 16 and 0 < Hh <= 64 and 0 < Ww <= 255
+            and N.lib().vp_null_key_mass_bwd_lds_bytes(F_, Hh, Ww) <= 160 * 1024)
+
+
+def null_key_mass_bwd(q: torch.Tensor, heads: int, text_len: int, grid, beta: torch.Tensor, axis_tables,
+                      tok_mask: torch.Tensor, segments, scale: float, lse: torch.Tensor, delta: torch.Tensor,
+                      dq: torch.Tensor) -> torch.Tensor:
+    """The closed-form null keys' share of the query gradient, added into dq [B, N, heads*64] (bf16, any row / batch
+    stride): dq[b, n, h] += -scale * delta[b, h, n] * sum over the null keys of exp2(c q.k - lse[b, h, n]) k
+    (include/vp_hip.h vp_null_key_mass_bwd).  q, beta, axis_tables, tok_mask, segments: as `null_key_mass` takes them;
+    lse: the forward's statistics (l_extra included); delta: `attention_bwd`'s D.  A batch row without a null key is
+    left untouched."""
+    _chk(q, "q")
+    _chk(beta, "beta")
+    _chk(tok_mask, "tok_mask", torch.uint8)
+    _chk(dq, "dq")
+    segs, meta = segments
+    _chk(segs, "segs", torch.uint8)
+    _chk(meta, "meta", torch.int32)
+    F_, Hh, Ww = (int(g) for g in grid)
+    B, Ntok, D = q.shape
+    if D != heads * 64 or q.stride(-1) != 1 or Ntok != text_len + F_ * Hh * Ww:
+        raise ValueError(f"q must be [B, {text_len} + {F_}*{Hh}*{Ww}, heads*64], got {tuple(q.shape)}")
+    if tuple(dq.shape) != (B, Ntok, D) or dq.stride(-1) != 1:
+        raise ValueError(f"dq must be [{B}, {Ntok}, {D}] with a contiguous last dim, got {tuple(dq.shape)}")
+    if tuple(beta.shape) != (64,) or not beta.is_contiguous():
+        raise ValueError("beta must be contiguous bf16 [64]")
+    if (tuple(tok_mask.shape) != (B, Ntok) or tok_mask.stride(1) != 1 or tuple(segs.shape) != (B * F_ * Hh, 16)
+            or tuple(meta.shape) != (B * F_ + B,) or not segs.is_contiguous() or not meta.is_contiguous()):
+        raise ValueError("tok_mask / segments do not match q")
+    for t, n in ((lse, "lse"), (delta, "delta")):
+        _chk(t, n, torch.float32)
+        if tuple(t.shape) != (B, heads, Ntok) or not t.is_contiguous():
+            raise ValueError(f"{n} must be contiguous fp32 [{B}, {heads}, {Ntok}]")
+    tabs = list(axis_tables)
+    for t, shp in zip(tabs, ((F_, 16), (F_, 16), (Hh, 24), (Hh, 24), (Ww, 24), (Ww, 24))):
+        _chk(t, "rope axis table", torch.float32)
+        if tuple(t.shape) != shp or not t.is_contiguous():
+            raise ValueError(f"rope axis table must be contiguous fp32 {shp}, got {tuple(t.shape)}")
+    ev = _t0("null_key_mass_bwd")
+    N.check(N.lib().vp_null_key_mass_bwd(_p(q), q.stride(0), q.stride(1), B, heads, Ntok, text_len, F_, Hh, Ww,
+                                         _p(beta), *[_p(t) for t in tabs], _p(tok_mask), tok_mask.stride(0), _p(segs),
+                                         _p(meta), scale, _p(lse), _p(delta), _p(dq), dq.stride(0), dq.stride(1),
+                                         _stream()), "vp_null_key_mass_bwd")
+    _t1("null_key_mass_bwd", ev)
+    return dq
+
+
+def gather_add_rows(x: torch.Tensor, y: torch.Tensor, tok_mask: torch.Tensor, rows: torch.Tensor) -> torch.Tensor:
+    """y[b, n] += x[b, rows[b, n]] (bf16, one rounding) on the rows n with tok_mask[b, n] set and rows[b, n] >= 0; every
+    other row of y is left as it is.  x: [B, Nx, D], y: [B, N, D] (contiguous last dim, any row / batch stride), rows:
+    int32 [B, N] — the `dst_rows` of a compact copy, whose gradient this adds back onto the source rows."""
+    _chk(x, "x")
+    _chk(y, "y")
+    _chk(tok_mask, "tok_mask", torch.uint8)
+    B, Ntok, D = y.shape
+    if x.dim() != 3 or x.shape[0] != B or x.shape[2] != D or x.stride(-1) != 1 or y.stride(-1) != 1:
+        raise ValueError(f"x must be [{B}, Nx, {D}] with a contiguous last dim, got {tuple(x.shape)}")
+    if tuple(tok_mask.shape) != (B, Ntok) or tok_mask.stride(1) != 1:
+        raise ValueError(f"tok_mask must be uint8 [{B}, {Ntok}] with contiguous rows")
+    _chk_rows(rows, B, Ntok)
+    if rows is None:
+        raise ValueError("gather_add_rows needs rows")
+    N.check(N.lib().vp_gather_add_rows_bf16(_p(x), x.stride(1), x.stride(0), x.shape[1], _p(y), y.stride(1),
+                                            y.stride(0), B, Ntok, D, _p(tok_mask), tok_mask.stride(0), _p(rows),
+                                            _stream()), "vp_gather_add_rows_bf16")
+    return y
 
 
 def mask_scale_rows(x_in: torch.Tensor, out: torch.Tensor, tok_mask: torch.Tensor, scale: float,

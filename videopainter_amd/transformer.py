@@ -286,6 +286,15 @@ class CogVideoXBlock(nn.Module):
         attn.fp8_qk_exp = (K.qk_fp8_exponent(attn.norm_q.weight, attn.norm_q.bias, attn.scale * K.LOG2E),
                            K.qk_fp8_exponent(attn.norm_k.weight, attn.norm_k.bias))
 
+    def enable_closed_form_resample_backward(self, enabled: bool = True) -> None:
+        """The ID-resample processor's training backward on the forward's compact plan (autograd.block_backward): the
+        training forward keeps the two-segment launch's o / lse, the flash backward runs over the N own keys plus the
+        masked rows (a per-batch key length), and the null keys' share of dq comes from the closed form
+        (kernels.null_key_mass_bwd).  Needs the video grid on the rope, a separable table and a frozen norm_k bias;
+        an unmet condition raises when the block is applied.  No effect on a block without that processor."""
+        if isinstance(self.attn1.processor, CogVideoXAttnProcessor2_0_resample):
+            self.attn1.closed_form_resample_backward = bool(enabled)
+
     # -- the CFG halves' shared first-block work --
     def _cfg_shared_ok(self, x: torch.Tensor, text_len: int) -> bool:
         """The shared path restates the plain bf16 block only: two batch rows with text, the standard processor with
@@ -370,6 +379,10 @@ class CogVideoXBlock(nn.Module):
         if (keep is not None and pn is None and qkv is None and getattr(a, "fp8_qk_exp", None) is None
                 and not isinstance(a.processor, CogVideoXAttnProcessor2_0_resample)):
             return a.processor.attend(a, x, text_len, rope, keep=keep)
+        if keep is not None and getattr(a, "closed_form_resample_backward", False):
+            # (the resample processor's two-segment launch keeps o / lse for the closed-form backward)
+            return a.processor.attend(a, x, text_len, rope, pn, prev_clip_weight, resample_mask, prev_resample_mask,
+                                      qkv=qkv, keep=keep)
         return a.processor.attend(a, x, text_len, rope, pn, prev_clip_weight, resample_mask, prev_resample_mask,
                                   qkv=qkv)
 
@@ -632,6 +645,16 @@ class CogVideoXTransformer3DModel(ModelMixin):
         processor's two-segment attention (off by default: that processor then stays bf16)."""
         for blk in self.transformer_blocks:
             blk.enable_fp8_attention(enabled, resample)
+        return self
+
+    def enable_closed_form_resample_backward(self, enabled: bool = True):
+        """Opt in (default off) to the closed-form backward of the ID-resample processor in every block that carries
+        it (VideoPainterID LoRA training, window 0): the backward differentiates the forward's compact plan — no
+        attention recompute, the flash backward over N + masked-row keys instead of 2 N, the null keys' query
+        gradient in closed form (CogVideoXBlock.enable_closed_form_resample_backward; INTEGRATION.md, training).
+        Off, the backward stays the explicit 2 N-key form."""
+        for blk in self.transformer_blocks:
+            blk.enable_closed_form_resample_backward(enabled)
         return self
 
     def enable_fp8_qkv(self, enabled: bool = True):
