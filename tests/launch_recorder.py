@@ -1,5 +1,6 @@
-"""The launch recorder of the CPU launch-trace tests (tests/test_block_launches_cpu.py, tests/test_model_launches_cpu.py):
-the `videopainter_amd.kernels` entry points a block or a whole model forward calls are replaced, INSIDE THOSE TESTS
+"""The launch recorder of the CPU launch-trace tests (tests/test_block_launches_cpu.py, test_model_launches_cpu.py,
+test_block_backward_launches_cpu.py): the `videopainter_amd.kernels` entry points a block's forward and backward or a
+whole model forward call are replaced, INSIDE THOSE TESTS
 ONLY, by recorders that log the entry, every scalar argument, and shape / strides / dtype of every tensor argument, and
 return their `out` argument (or an empty tensor of the documented shape).  The product path has no such substitute.
 
@@ -43,6 +44,10 @@ def _tokens(a, src):
     return B, F * (H // a["p"]) * (W // a["p"])
 
 
+def _rows(t):
+    return t.numel() // t.shape[-1]
+
+
 # what an entry returns when it is given no `out`: an empty tensor of the documented shape
 _RETURNS = {
     "gemm": lambda a: a["out"],
@@ -71,6 +76,23 @@ _RETURNS = {
                                      _empty(a["tok_mask"].shape[0] * (a["grid"][0] + 1), like=a["tok_mask"],
                                             dtype=torch.int32)),
     "null_key_mass": lambda a: _empty(a["q"].shape[0], a["heads"], a["q"].shape[1], like=a["q"], dtype=torch.float32),
+    # a block's backward
+    "attention_bwd": lambda a: tuple(a[d] if a[d] is not None else _empty(*a[s].shape, like=a[s])
+                                     for d, s in (("dq", "q"), ("dk", "k"), ("dv", "v"))),
+    "rowscale": lambda a: a["out"],
+    "adaln_bwd": lambda a: a["dx"],
+    "colsum": lambda a: a["out"] if a["out"] is not None else _empty(
+        _rows(a["a"]) // (a["tokens_per_batch"] or _rows(a["a"])), 2, a["a"].shape[-1], like=a["a"],
+        dtype=torch.float32),
+    "wgrad": lambda a: _empty(a["dy"].shape[-1], a["x"].shape[-1], like=a["dy"]),
+    "transpose": lambda a: a["out"] if a["out"] is not None else _empty(
+        a["x"].shape[-1], -(-_rows(a["x"]) // a["pad_to"]) * a["pad_to"], like=a["x"]),
+    "axpy": lambda a: a["out"] if a["out"] is not None else torch.empty_like(a["a"]),
+    "silu": lambda a: torch.empty_like(a["x"]),
+    "silu_bwd": lambda a: torch.empty_like(a["x"]),
+    "head_norm_rope_bwd": lambda a: a["dx"],
+    "gather_add_rows": lambda a: a["y"],
+    "null_key_mass_bwd": lambda a: a["dq"],
 }
 
 
@@ -101,8 +123,8 @@ def into(log: list):
 def recording():
     """Replaces the kernel entry points with recorders; yields the list they append to.  Arguments are bound to the
     real entry's signature with its defaults applied, so a default passed explicitly records like one left out.
-    Host-side helpers that need the device or the library (the batched linears' pointer table, the null-key kernel's
-    size predicate) are replaced too, unrecorded: they are no launches."""
+    Host-side helpers that need the device or the library (the batched linears' pointer table, the null-key kernels'
+    size predicates) are replaced too, unrecorded: they are no launches."""
     from videopainter_amd import kernels as K
     log, saved = [], {}
 
@@ -121,7 +143,8 @@ def recording():
     patches = [(K, n, recorder(n, getattr(K, n))) for n in _RETURNS]
     patches += [(torch.cuda, "Event", _Event), (torch.cuda, "current_stream", lambda device=None: _Stream()),
                 (K.LinearGroupTable, "cached", staticmethod(lambda holder, linears: _Table(linears))),
-                (K, "null_key_mass_supported", lambda grid: True)]
+                (K, "null_key_mass_supported", lambda grid: True),
+                (K, "null_key_mass_bwd_supported", lambda grid: True)]
     try:
         for obj, n, f in patches:
             saved[(obj, n)] = obj.__dict__[n] if isinstance(obj, type) else getattr(obj, n)

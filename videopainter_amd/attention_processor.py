@@ -131,8 +131,10 @@ def keeps_all(keep: Optional[dict]) -> bool:
 def _qkv(attn, x: torch.Tensor, norm_rope=None, keep: Optional[dict] = None) -> torch.Tensor:
     """The fused QKV projection; with norm_rope = (text_len, rope) q and k leave the GEMM already through norm_q /
     norm_k and RoPE (the epilogue EPI_BIAS_QKNORM_ROPE: bit-equal to the GEMM + vp_head_norm_rope_bf16 on each).
-    keep, at the level "all", receives "qkv", the pre-norm q | k "qkp" (the fused epilogue's aux output, requested
-    then only) and, with train, the operand the GEMM read, "xq" (x, or its K-augmented form under unfused LoRA)."""
+    keep, at the level "all", receives views of what the GEMM wrote under the names the backward reads them by
+    (autograd): "v", the pre-norm "qpre" / "kpre" — the output's columns, or with norm_rope those of the fused
+    epilogue's aux output (requested then only) beside the normed + rotated "q" / "k" — and, with train, the operand
+    the GEMM read, "xq" (x, or its K-augmented form under unfused LoRA)."""
     B, Ntok, D = x.shape
     out = torch.empty(B, Ntok, 3 * attn.inner_dim if hasattr(attn, "inner_dim") else 3 * D, device=x.device,
                       dtype=BF16)
@@ -141,20 +143,23 @@ def _qkv(attn, x: torch.Tensor, norm_rope=None, keep: Optional[dict] = None) -> 
     a = x.reshape(-1, D)
     aug = AugmentedProjection.of((attn.to_q, attn.to_k, attn.to_v))
     kw = {}
+    pre = out
     if norm_rope is not None:
         text_len, rope = norm_rope
         kw = dict(epilogue=NAT.EPI_BIAS_QKNORM_ROPE, qk_norm=(attn.norm_q, attn.norm_k), rope=rope,
                   tokens_per_batch=Ntok, text_len=text_len)
         if keeps_all(keep):
-            keep["qkp"] = torch.empty(B, Ntok, 2 * D, device=x.device, dtype=BF16)
-            kw["aux"] = keep["qkp"].view(B * Ntok, 2 * D)
+            pre = torch.empty(B, Ntok, 2 * D, device=x.device, dtype=BF16)
+            kw["aux"] = pre.view(B * Ntok, 2 * D)
     if aug is not None:  # LoRA adapters, unfused (lora.AugmentedProjection)
         a = aug.input(a)
         aug.gemm(a, bs, out.view(B * Ntok, -1), **kw)
     else:
         K.gemm(a, ws, bs, out.view(B * Ntok, -1), **kw)
     if keeps_all(keep):
-        keep["qkv"] = out
+        keep["qpre"], keep["kpre"], keep["v"] = pre[..., :D], pre[..., D:2 * D], out[..., 2 * D:]
+        if pre is not out:
+            keep["q"], keep["k"] = out[..., :D], out[..., D:2 * D]
         if keep["train"]:
             keep["xq"] = a
     return out

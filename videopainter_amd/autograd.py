@@ -12,12 +12,19 @@ path itself (same launches, same rounding points) and whose backward runs only n
     statistics, the gated residual, the FF1 pre-activation; with trainable parameters also the AdaLN outputs, the QKV
     operand and h), else "attention" (SAVE_ATTENTION: the attention output + statistics), else nothing.  What was not
     kept the backward recomputes with the same stages (`_block_front`: stopping after the FF front, skipping the
-    attention call when its output was kept), then runs
-      FF2 dgrad -> GELU' -> FF1 dgrad -> AdaLN2' (+ residual) -> gate1 row-scale -> to_out dgrad
-      -> flash-attention backward -> (LayerNorm(64) + RoPE)' for q, k -> fused QKV dgrad -> AdaLN1' (+ residual)
-    with the dgrad GEMMs against cached transposed weights.  Trainable blocks add the weight gradients (one GEMM over
-    the token dimension per weight, `kernels.wgrad`), bias / LayerNorm-affine / modulation sums (`kernels.colsum`)
-    and the modulation linear's backward into the time embedding.
+    attention call when its output was kept).  `block_backward` is the forward's stages in reverse, one function each:
+      `_ff_bwd`           FF2 dgrad -> GELU' -> FF1 dgrad -> AdaLN2' (+ residual)
+      `_attn_output_bwd`  gate1 row-scale -> to_out dgrad
+      the attention form  flash-attention backward -> (LayerNorm(64) + RoPE)' for q, k: the pre-norm d(q | k | v)
+      `_qkv_bwd`          fused QKV dgrad
+      `_attn_input_bwd`   AdaLN1' (+ residual) -> both modulation linears' backward into the time embedding
+    with the dgrad GEMMs against cached transposed weights; `_AdaLNBwd` is the AdaLN' of both sites.  Trainable blocks
+    add the weight gradients (one GEMM over the token dimension per weight, `kernels.wgrad`) and the bias /
+    LayerNorm-affine / modulation sums (`kernels.colsum`).  The stages hand tensors on through the kept dict and pop
+    what they read last: the block's backward runs near the memory peak, and a caller's local would hold a tensor
+    until the stage returned.  Everything that depends on the attention processor is one of three forms with one
+    interface, chosen once per block call (`_attention_form`: `_SingleSegment`, and for the resample processor
+    `_Explicit2N` or `_ClosedForm`, below).
   * `_HeadFn` — norm_final + norm_out (AdaLN, shift|scale) + proj_out + unpatchify (:613-637), input gradient only
     (the transformer is frozen in the reference's training; trainable head parameters raise).
   * `_PatchEmbedFn` (embeddings.py:400-454), `_TimeEmbedFn` (embeddings.py:729-774), `_RowLinearFn` (the branch's
@@ -227,293 +234,410 @@ def _closed_form_plan(a, T: int, rope, resample_mask):
     return m, dst, cnt, segments, axes, rope.grid
 
 
-def _check_block_trainable_path(block, resample_mask=None, rope=None) -> None:
+# ---- the attention's backward, per form --------------------------------------------------------------------------
+# One form per block call (`_attention_form`), with one interface: `check` (what it refuses), `keep_level` (what a
+# training forward may keep for it), `recompute` (fills the kept set from xn) and `backward` (the pre-norm d(q | k | v)
+# from the kept set).  The kept set — a keep-all dict, filled by the forward's stages or by `_block_front` — names
+# the attention's operands alike in all forms: "q" / "k" / "v" as attention_bwd reads them (normed + rotated queries,
+# keys and values), the pre-norm "qpre" / "kpre", "o", "lse", and "plan" where there is one; `_attn_output_bwd` adds
+# "do".
+
+def _attention_operands(s: dict):
+    """(q, k, v, o, do, lse) popped from the kept set, and a fresh d(q | k | v) [B, N, 3D]."""
+    q, k, v, o, do, lse = (s.pop(n) for n in ("q", "k", "v", "o", "do", "lse"))
+    B, Ntok, D = do.shape
+    return q, k, v, o, do, lse, torch.empty(B, Ntok, 3 * D, device=do.device, dtype=BF16)
+
+
+def _qk_norm_bwd(a, qpre, kpre, dk, dqkv: torch.Tensor, T: int, rope, train: bool):
+    """(LayerNorm(64) + RoPE)' for q (in place in dqkv's q columns) and k (dk -> dqkv's k columns).  Returns the
+    affine gradients' fp32 accumulators (dlnq, dlnk), (None, None) when neither norm trains."""
+    D = dqkv.shape[-1] // 3
+    dlnq = dlnk = None
+    if train and (a.norm_q.weight.requires_grad or a.norm_k.weight.requires_grad):
+        dlnq, dlnk = (tuple(torch.zeros(64, device=dqkv.device, dtype=F32) for _ in range(2)) for _ in range(2))
+    K.head_norm_rope_bwd(qpre, dqkv[..., :D], dqkv[..., :D], a.heads, T, a.norm_q, rope, dlnq)
+    K.head_norm_rope_bwd(kpre, dk, dqkv[..., D:2 * D], a.heads, T, a.norm_k, rope, dlnk)
+    return dlnq, dlnk
+
+
+def _qk_norm_grads(a, dln, G: _Grads) -> None:
+    if dln[0] is not None:
+        for ln, (dw, db) in zip((a.norm_q, a.norm_k), dln):
+            G.put(ln.weight, dw)
+            G.put(ln.bias, db)
+
+
+class _AttentionForm:
+    def __init__(self, a, mask=None):
+        self.a, self.mask = a, mask  # the attention module; the resample processor's token mask
+
+    def check(self, rope) -> None:
+        """Raises what the form refuses beyond `_trainable_form`'s own refusals."""
+
+
+class _SingleSegment(_AttentionForm):
+    """The standard processor (and its text-free form): one key segment, q / k normed in the QKV GEMM's epilogue."""
+
+    def keep_level(self, block, x: torch.Tensor, train: bool) -> Optional[str]:
+        """"all" while the device has room, else the attention output + statistics (SAVE_ATTENTION), else nothing."""
+        a = self.a
+        qaug = AugmentedProjection.of((a.to_q, a.to_k, a.to_v)) if train else None
+        if SAVE_ACTIVATIONS and _room_for(x, block.ff.net[0].proj.weight.shape[0], train,
+                                          qaug.R if qaug is not None else 0):
+            return "all"
+        if SAVE_ATTENTION and type(a.processor) is CogVideoXAttnProcessor2_0:
+            return "attention"
+        return None
+
+    def recompute(self, block, xn: torch.Tensor, T: int, rope, keep: dict) -> None:
+        """The block's attention stage — its projection alone where the forward kept "o" / "lse"."""
+        if "o" in keep:
+            _qkv(self.a, xn, (T, rope), keep)
+        else:
+            block._attention(xn, T, rope, keep=keep)
+
+    def backward(self, s: dict, T: int, rope, train: bool, G: _Grads) -> torch.Tensor:
+        a = self.a
+        q, k, v, o, do, lse, dqkv = _attention_operands(s)
+        D = do.shape[-1]
+        K.attention_bwd(q, k, v, o, do, lse, a.heads, scale=a.scale, dq=dqkv[..., :D], dk=dqkv[..., D:2 * D],
+                        dv=dqkv[..., 2 * D:])
+        del q, k, v, o, do, lse
+        _qk_norm_grads(a, _qk_norm_bwd(a, s.pop("qpre"), s.pop("kpre"), dqkv[..., D:2 * D], dqkv, T, rope, train), G)
+        return dqkv
+
+
+class _TwoSegment(_AttentionForm):
+    """The resample processor (window 0) as the backward differentiates it: keys / values as ONE buffer each,
+    [B, 2N, D] — K / V in rows [0, N), the second segment behind them — so one flash backward covers both."""
+
+    def _recompute_operands(self, xn: torch.Tensor, T: int, rope, keep: dict, second=None):
+        """What both forms recompute alike: the pre-norm projections ("qpre" / "kpre"; `_qkv`), the buffers "q" [B, N,
+        D] and "k" / "v" [B, 2N, D], and the q and K norm launches into them — after `second(k, v, kc, vc)`, the
+        launches of a second segment built from the pre-norm projections.  Returns (v, kc, vc)."""
+        a = self.a
+        B, Ntok, D = xn.shape
+        H, dev, nq, nk = a.heads, xn.device, a.norm_q, a.norm_k
+        qkv = _qkv(a, xn, None, keep)
+        q, k, v = qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:]
+        qn = torch.empty(B, Ntok, D, device=dev, dtype=BF16)
+        kc = torch.empty(B, 2 * Ntok, D, device=dev, dtype=BF16)
+        vc = torch.empty(B, 2 * Ntok, D, device=dev, dtype=BF16)
+        if second is not None:
+            second(k, v, kc, vc)
+        K.head_norm_rope(q, qn, H, T, nq.weight, nq.bias, nq.eps, rope)
+        K.head_norm_rope(k, kc[:, :Ntok], H, T, nk.weight, nk.bias, nk.eps, rope)
+        keep.update(q=qn, k=kc, v=vc)
+        return v, kc, vc
+
+
+class _Explicit2N(_TwoSegment):
+    """The explicit form: K2 = LN(mask . k) + RoPE (masked rows: = K's rows; null rows: the norm_k bias, rotated) and
+    V2 = mask . v, all N rows of each; the second segment's gradients go back through the masked copy (masked rows
+    to k / v, the null keys' to the norm_k affine)."""
+
+    def keep_level(self, block, x, train):
+        return None  # (its backward recomputes the attention over the 2N keys)
+
+    def recompute(self, block, xn, T, rope, keep):
+        a, nk, Ntok = self.a, self.a.norm_k, xn.shape[1]
+
+        def second(k, v, kc, vc):
+            K.head_norm_rope(k, kc[:, Ntok:], a.heads, T, nk.weight, nk.bias, nk.eps, rope, tok_mask=self.mask,
+                             pre_scale=1.0)
+            vc[:, :Ntok].copy_(v)
+            K.mask_scale_rows(v, vc[:, Ntok:], self.mask, 1.0)
+        self._recompute_operands(xn, T, rope, keep, second)
+        o = augmented_rows((a.to_out[0],), *xn.shape, xn.device)
+        lse = torch.empty(xn.shape[0], a.heads, Ntok, device=xn.device, dtype=F32)
+        K.attention(keep["q"], keep["k"], keep["v"], o, a.heads, scale=a.scale, bounded_scores=bounded_scores(a),
+                    lse=lse)
+        keep.update(o=o, lse=lse)
+
+    def backward(self, s, T, rope, train, G):
+        a, mask = self.a, self.mask
+        q, k, v, o, do, lse, dqkv = _attention_operands(s)
+        B, Ntok, D = do.shape
+        dkc, dvc = torch.empty_like(k), torch.empty_like(k)  # d "k", d "v" [B, 2N, D]
+        K.attention_bwd(q, k, v, o, do, lse, a.heads, scale=a.scale, dq=dqkv[..., :D], dk=dkc, dv=dvc)
+        dqkv[..., D:2 * D].copy_(dkc[:, :Ntok])
+        dv2 = torch.empty(B, Ntok, D, device=do.device, dtype=BF16)
+        K.mask_scale_rows(dvc[:, Ntok:], dv2, mask, 1.0)  # V2 = mask . v
+        torch.add(dvc[:, :Ntok], dv2, out=dv2)
+        dqkv[..., 2 * D:].copy_(dv2)
+        del dvc, dv2, q, k, v, o, do, lse
+        kpre = s.pop("kpre")
+        dln = _qk_norm_bwd(a, s.pop("qpre"), kpre, dqkv[..., D:2 * D], dqkv, T, rope, train)
+        # K2 = LN(mask . k) + RoPE: (LN + RoPE)' at the masked input, then x mask (null rows: LN of a zero row,
+        # whose input gradient the mask cancels; their d beta stays in dlnk)
+        km = torch.empty(B, Ntok, D, device=dqkv.device, dtype=BF16)
+        K.mask_scale_rows(kpre, km, mask, 1.0)
+        dkm = K.head_norm_rope_bwd(km, dkc[:, Ntok:], torch.empty(B, Ntok, D, device=km.device, dtype=BF16), a.heads,
+                                   T, a.norm_k, rope, dln[1])
+        K.mask_scale_rows(dkm, km, mask, 1.0)
+        dqkv[..., D:2 * D].add_(km)
+        _qk_norm_grads(a, dln, G)
+        return dqkv
+
+
+class _ClosedForm(_TwoSegment):
+    """The forward's compact plan (opt-in; the module docstring has the derivation): the second segment holds the
+    masked rows of K / V alone, in partition order, `cnt[b]` of them (the rows past N + cnt[b] are never read:
+    attention_bwd's k_len); the null keys reach only dq, in closed form."""
+
+    def check(self, rope) -> None:
+        a = self.a
+        # the null keys' dS reaches only the norm_k bias (the mask cancels the path into k): not built
+        if a.norm_k.bias is not None and a.norm_k.bias.requires_grad:
+            raise NotImplementedError("the closed-form resample backward builds no norm_k bias gradient: freeze "
+                                      "norm_k.bias or disable it (enable_closed_form_resample_backward(False))")
+        _check_closed_form_plan(a, rope)
+
+    def keep_level(self, block, x, train):
+        return "attention"  # (the two-segment launch's o / lse, the null-key mass included)
+
+    def recompute(self, block, xn, T, rope, keep):
+        """No attention launch (the forward kept "o" / "lse"): compact copies, as the fused forward makes them."""
+        Ntok = xn.shape[1]
+        keep["plan"] = m, dst, _, _, _, _ = _closed_form_plan(self.a, T, rope, self.mask)
+        v, kc, vc = self._recompute_operands(xn, T, rope, keep)
+        # LN(1 . k) + RoPE of a masked row is K's row, and V2 = v there
+        K.mask_scale_rows(kc[:, :Ntok], kc[:, Ntok:], m, 1.0, dst_rows=dst)
+        vc[:, :Ntok].copy_(v)
+        K.mask_scale_rows(v, vc[:, Ntok:], m, 1.0, dst_rows=dst)
+
+    def backward(self, s, T, rope, train, G):
+        a = self.a
+        m, dst, cnt, segments, axes, grid = s.pop("plan")
+        q, k, v, o, do, lse, dqkv = _attention_operands(s)
+        B, Ntok, D = do.shape
+        dkc, dvc = torch.empty_like(k), torch.empty_like(k)  # d "k", d "v" [B, 2N, D]
+        delta = torch.empty(B, a.heads, Ntok, device=do.device, dtype=F32)
+        K.attention_bwd(q, k, v, o, do, lse, a.heads, scale=a.scale, dq=dqkv[..., :D], dk=dkc, dv=dvc,
+                        k_len=cnt + Ntok, delta=delta)
+        K.null_key_mass_bwd(q, a.heads, T, grid, a.norm_k.bias, axes, m, segments, a.scale, lse, delta, dqkv[..., :D])
+        K.gather_add_rows(dkc[:, Ntok:], dkc[:, :Ntok], m, dst)
+        K.gather_add_rows(dvc[:, Ntok:], dvc[:, :Ntok], m, dst)
+        dqkv[..., 2 * D:].copy_(dvc[:, :Ntok])
+        del dvc, delta, q, k, v, o, do, lse
+        _qk_norm_grads(a, _qk_norm_bwd(a, s.pop("qpre"), s.pop("kpre"), dkc[:, :Ntok], dqkv, T, rope, train), G)
+        return dqkv
+
+
+def _attention_form(a, resample_mask=None):
+    """The form of the attention's backward for one block call: by the processor, the mask and the opt-in."""
+    if isinstance(a.processor, CogVideoXAttnProcessor2_0_resample):
+        if resample_mask is None:
+            raise ValueError("the resample processor needs resample_mask (id_pool_resample needs masks)")
+        return (_ClosedForm if closed_form_resample(a) else _Explicit2N)(a, resample_mask)
+    if resample_mask is not None:
+        # (such a block's forward ignores the mask, while the backward would differentiate the resample attention)
+        raise NotImplementedError("resample_mask on a block without the resample processor has no backward")
+    return _SingleSegment(a)
+
+
+def _trainable_form(block, resample_mask=None, rope=None):
+    """The attention form of a block call the backward can run; raises what it refuses."""
     a = block.attn1
     if (block.ff_mx is not None or block.qkv_mx is not None or getattr(block, "out_mx", None) is not None
             or getattr(a, "fp8_qk_exp", None) is not None):
         raise NotImplementedError("the backward runs the bf16 path: disable the fp8 modes for training")
-    if isinstance(a.processor, CogVideoXAttnProcessor2_0_resample):
-        if resample_mask is None:
-            raise ValueError("the resample processor needs resample_mask (id_pool_resample needs masks)")
-        if closed_form_resample(a):
-            # the null keys' dS reaches only the norm_k bias (the mask cancels the path into k): not built
-            if a.norm_k.bias is not None and a.norm_k.bias.requires_grad:
-                raise NotImplementedError("the closed-form resample backward builds no norm_k bias gradient: freeze "
-                                          "norm_k.bias or disable it (enable_closed_form_resample_backward(False))")
-            _check_closed_form_plan(a, rope)
-    elif resample_mask is not None:
-        # (such a block's forward ignores the mask, while the backward would differentiate the resample attention)
-        raise NotImplementedError("resample_mask on a block without the resample processor has no backward")
+    form = _attention_form(a, resample_mask)
+    form.check(rope)
+    return form
 
 
-def _put_linear_grads(G: _Grads, lin, dw: torch.Tensor) -> None:
-    """The weight gradient of one projection without a trainable adapter (those go through _aug_dgrad)."""
-    G.put(lin.weight, dw)
-
-
-def _resample_attention(a, xn: torch.Tensor, T: int, rope, resample_mask: torch.Tensor, keep: dict) -> None:
-    """The resample processor's attention as the backward differentiates it, in place of the block's attention
-    stage: keys / values as one explicit 2N-key sequence [K; K2], [V; V2] with K2 = LN(mask . k) + RoPE (masked
-    rows: = K's rows; null rows: the norm_k bias, rotated) and V2 = mask . v.  keep receives the pre-norm
-    projections "qkv", the normed queries "qn", "kc" / "vc", and "o" / "lse"."""
-    B, Ntok, D = xn.shape
-    H, dev, nq, nk = a.heads, xn.device, a.norm_q, a.norm_k
-    qkv = _qkv(a, xn, None, keep)
-    q, k, v = qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:]
-    qn = torch.empty(B, Ntok, D, device=dev, dtype=BF16)
-    kc = torch.empty(B, 2 * Ntok, D, device=dev, dtype=BF16)
-    vc = torch.empty(B, 2 * Ntok, D, device=dev, dtype=BF16)
-    K.head_norm_rope(k, kc[:, Ntok:], H, T, nk.weight, nk.bias, nk.eps, rope, tok_mask=resample_mask, pre_scale=1.0)
-    vc[:, :Ntok].copy_(v)
-    K.mask_scale_rows(v, vc[:, Ntok:], resample_mask, 1.0)
-    K.head_norm_rope(q, qn, H, T, nq.weight, nq.bias, nq.eps, rope)
-    K.head_norm_rope(k, kc[:, :Ntok], H, T, nk.weight, nk.bias, nk.eps, rope)
-    o = augmented_rows((a.to_out[0],), B, Ntok, D, dev)
-    lse = torch.empty(B, H, Ntok, device=dev, dtype=F32)
-    K.attention(qn, kc, vc, o, H, scale=a.scale, bounded_scores=bounded_scores(a), lse=lse)
-    keep.update(qn=qn, kc=kc, vc=vc, o=o, lse=lse)
-
-
-def _resample_operands(a, xn: torch.Tensor, T: int, rope, resample_mask: torch.Tensor, keep: dict) -> None:
-    """The closed-form backward's operands, without an attention launch (its o / lse were kept by the forward): the
-    pre-norm projections "qkv", the normed queries "qn", and one key / value buffer each, "kc" / "vc" [B, 2N, D] —
-    K / V in rows [0, N), the forward's compact second segment behind them (the masked rows of K / V in partition
-    order, `cnt[b]` of them; the rows past N + cnt[b] are never read: attention_bwd's k_len) — and the plan "rplan"."""
-    B, Ntok, D = xn.shape
-    H, dev, nq, nk = a.heads, xn.device, a.norm_q, a.norm_k
-    rplan = m, dst, _, _, _, _ = _closed_form_plan(a, T, rope, resample_mask)
-    qkv = _qkv(a, xn, None, keep)
-    q, k, v = qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:]
-    qn = torch.empty(B, Ntok, D, device=dev, dtype=BF16)
-    kc = torch.empty(B, 2 * Ntok, D, device=dev, dtype=BF16)
-    vc = torch.empty(B, 2 * Ntok, D, device=dev, dtype=BF16)
-    K.head_norm_rope(q, qn, H, T, nq.weight, nq.bias, nq.eps, rope)
-    K.head_norm_rope(k, kc[:, :Ntok], H, T, nk.weight, nk.bias, nk.eps, rope)
-    # LN(1 . k) + RoPE of a masked row is K's row, and V2 = v there: compact copies, as the fused forward makes them
-    K.mask_scale_rows(kc[:, :Ntok], kc[:, Ntok:], m, 1.0, dst_rows=dst)
-    vc[:, :Ntok].copy_(v)
-    K.mask_scale_rows(v, vc[:, Ntok:], m, 1.0, dst_rows=dst)
-    keep.update(qn=qn, kc=kc, vc=vc, rplan=rplan)
-
+# ---- the block's stages, backward --------------------------------------------------------------------------------
 
 def _block_front(block, x: torch.Tensor, T: int, temb: torch.Tensor, rope, resample_mask, attn_saved=None,
-                 with_h: bool = False) -> dict:
+                 with_h: bool = False, form=None) -> dict:
     """The backward's recompute: forward_joint's stages (CogVideoXBlock) up to the FF front with a keep-all dict,
-    which it returns.  attn_saved: the forward's (attention output, lse); then the attention call alone is skipped.
-    with_h: FF1 runs its GELU epilogue (h, and z as its aux output: the same bits as FF1 + vp_gelu_bf16); without,
-    it stores z alone.  Both modulations are computed up front."""
+    which it returns — the attention stage as `form` recomputes it (block_backward hands over the block call's;
+    a caller without one gets it from resample_mask).  attn_saved: the forward's (attention output, lse); then no
+    attention is launched.  with_h: FF1 runs its GELU epilogue (h, and z as its aux output: the same bits as FF1 +
+    vp_gelu_bf16); without, it stores z alone.  Both modulations are computed up front."""
+    if form is None:
+        form = _attention_form(block.attn1, resample_mask)
     keep = dict(level="all", train=True)
     keep["mod1"], keep["mod2"] = mod1, mod2 = block.norm1.modulation(temb), block.norm2.modulation(temb)
     xn, _, _ = block._attn_input(x, T, mod1, keep=keep)
-    if resample_mask is not None and attn_saved is not None:  # (kept by the closed-form forward only)
+    if attn_saved is not None:
         keep["o"], keep["lse"] = attn_saved
-        _resample_operands(block.attn1, xn, T, rope, resample_mask, keep)
-    elif resample_mask is not None:
-        _resample_attention(block.attn1, xn, T, rope, resample_mask, keep)
-    elif attn_saved is not None:
-        keep["o"], keep["lse"] = attn_saved
-        _qkv(block.attn1, xn, (T, rope), keep)
-    else:
-        block._attention(xn, T, rope, keep=keep)
+    form.recompute(block, xn, T, rope, keep)
     block._ff_front(block._attn_output(x, keep["o"], mod1, T, keep), mod2, T, keep, activate=with_h)
     return keep
 
 
-def block_backward(block, x: torch.Tensor, T: int, temb: torch.Tensor, rope, inject_mask: Optional[torch.Tensor],
-                   dout: torch.Tensor, want_dtemb: bool, want_dinject: bool, train: bool,
-                   resample_mask: Optional[torch.Tensor] = None, attn_saved=None, front: Optional[dict] = None):
-    """Gradient-checkpointed backward of `block.forward_joint(x, T, temb, rope, resample_mask=.., inject=..,
-    inject_mask=..)`.  Returns (dx [B, Ntok, D], dtemb or None, dinject [B, Nv, D] or None, _Grads).  attn_saved:
-    the forward's (attention output, lse) — then the attention is not recomputed (SAVE_ATTENTION); front: the
-    training forward's keep-all dict (_BlockFn.forward) — then nothing is recomputed."""
-    B, Ntok, D = x.shape
+class _AdaLNBwd:
+    """AdaLN' at one of the block's two sites (norm2 on x_mid, norm1 on x), in the three steps both share and between
+    which a site runs its own launches: the constructor adds LN'(dy (1 + scale) w) into g — with need_dmod it also
+    stores the LayerNorm's output, that output's gradient and x-hat; `mod_grad` sums the modulation's gradient;
+    `affine_grads` the LayerNorm weight's and bias's."""
+
+    def __init__(self, nz, x: torch.Tensor, dy: torch.Tensor, g: torch.Tensor, T: int, mod: torch.Tensor,
+                 need_dmod: bool):
+        self.ln, self.dy, self.T = nz.norm, dy, T
+        self.n = self.dn = self.xhat = None
+        if need_dmod:
+            self.n, self.dn, self.xhat = (torch.empty_like(x) for _ in range(3))
+        K.adaln_bwd(x, dy, g, T, self.ln.weight, self.ln.bias, self.ln.eps, mod, n_out=self.n, dn_out=self.dn,
+                    xhat_out=self.xhat)
+
+    def mod_grad(self, gate) -> torch.Tensor:
+        """[B, 6D] (_mod_grad) from the shift and scale column sums and the gate's: `gate` [B, 2, D], or the pair
+        (d out, branch output) to sum it from."""
+        _, Ntok, D = self.dy.shape
+        kw = dict(tokens_per_batch=Ntok, text_len=self.T)
+        shift = K.colsum(self.dy.view(-1, D), **kw)
+        scale = K.colsum(self.dy.view(-1, D), self.n.view(-1, D), **kw)
+        return _mod_grad(shift, scale, K.colsum(*gate, **kw) if isinstance(gate, tuple) else gate)
+
+    def affine_grads(self, G: _Grads) -> None:
+        D = self.dy.shape[-1]
+        G.put(self.ln.weight, _total(self.dn.view(-1, D), self.xhat.view(-1, D)))
+        G.put(self.ln.bias, _total(self.dn.view(-1, D)))
+
+
+def _ff_bwd(block, s: dict, dout: torch.Tensor, g: torch.Tensor, T: int, mod2: torch.Tensor, need_dmod: bool,
+            train: bool, G: _Grads) -> Optional[torch.Tensor]:
+    """FeedForward + gated residual 2: FF2 dgrad -> GELU' -> FF1 dgrad -> AdaLN2' added into g (= dout: the residual).
+    Returns the norm2 modulation's gradient (need_dmod)."""
+    B, Ntok, D = dout.shape
     M = B * Ntok
-    a = block.attn1
-    H = a.heads
-    n1, n2 = block.norm1, block.norm2
-    ff0, ff2, to_out = block.ff.net[0].proj, block.ff.net[2], a.to_out[0]
-    F4 = ff0.weight.shape[0]
-    dev = x.device
+    ff0, ff2 = block.ff.net[0].proj, block.ff.net[2]
+    x_mid, z, xn2, h = s.pop("x_mid"), s.pop("z"), s.pop("xn2", None), s.pop("h", None)
+    dout2 = dout.view(M, D)
+    df = torch.empty(M, D, device=dout.device, dtype=BF16)
+    K.rowscale(dout2, df, Ntok, T, mod2, 2, 5)
+    dz = torch.empty(M, ff0.weight.shape[0], device=dout.device, dtype=BF16)
+    K.gemm(df, [_wt(ff2.weight)], [None], dz, epilogue=NAT.EPI_GELU_BWD, z=z)  # (df W2) * GELU'(z), one pass
+    dxn2 = torch.empty(B, Ntok, D, device=dout.device, dtype=BF16)
+    _dgrad(dz, ff0.weight, dxn2.view(M, D))
+    ad = _AdaLNBwd(block.norm2, x_mid, dxn2, g, T, mod2, need_dmod)
+    if not need_dmod:
+        return None
+    # h exactly as the forward made it: GELU applied in the FF1 GEMM epilogue on the fp32 accumulator (a GELU of the
+    # bf16-rounded z would differ by one rounding, and so would ff2's weight and gate-2 gradients)
+    if h is None:
+        h = K.linear(xn2.view(M, D), ff0.weight, ff0.bias, gelu=True)
+    f = torch.empty(M, D, device=dout.device, dtype=BF16)
+    K.gemm(h, [ff2.weight], [ff2.bias], f)
+    dmod2 = ad.mod_grad((dout2, f))
+    del f
+    if train:
+        G.put(ff2.weight, K.wgrad(df, h))
+        G.put(ff2.bias, _total(df))
+        G.put(ff0.weight, K.wgrad(dz, xn2.view(M, D)))
+        G.put(ff0.bias, _total(dz))
+        ad.affine_grads(G)
+    return dmod2
+
+
+def _attn_output_bwd(block, s: dict, g: torch.Tensor, T: int, mod1: torch.Tensor, need_dmod: bool, train: bool,
+                     G: _Grads) -> Optional[torch.Tensor]:
+    """to_out + gated residual 1: gate-1 row-scale -> to_out dgrad, "do" into s (from its "o", which stays for the
+    attention).  Returns the gate-1 column sums (need_dmod)."""
+    B, Ntok, D = g.shape
+    M = B * Ntok
+    to_out = block.attn1.to_out[0]
+    oaug = AugmentedProjection.of((to_out,))
+    o2 = s["o"].view(M, D)
+    dao = torch.empty(M, D, device=g.device, dtype=BF16)
+    K.rowscale(g.view(M, D), dao, Ntok, T, mod1, 2, 5)
+    o_aug = gate1 = None
+    if need_dmod:
+        ao = torch.empty(M, D, device=g.device, dtype=BF16)
+        project_out(to_out, o2, ao)
+        gate1 = K.colsum(g.view(M, D), ao, tokens_per_batch=Ntok, text_len=T)
+        del ao
+        if train:
+            if oaug is not None:
+                o_aug = oaug.input(o2)
+            elif to_out.weight.requires_grad:
+                G.put(to_out.weight, K.wgrad(dao, o2))
+            G.put(to_out.bias, _total(dao))
+    do = torch.empty(B, Ntok, D, device=g.device, dtype=BF16)
+    _dgrad(dao, to_out.weight, do.view(M, D))
+    if oaug is not None:
+        _aug_dgrad(oaug, dao, o2, do.view(M, D), train and need_dmod, G, o_aug)
+    s["do"] = do
+    return gate1
+
+
+def _qkv_bwd(a, s: dict, train: bool, G: _Grads) -> torch.Tensor:
+    """The fused QKV projection: "dqkv" -> d xn [B, N, D], and the weight / bias / LoRA gradients."""
+    dqkv, xn, xq = s.pop("dqkv"), s.pop("xn", None), s.pop("xq", None)
+    B, Ntok, D3 = dqkv.shape
+    D, M = D3 // 3, B * Ntok
+    lins = (a.to_q, a.to_k, a.to_v)
+    qaug = AugmentedProjection.of(lins)
+    dxn = torch.empty(B, Ntok, D, device=dqkv.device, dtype=BF16)
+    K.gemm(dqkv.view(M, D3), [_qkv_t(a)], [None], dxn.view(M, D))
+    if train:
+        db = _total(dqkv.view(M, D3))
+        if qaug is None and any(l.weight.requires_grad for l in lins):
+            dw = K.wgrad(dqkv.view(M, D3), xq)
+            for i, lin in enumerate(lins):
+                G.put(lin.weight, dw[i * D:(i + 1) * D])
+        for i, lin in enumerate(lins):
+            G.put(lin.bias, db[i * D:(i + 1) * D])
+        if qaug is not None:
+            _aug_dgrad(qaug, dqkv.view(M, D3), xn.view(M, D), dxn.view(M, D), True, G, xq)
+    elif qaug is not None:
+        # (no parameter gradients: x2 is not read — and a frozen block's saving forward keeps no xn)
+        _aug_dgrad(qaug, dqkv.view(M, D3), None, dxn.view(M, D), False, G)
+    return dxn
+
+
+def _attn_input_bwd(block, x: torch.Tensor, dxn: torch.Tensor, g: torch.Tensor, T: int, temb: torch.Tensor,
+                    mod1: torch.Tensor, gate1, dmod2, need_dmod: bool, want_dtemb: bool, train: bool,
+                    G: _Grads) -> Optional[torch.Tensor]:
+    """AdaLN1' added into g (now d x), then both modulation linears' backward into the time embedding: dtemb."""
+    ad = _AdaLNBwd(block.norm1, x, dxn, g, T, mod1, need_dmod)
+    if not need_dmod:
+        return None
+    dmod1 = ad.mod_grad(gate1)
+    if train:
+        ad.affine_grads(G)
+    st = K.silu(temb.contiguous())
+    ds = K.axpy(_small_linear_bwd(G, block.norm1.linear, st, dmod1),
+                _small_linear_bwd(G, block.norm2.linear, st, dmod2))
+    return K.silu_bwd(ds, temb.contiguous()) if want_dtemb else None
+
+
+def block_backward(block, form, x: torch.Tensor, T: int, temb: torch.Tensor, rope,
+                   inject_mask: Optional[torch.Tensor], dout: torch.Tensor, want_dtemb: bool, want_dinject: bool,
+                   train: bool, attn_saved=None, front: Optional[dict] = None):
+    """Gradient-checkpointed backward of `block.forward_joint(x, T, temb, rope, resample_mask=.., inject=..,
+    inject_mask=..)`, the forward's stages in reverse.  Returns (dx [B, Ntok, D], dtemb or None, dinject [B, Nv, D]
+    or None, _Grads).  form: the attention's (`_attention_form`); attn_saved: the forward's (attention output, lse) —
+    then the attention is not recomputed; front: the training forward's keep-all dict (_BlockFn.forward) — then
+    nothing is recomputed."""
+    B, Ntok, D = x.shape
     need_dmod = train or want_dtemb
     G = _Grads()
-
-    # ---- the forward's intermediates: kept by the training forward (the `keep` level "all") or recomputed here by
-    # forward_joint's own stages ----
-    if front is None:
-        front = _block_front(block, x, T, temb, rope, resample_mask, attn_saved, with_h=need_dmod)
-    f = front
-    mod1, mod2, qkv, o, lse, x_mid, z = (f.pop(k) for k in ("mod1", "mod2", "qkv", "o", "lse", "x_mid", "z"))
-    xn, xq, xn2, h_saved = f.pop("xn", None), f.pop("xq", None), f.pop("xn2", None), f.pop("h", None)
-    qaug = AugmentedProjection.of((a.to_q, a.to_k, a.to_v))
-    oaug = AugmentedProjection.of((to_out,))
-    resample = resample_mask is not None
-    v = qkv[..., 2 * D:]
-    kc = vc = None
-    rplan = f.pop("rplan", None)  # the closed-form plan (_resample_operands), else the explicit 2N-key form
-    if resample:  # qkv: the pre-norm projections
-        qn, kc, vc = f.pop("qn"), f.pop("kc"), f.pop("vc")
-        qpre, kpre = qkv[..., :D], qkv[..., D:2 * D]
-    else:  # qkv: the normed q | k and v; qkp: the pre-norm q | k
-        qkp = f.pop("qkp")
-        qn, kn = qkv[..., :D], qkv[..., D:2 * D]
-        qpre, kpre = qkp[..., :D], qkp[..., D:]
-    del front, f
+    # the forward's intermediates: kept by the training forward (the `keep` level "all") or recomputed here by
+    # forward_joint's own stages; the stages below pop them, and hand "do" / "dqkv" on, through this dict
+    s = front if front is not None else _block_front(block, x, T, temb, rope, form.mask, attn_saved, need_dmod, form)
+    del front
+    mod1, mod2 = s.pop("mod1"), s.pop("mod2")
 
     dout = dout.contiguous()
-    dout2 = dout.view(M, D)
     dinj = None
     if want_dinject:
         if inject_mask is None:
             dinj = dout[:, T:].clone()
         else:
-            dinj = torch.empty(B, Ntok - T, D, device=dev, dtype=BF16)
+            dinj = torch.empty(B, Ntok - T, D, device=x.device, dtype=BF16)
             K.mask_scale_rows(dout[:, T:], dinj, (inject_mask == 0).to(torch.uint8), 1.0)
 
-    # ---- FeedForward + gated residual 2 ----
     g = dout.clone()  # d x_mid, then d x
-    df = torch.empty(M, D, device=dev, dtype=BF16)
-    K.rowscale(dout2, df, Ntok, T, mod2, 2, 5)
-    dz = torch.empty(M, F4, device=dev, dtype=BF16)
-    K.gemm(df, [_wt(ff2.weight)], [None], dz, epilogue=NAT.EPI_GELU_BWD, z=z)  # (df W2) * GELU'(z), one pass
-    dxn2 = torch.empty(B, Ntok, D, device=dev, dtype=BF16)
-    _dgrad(dz, ff0.weight, dxn2.view(M, D))
-    n2o = dn2 = xh2 = None
-    if need_dmod:
-        n2o, dn2, xh2 = (torch.empty_like(x) for _ in range(3))
-    K.adaln_bwd(x_mid, dxn2, g, T, n2.norm.weight, n2.norm.bias, n2.norm.eps, mod2, n_out=n2o, dn_out=dn2,
-                xhat_out=xh2)
-    if need_dmod:
-        # h exactly as the forward made it: GELU applied in the FF1 GEMM epilogue on the fp32 accumulator (a GELU
-        # of the bf16-rounded z would differ by one rounding, and so would ff2's weight and gate-2 gradients)
-        h = h_saved if h_saved is not None else K.linear(xn2.view(M, D), ff0.weight, ff0.bias, gelu=True)
-        f = torch.empty(M, D, device=dev, dtype=BF16)
-        K.gemm(h, [ff2.weight], [ff2.bias], f)
-        dmod2 = _mod_grad(K.colsum(dxn2.view(M, D), tokens_per_batch=Ntok, text_len=T),
-                          K.colsum(dxn2.view(M, D), n2o.view(M, D), tokens_per_batch=Ntok, text_len=T),
-                          K.colsum(dout2, f, tokens_per_batch=Ntok, text_len=T))
-        del f
-        if train:
-            G.put(ff2.weight, K.wgrad(df, h))
-            G.put(ff2.bias, _total(df))
-            G.put(ff0.weight, K.wgrad(dz, xn2.view(M, D)))
-            G.put(ff0.bias, _total(dz))
-            G.put(n2.norm.weight, _total(dn2.view(M, D), xh2.view(M, D)))
-            G.put(n2.norm.bias, _total(dn2.view(M, D)))
-        del h
-    del z, dz, df, xn2, n2o, dn2, xh2, dxn2, h_saved
-
-    # ---- attention + gated residual 1 ----
-    dao = torch.empty(M, D, device=dev, dtype=BF16)
-    K.rowscale(g.view(M, D), dao, Ntok, T, mod1, 2, 5)
-    o_aug = None
-    if need_dmod:
-        ao = torch.empty(M, D, device=dev, dtype=BF16)
-        project_out(to_out, o.view(M, D), ao)
-        gate1 = K.colsum(g.view(M, D), ao, tokens_per_batch=Ntok, text_len=T)
-        del ao
-        if train:
-            if oaug is None:
-                if to_out.weight.requires_grad:
-                    _put_linear_grads(G, to_out, K.wgrad(dao, o.view(M, D)))
-            else:
-                o_aug = oaug.input(o.view(M, D))
-            G.put(to_out.bias, _total(dao))
-    do = torch.empty(B, Ntok, D, device=dev, dtype=BF16)
-    _dgrad(dao, to_out.weight, do.view(M, D))
-    if oaug is not None:
-        _aug_dgrad(oaug, dao, o.view(M, D), do.view(M, D), train and need_dmod, G, o_aug)
-    del dao, o_aug
-    dqkv = torch.empty(B, Ntok, 3 * D, device=dev, dtype=BF16)
-    dk2 = None
-    kgrad = dqkv[..., D:2 * D]  # d (normed + rotated K), the k norm backward's input
-    if rplan is not None:
-        # the closed-form plan: keys = K's N rows + the cnt[b] masked rows behind them (k_len, on the device); the
-        # null keys (value 0: dS = -P D) reach only dq, in closed form; a masked row's K2 / V2 row is the same
-        # function of the same k / v row as its K / V row, so their gradients add up before the one norm backward
-        m, dst, cnt, segments, axes, grid = rplan
-        dkc = torch.empty(B, 2 * Ntok, D, device=dev, dtype=BF16)
-        dvc = torch.empty(B, 2 * Ntok, D, device=dev, dtype=BF16)
-        delta = torch.empty(B, H, Ntok, device=dev, dtype=F32)
-        K.attention_bwd(qn, kc, vc, o, do, lse, H, scale=a.scale, dq=dqkv[..., :D], dk=dkc, dv=dvc,
-                        k_len=cnt + Ntok, delta=delta)
-        K.null_key_mass_bwd(qn, H, T, grid, a.norm_k.bias, axes, m, segments, a.scale, lse, delta, dqkv[..., :D])
-        K.gather_add_rows(dkc[:, Ntok:], dkc[:, :Ntok], m, dst)
-        K.gather_add_rows(dvc[:, Ntok:], dvc[:, :Ntok], m, dst)
-        dqkv[..., 2 * D:].copy_(dvc[:, :Ntok])
-        kgrad = dkc[:, :Ntok]
-        del dvc, kc, vc, delta
-    elif resample:
-        dkc = torch.empty(B, 2 * Ntok, D, device=dev, dtype=BF16)
-        dvc = torch.empty(B, 2 * Ntok, D, device=dev, dtype=BF16)
-        K.attention_bwd(qn, kc, vc, o, do, lse, H, scale=a.scale, dq=dqkv[..., :D], dk=dkc, dv=dvc)
-        dqkv[..., D:2 * D].copy_(dkc[:, :Ntok])
-        dv2 = torch.empty(B, Ntok, D, device=dev, dtype=BF16)
-        K.mask_scale_rows(dvc[:, Ntok:], dv2, resample_mask, 1.0)  # V2 = mask . v
-        torch.add(dvc[:, :Ntok], dv2, out=dv2)
-        dqkv[..., 2 * D:].copy_(dv2)
-        dk2 = dkc[:, Ntok:]
-        del dvc, dv2, kc, vc
-    else:
-        K.attention_bwd(qn, kn, v, o, do, lse, H, scale=a.scale, dq=dqkv[..., :D], dk=dqkv[..., D:2 * D],
-                        dv=dqkv[..., 2 * D:])
-        del qn, kn, v, qkv
-    del do, o, lse
-    dlnq = dlnk = None
-    if train and (a.norm_q.weight.requires_grad or a.norm_k.weight.requires_grad):
-        dlnq = (torch.zeros(64, device=dev, dtype=F32), torch.zeros(64, device=dev, dtype=F32))
-        dlnk = (torch.zeros(64, device=dev, dtype=F32), torch.zeros(64, device=dev, dtype=F32))
-    K.head_norm_rope_bwd(qpre, dqkv[..., :D], dqkv[..., :D], H, T, a.norm_q, rope, dlnq)
-    K.head_norm_rope_bwd(kpre, kgrad, dqkv[..., D:2 * D], H, T, a.norm_k, rope, dlnk)
-    del kgrad
-    if dk2 is not None:
-        # K2 = LN(mask . k) + RoPE: (LN + RoPE)' at the masked input, then x mask (null rows: LN of a zero row,
-        # whose input gradient the mask cancels; their d beta stays in dlnk)
-        km = torch.empty(B, Ntok, D, device=dev, dtype=BF16)
-        K.mask_scale_rows(kpre, km, resample_mask, 1.0)
-        dkm = K.head_norm_rope_bwd(km, dk2, torch.empty(B, Ntok, D, device=dev, dtype=BF16), H, T, a.norm_k, rope,
-                                   dlnk)
-        K.mask_scale_rows(dkm, km, resample_mask, 1.0)
-        dqkv[..., D:2 * D].add_(km)
-        del km, dkm, dk2, dkc
-    del qpre, kpre
-    if dlnq is not None:
-        G.put(a.norm_q.weight, dlnq[0])
-        G.put(a.norm_q.bias, dlnq[1])
-        G.put(a.norm_k.weight, dlnk[0])
-        G.put(a.norm_k.bias, dlnk[1])
-    dxn = torch.empty(B, Ntok, D, device=dev, dtype=BF16)
-    K.gemm(dqkv.view(M, 3 * D), [_qkv_t(a)], [None], dxn.view(M, D))
-    if train:
-        db = _total(dqkv.view(M, 3 * D))
-        if qaug is None and any(l.weight.requires_grad for l in (a.to_q, a.to_k, a.to_v)):
-            dw = K.wgrad(dqkv.view(M, 3 * D), xq)
-            for s, lin in enumerate((a.to_q, a.to_k, a.to_v)):
-                _put_linear_grads(G, lin, dw[s * D:(s + 1) * D])
-            del dw
-        for s, lin in enumerate((a.to_q, a.to_k, a.to_v)):
-            G.put(lin.bias, db[s * D:(s + 1) * D])
-        if qaug is not None:
-            _aug_dgrad(qaug, dqkv.view(M, 3 * D), xn.view(M, D), dxn.view(M, D), True, G, xq)
-    elif qaug is not None:
-        # (no parameter gradients: x2 is not read — and a frozen block's saving forward keeps no xn)
-        _aug_dgrad(qaug, dqkv.view(M, 3 * D), None, dxn.view(M, D), False, G)
-    del dqkv, xn, xq
-    n1o = dn1 = xh1 = None
-    if need_dmod:
-        n1o, dn1, xh1 = (torch.empty_like(x) for _ in range(3))
-    K.adaln_bwd(x, dxn, g, T, n1.norm.weight, n1.norm.bias, n1.norm.eps, mod1, n_out=n1o, dn_out=dn1, xhat_out=xh1)
-
-    dtemb = None
-    if need_dmod:
-        dmod1 = _mod_grad(K.colsum(dxn.view(M, D), tokens_per_batch=Ntok, text_len=T),
-                          K.colsum(dxn.view(M, D), n1o.view(M, D), tokens_per_batch=Ntok, text_len=T), gate1)
-        if train:
-            G.put(n1.norm.weight, _total(dn1.view(M, D), xh1.view(M, D)))
-            G.put(n1.norm.bias, _total(dn1.view(M, D)))
-        s = K.silu(temb.contiguous())
-        ds = K.axpy(_small_linear_bwd(G, n1.linear, s, dmod1), _small_linear_bwd(G, n2.linear, s, dmod2))
-        if want_dtemb:
-            dtemb = K.silu_bwd(ds, temb.contiguous())
+    dmod2 = _ff_bwd(block, s, dout, g, T, mod2, need_dmod, train, G)
+    gate1 = _attn_output_bwd(block, s, g, T, mod1, need_dmod, train, G)
+    s["dqkv"] = form.backward(s, T, rope, train, G)
+    dxn = _qkv_bwd(block.attn1, s, train, G)
+    dtemb = _attn_input_bwd(block, x, dxn, g, T, temb, mod1, gate1, dmod2, need_dmod, want_dtemb, train, G)
     return g, dtemb, dinj, G
 
 
@@ -544,30 +668,22 @@ def _room_for(x: torch.Tensor, F4: int, keep_train: bool = False, R: int = 0) ->
 
 class _BlockFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, block, T, rope, inject_mask, resample_mask, x, temb, inject, *params):
-        """forward_joint with a `keep` dict at the level the switches and the device's room choose: "all" (then
+    def forward(ctx, block, T, rope, inject_mask, form, x, temb, inject, *params):
+        """forward_joint with a `keep` dict at the level the attention's form states (`keep_level`): "all" (then
         nothing is recomputed; a frozen block drops xn / xq / xn2 / h, train=False), "attention", or none."""
-        a = block.attn1
         train = any(p.requires_grad for p in params) or temb.requires_grad
-        qaug = AugmentedProjection.of((a.to_q, a.to_k, a.to_v)) if train else None
+        level = form.keep_level(block, x, train)
         keep = mod1 = mod2 = None
-        if resample_mask is not None:
-            # (the explicit 2N-key backward recomputes its attention; the closed-form one keeps the forward's)
-            if closed_form_resample(a):
-                keep = dict(level="attention", train=train)
-        else:
-            if SAVE_ACTIVATIONS and _room_for(x, block.ff.net[0].proj.weight.shape[0], train,
-                                              qaug.R if qaug is not None else 0):
-                keep = dict(level="all", train=train)
-                mod1, mod2 = block.norm1.modulation(temb), block.norm2.modulation(temb)  # (as _block_front)
-            elif SAVE_ATTENTION and type(a.processor) is CogVideoXAttnProcessor2_0:
-                keep = dict(level="attention", train=train)
-        out = block.forward_joint(x, T, temb, rope, resample_mask=resample_mask, inject=inject,
+        if level is not None:
+            keep = dict(level=level, train=train)
+        if level == "all":
+            mod1, mod2 = block.norm1.modulation(temb), block.norm2.modulation(temb)  # (as _block_front)
+        out = block.forward_joint(x, T, temb, rope, resample_mask=form.mask, inject=inject,
                                   inject_mask=inject_mask if inject is not None else None, keep=keep, mod1=mod1,
                                   mod2=mod2)
         ctx.front = keep if keeps_all(keep) else None
         ctx.attn_saved = (keep["o"], keep["lse"]) if keep is not None and ctx.front is None else None
-        ctx.block, ctx.T, ctx.rope, ctx.inject_mask, ctx.resample_mask = block, T, rope, inject_mask, resample_mask
+        ctx.block, ctx.T, ctx.rope, ctx.inject_mask, ctx.form = block, T, rope, inject_mask, form
         ctx.has_inject = inject is not None
         ctx.params = params
         ctx.save_for_backward(x, temb)
@@ -580,9 +696,9 @@ class _BlockFn(torch.autograd.Function):
         train = any(need[8:])
         front, ctx.front = ctx.front, None  # (the backward pops it: each intermediate is freed as it is used)
         attn_saved, ctx.attn_saved = ctx.attn_saved, None
-        dx, dtemb, dinj, G = block_backward(ctx.block, x, ctx.T, temb, ctx.rope,
+        dx, dtemb, dinj, G = block_backward(ctx.block, ctx.form, x, ctx.T, temb, ctx.rope,
                                             ctx.inject_mask if ctx.has_inject else None, dout, need[6],
-                                            need[7] and ctx.has_inject, train, ctx.resample_mask, attn_saved, front)
+                                            need[7] and ctx.has_inject, train, attn_saved, front)
         return (None, None, None, None, None, dx if need[5] else None, dtemb, dinj, *G.out(ctx.params))
 
 
@@ -591,9 +707,9 @@ def block_apply(block, x: torch.Tensor, T: int, temb: torch.Tensor, rope, inject
                 resample_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Differentiable `block.forward_joint` (gradient-checkpointed).  resample_mask: the uint8 token mask of the
     blocks' resample processor (window 0 of VideoPainterID training)."""
-    _check_block_trainable_path(block, resample_mask, rope)
+    form = _trainable_form(block, resample_mask, rope)
     params = [p for p in block.parameters()]
-    return _BlockFn.apply(block, T, rope, inject_mask, resample_mask, x, temb, inject, *params)
+    return _BlockFn.apply(block, T, rope, inject_mask, form, x, temb, inject, *params)
 
 
 # ------------------------------------------------------------------------------------------------------------------

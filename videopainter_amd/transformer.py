@@ -17,7 +17,10 @@ the classifier-free-guidance halves — share once, `CogVideoXBlock._attend_cfg_
 
 The block's forward is written once, as five stages (`CogVideoXBlock._attn_input`, `_attention`, `_attn_output`,
 `_ff_front`, `_ff_back`): `forward_joint` composes them, a training forward is the same call with a `keep` dict the
-stages fill for the backward, and the backward's recompute (autograd._block_front) runs the same stages.
+stages fill for the backward, the backward's recompute (autograd._block_front) runs the same stages, and the backward
+itself (autograd.block_backward) is one function per stage, in reverse.  Whether a training forward passes `keep`, and
+at what level, is the rule of its attention's backward form (autograd._attention_form); the attention stage hands it
+to the processor's `attend` in one call.
 
 A model's inference forward is written once too (`_forward_infer`, the head `_head`): `forward` parses the call and
 shapes the return; the Ulysses head-parallel split (ulysses.py) runs the same body on a rank's row shard by passing a
@@ -370,21 +373,15 @@ class CogVideoXBlock(nn.Module):
         """x: the attention-input stage's xn (with an fp8 projection `qkv`: any [B, N, D] tensor, for its shape)
         -> o [B, N, D], through the `attend` hook or the processor.  The hook also gets the fp8 projection's `qkv` and
         whether the output projection is the fp8 one (it may then return o as the MXTensor `_attn_output` takes).
-        keep: handed to the processor (which fills it, CogVideoXAttnProcessor2_0.attend) where the attention is the
-        single-segment bf16 one; left as it is elsewhere."""
+        keep: handed to the processor, which fills it (`attend` of either processor; a ValueError where it keeps
+        nothing: the fp8 forms, the prev-clip blend, a handed-over qkv).  Whether a training forward passes one is the
+        rule of its attention's backward form (autograd: `keep_level`)."""
         a = self.attn1
         if attend is not None:
             return attend(a, x, text_len, rope, pn, prev_clip_weight, resample_mask, prev_resample_mask, qkv,
                           self.out_mx is not None)
-        if (keep is not None and pn is None and qkv is None and getattr(a, "fp8_qk_exp", None) is None
-                and not isinstance(a.processor, CogVideoXAttnProcessor2_0_resample)):
-            return a.processor.attend(a, x, text_len, rope, keep=keep)
-        if keep is not None and getattr(a, "closed_form_resample_backward", False):
-            # (the resample processor's two-segment launch keeps o / lse for the closed-form backward)
-            return a.processor.attend(a, x, text_len, rope, pn, prev_clip_weight, resample_mask, prev_resample_mask,
-                                      qkv=qkv, keep=keep)
         return a.processor.attend(a, x, text_len, rope, pn, prev_clip_weight, resample_mask, prev_resample_mask,
-                                  qkv=qkv)
+                                  qkv=qkv, keep=keep)
 
     def _attn_output(self, x: torch.Tensor, o, mod1: torch.Tensor, text_len: int,
                      keep: Optional[dict] = None) -> torch.Tensor:
@@ -473,9 +470,10 @@ class CogVideoXBlock(nn.Module):
         back as its MX-FP8 operand).
         keep: {"level": "attention" | "all", "train": bool}, a training forward's dict that the stages fill for its
         backward (autograd._BlockFn) without changing a launch.  "attention": the attention output "o" and its softmax
-        statistics "lse" (where the attention is the single-segment bf16 one).  "all": also "mod1", "mod2", "qkv",
-        the pre-norm q | k "qkp", "x_mid" and the FF1 pre-activation "z" (the two GEMMs' aux outputs, requested at this
-        level only) and, with train, "xn", "xq", "xn2" and "h"."""
+        statistics "lse" (the single-segment bf16 attention, or the resample processor's closed-form plan).  "all":
+        also "mod1", "mod2", the normed "q" / "k" and "v", the pre-norm "qpre" / "kpre", "x_mid" and the FF1
+        pre-activation "z" (the two GEMMs' aux outputs, requested at this level only) and, with train, "xn", "xq",
+        "xn2" and "h"."""
         processor = self.attn1.processor
         if not isinstance(processor, CogVideoXAttnProcessor2_0):
             raise ValueError(f"Unsupported processor type: {type(processor)}")
