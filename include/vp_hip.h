@@ -33,7 +33,7 @@ extern "C" {
 #define VP_ERR_UNSUPPORTED 1001
 
 /* ABI version: bump when any struct layout or signature below changes. */
-#define VP_ABI_VERSION 26
+#define VP_ABI_VERSION 27
 int vp_abi_version(void);
 /* "<sha256 of sources + flags>:<sha256 of the compiler version>" of the build (no reference counterpart) */
 const char* vp_build_digest(void);
@@ -47,9 +47,9 @@ const char* vp_build_digest(void);
  * runs two variants on the same operands.  Returns VP_ERR_ARG for an unknown name or a value over 31 bytes.  Host
  * only; not thread-safe against launches in flight on other host threads.  (ABI 14.) */
 int vp_set_knob(const char* name, const char* value);
-/* sizeof of the descriptor structs as compiled into the library: out[0..13] = gemm, attn, dpm, gemm_mx, attn_fp8,
- * conv3d, attn_bwd, mt_tensor, mt_chunk, optim_scalars, zero_range, zero_record, attn_merge, linear_group (ABI
- * check) */
+/* sizeof of the descriptor structs as compiled into the library: out[0..14] = gemm, attn, dpm, gemm_mx, attn_fp8,
+ * conv3d, attn_bwd, mt_tensor, mt_chunk, optim_scalars, zero_range, zero_record, attn_merge, linear_group,
+ * prodigy_scalars (ABI check) */
 void vp_struct_sizes(int64_t* out);
 
 /* ---------------------------------------------------------------------------------------------------------------
@@ -839,6 +839,67 @@ int vp_v_loss_bf16(const void* model_output, const void* noisy, const void* targ
                    int32_t mask_is_f32, const int64_t* timesteps, const float* alphas_cumprod, int32_t n_alphas,
                    int32_t B, int32_t F, int32_t C, int32_t HW, float lambda, float* partials, float* loss,
                    void* dout, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Plain Adam and Prodigy (ABI 27; csrc/optim.hip, csrc/prodigy.hip): the other two choices of the reference's
+ * get_optimizer (train/train_cogvideox_inpainting_i2v_video.py:1283-1361), on the tables, the flat fp32 state space,
+ * the norm pass and the scalars block of the training tail above. */
+/* torch.optim.Adam (amsgrad = False, maximize = False): vp_mt_adamw_bf16 with the weight decay as an L2 term on the
+ * gradient, g = grad (* clip_coef) + weight_decay * master, instead of the factor on the master; everything else,
+ * the skipped step included, as there. */
+int vp_mt_adam_bf16(const vp_mt_tensor* tensors, const vp_mt_chunk* chunks, int32_t chunk_begin, int32_t n_chunks,
+                    float* master, float* exp_avg, float* exp_avg_sq, const vp_optim_scalars* scalars, double lr,
+                    double beta1, double beta2, double eps, double weight_decay, int32_t use_clip, int32_t zero_grads,
+                    void* stream);
+/* Prodigy (prodigyopt 1.0's step() with slice_p = 1, no FSDP) with fp32 master weights.  State: master, exp_avg,
+ * exp_avg_sq, s, p0 (the initial master), fp32 over the flat state space.  The distance estimate lives in a device
+ * block of doubles (the reference keeps these in Python floats); only vp_prodigy_finalize writes it. */
+typedef struct {
+  double d;            /* the distance estimate (starts at d0) */
+  double d_max;        /* the largest d_hat so far (starts at d0) */
+  double d_hat;        /* d_coef * d_numerator / d_denom of the last step that made progress */
+  double d_numerator;  /* beta3-decayed sum of (d / d0) dlr <g, p0 - p> */
+  double d_denom;      /* sum |s| of the last step */
+  double dlr;          /* d * lr * bias correction of the step, from the d BEFORE the step's update */
+  int32_t no_progress; /* 1 when the last step found d_denom == 0: no parameter changed, the counter stood still */
+  int32_t pad;
+} vp_prodigy_scalars;
+/* One step is, after the norm pass and vp_optim_finalize (advance_step = 1: clip_coef, skipped, the counter):
+ *   vp_prodigy_finalize(phase 0)    dlr = d lr bc, bc = sqrt(1 - beta2^step) / (1 - beta1^step) with the advanced
+ *                                   counter when use_bias_correction, else 1
+ *   vp_mt_prodigy_moments_bf16      once per parameter group: the moments, s and the two partials of every chunk
+ *   vp_prodigy_finalize(phase 1)    d_numerator = beta3 d_numerator + (d / d0) dlr sum(dot), d_denom = sum(|s|), both
+ *                                   sums over partials[0 .. 2 n_chunks) in a fixed order in double; d_denom == 0:
+ *                                   no_progress = 1, the counter goes back by one and the rest of the block stays;
+ *                                   else, when lr > 0, d_hat = d_coef d_numerator / d_denom, d = max(d, d_hat) while
+ *                                   d == d0, d_max = max(d_max, d_hat), d = min(d_max, d growth_rate)
+ *   vp_mt_prodigy_update_bf16       once per parameter group: the update with the NEW d in d * eps
+ * A skipped step (scalars->skipped) changes nothing in either phase.  One workgroup; n_chunks is used by phase 1 only
+ * (partials may be NULL in phase 0).  VP_ERR_ARG for a phase other than 0 / 1, lr < 0, betas or beta3 outside [0, 1),
+ * d0 <= 0, d_coef <= 0, growth_rate < 1, or any NaN. */
+int vp_prodigy_finalize(int32_t phase, const float* partials, int32_t n_chunks, double lr, double beta1, double beta2,
+                        double beta3, double d0, double d_coef, double growth_rate, int32_t use_bias_correction,
+                        vp_optim_scalars* scalars, vp_prodigy_scalars* dstate, void* stream);
+/* pass 1 over chunks [chunk_begin, chunk_begin + n_chunks).  Per element, in fp32, with d and dlr of the block:
+ *   g = grad (* clip_coef when use_clip) (+ weight_decay * master: the coupled decay; pass 0 when decoupled)
+ *   dot += g (p0 - master); exp_avg = beta1 exp_avg + d (1 - beta1) g; exp_avg_sq = beta2 exp_avg_sq +
+ *   d^2 (1 - beta2) g^2; s = beta3 s + (d / d0) (safeguard_warmup ? d : dlr) g; den += |s|
+ * partials[2 c] = dot and partials[2 c + 1] = den of chunk c (its index in the whole table).  22 bytes read and 12
+ * written per element.  A skipped step writes nothing. */
+int vp_mt_prodigy_moments_bf16(const vp_mt_tensor* tensors, const vp_mt_chunk* chunks, int32_t chunk_begin,
+                               int32_t n_chunks, const float* master, const float* p0, float* exp_avg,
+                               float* exp_avg_sq, float* s, float* partials, const vp_optim_scalars* scalars,
+                               const vp_prodigy_scalars* dstate, double beta1, double beta2, double beta3,
+                               double weight_decay, double d0, int32_t safeguard_warmup, int32_t use_clip,
+                               void* stream);
+/* pass 2 over the same chunks.  Per element, in fp32: denom = sqrt(exp_avg_sq) + d eps (the new d);
+ * p = master (+ master * (-weight_decay dlr): the decoupled decay; pass 0 when coupled); p -= dlr exp_avg / denom;
+ * master = p, param = bf16(p).  12 bytes read and 6 written per element (8 with zero_grads).  A skipped or
+ * no-progress step writes no state and no parameter (it still zeroes the gradients when asked to). */
+int vp_mt_prodigy_update_bf16(const vp_mt_tensor* tensors, const vp_mt_chunk* chunks, int32_t chunk_begin,
+                              int32_t n_chunks, float* master, const float* exp_avg, const float* exp_avg_sq,
+                              const vp_optim_scalars* scalars, const vp_prodigy_scalars* dstate, double eps,
+                              double weight_decay, int32_t zero_grads, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Sharded training tail (ABI 22; csrc/zero.hip): the kernels of a data-parallel optimizer step with the fp32 state

@@ -1,6 +1,6 @@
 """Optimizer-step time at the real branch parameter set on one MI355X: FusedAdamW against the torch equivalents.
 
-    python tools/bench_optim.py [--rounds R] [--iters N] [--sharded]
+    python tools/bench_optim.py [--rounds R] [--iters N] [--sharded] [--prodigy]
 
 Parameters: the trainable VideoPainter branch (5b-I2V config, num_layers=2, init_synthetic_weights_), bf16, with
 random bf16 gradients N(0, 1e-3^2); the training script's hyper-parameters (lr 1e-5, betas (0.9, 0.95), weight decay
@@ -20,6 +20,11 @@ run in RCCL on the device buffers, as copies), and afterwards times its kernels 
 bytes/s from its own byte count — pack 2 B read + 4 B written per parameter, shard AdamW 16 + 14 B, unpack 2 + 2 B —
 next to vp_mt_adamw_bf16's in the same run (the yardstick), and the three collectives.  No figure for world > 1 can be
 produced on one GPU.
+
+--prodigy adds videopainter_amd.FusedProdigy(lr=1.0, max_grad_norm=1.0) as a variant interleaved with the others, and
+afterwards times its two passes one by one, round by round beside vp_mt_adamw_bf16's update pass (the yardstick of
+the same round): pass 1 (vp_mt_prodigy_moments_bf16) 22 B read + 12 B written per parameter, pass 2
+(vp_mt_prodigy_update_bf16) 12 + 6 B; with the norm pass's 2 B the step moves 54 B per parameter against AdamW's 30.
 
 Prints ms per step per round (HIP events around N back-to-back steps), and for `fused` the effective bandwidth
 30 B x n_params / t (norm pass: 2 B read; update pass: 14 B read + 14 B written per parameter) as a fraction of
@@ -56,6 +61,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--sharded", action="store_true", help="add ShardedFusedAdamW at world 1 over RCCL")
+    ap.add_argument("--prodigy", action="store_true", help="add FusedProdigy and time its two passes")
     args = ap.parse_args()
     from videopainter_amd import CogvideoXBranchModel, FusedAdamW, device_scope
     from videopainter_amd import kernels as K
@@ -97,7 +103,11 @@ def main():
     opt16 = torch.optim.AdamW(p16, **HYP, foreach=True)
 
     variants = dict(fused=fused.step, torch_fp32=torch_fp32, torch_bf16=opt16.step)
-    sharded = None
+    sharded = prodigy = None
+    if args.prodigy:
+        from videopainter_amd import FusedProdigy
+        prodigy = FusedProdigy(with_grads(clone()), **dict(HYP, lr=1.0), max_grad_norm=1.0)
+        variants["prodigy"] = prodigy.step
     if args.sharded:
         import socket
         from videopainter_amd import ShardedFusedAdamW
@@ -139,6 +149,42 @@ def main():
                norm_pass_ms=norm_ms, norm_pass_gb_per_s=2.0 * n_params / (norm_ms * 1e-3) / 1e9,
                update_pass_ms=upd_ms, update_pass_gb_per_s=28.0 * n_params / (upd_ms * 1e-3) / 1e9,
                speedup_vs_torch_fp32=med["torch_fp32"] / med["fused"])
+    if prodigy is not None:
+        z, zt = prodigy, prodigy._tables
+        b3 = HYP["betas"][1] ** 0.5
+        d_steps = float(prodigy.d)  # (the passes below run out of their step's order: d means nothing afterwards)
+        passes = dict(
+            adamw_update=(28.0, lambda: K.mt_adamw(t.tensors, t.chunks, 0, t.n_chunks, fused._master, fused._exp_avg,
+                                                   fused._exp_avg_sq, fused._scalars, lr=HYP["lr"],
+                                                   betas=HYP["betas"], eps=HYP["eps"],
+                                                   weight_decay=HYP["weight_decay"], use_clip=True,
+                                                   zero_grads=False)),
+            moments=(34.0, lambda: K.mt_prodigy_moments(zt.tensors, zt.chunks, 0, zt.n_chunks, z._master, z._p0,
+                                                        z._exp_avg, z._exp_avg_sq, z._s, z._pairs, z._scalars,
+                                                        z._d_block, betas=HYP["betas"], beta3=b3, weight_decay=0.0,
+                                                        d0=z.d0, safeguard_warmup=False, use_clip=True)),
+            update=(18.0, lambda: K.mt_prodigy_update(zt.tensors, zt.chunks, 0, zt.n_chunks, z._master, z._exp_avg,
+                                                      z._exp_avg_sq, z._scalars, z._d_block, eps=HYP["eps"],
+                                                      weight_decay=HYP["weight_decay"], zero_grads=False)),
+            finalize=(0.0, lambda: K.prodigy_finalize(1, z._pairs, zt.n_chunks, z._scalars, z._d_block, lr=1.0,
+                                                      betas=HYP["betas"], beta3=b3, d0=z.d0, d_coef=z.d_coef,
+                                                      growth_rate=z.growth_rate, use_bias_correction=False)))
+        pms = {k: [] for k in passes}
+        for r in range(args.rounds):
+            for k, (_, fn) in passes.items():
+                pms[k].append(timed(fn, args.iters))
+            print("pass round %d: " % r + "  ".join(f"{k} {pms[k][-1]:.3f} ms" for k in passes), flush=True)
+        pmed = {k: sorted(v)[len(v) // 2] for k, v in pms.items()}
+        yard = 28.0 * n_params / (pmed["adamw_update"] * 1e-3) / 1e9
+        res["prodigy_passes"] = dict(ms=pms, median_ms=pmed, yardstick_mt_adamw_gb_per_s=yard)
+        for name in ("moments", "update"):
+            gbs = passes[name][0] * n_params / (pmed[name] * 1e-3) / 1e9
+            res["prodigy_passes"][name] = dict(bytes_per_param=passes[name][0], gb_per_s=gbs,
+                                               fraction_of_6p3_tb_s=gbs * 1e9 / HBM, vs_mt_adamw=gbs / yard)
+            print(f"prodigy {name}: {pmed[name]:.3f} ms = {gbs:.0f} GB/s = {gbs * 1e9 / HBM:.2f} of 6.3 TB/s "
+                  f"({gbs / yard:.2f} of vp_mt_adamw_bf16's {yard:.0f} GB/s in the same rounds)")
+        print(f"prodigy step: {med['prodigy']:.3f} ms against fused {med['fused']:.3f} ms (54 B against 30 B of "
+              f"traffic per parameter; d = {d_steps:.3e} after the steps); finaliser {pmed['finalize'] * 1e3:.1f} us")
     if sharded is not None:
         z, zt, c = sharded, sharded._tables, sharded._comm
         mine = z._flat16[z._lo:z._hi]

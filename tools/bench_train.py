@@ -1,7 +1,7 @@
 """Training-step throughput of the VideoPainter training path on one MI355X.
 
-    python tools/bench_train.py [--steps K] [--warmup W] [--height 60 --width 90] [--optimizer none|torch|fused|sharded]
-                                [--loss]
+    python tools/bench_train.py [--steps K] [--warmup W] [--height 60 --width 90]
+                                [--optimizer none|torch|fused|adam|prodigy|sharded] [--loss]
 
 One step = the reference's training iteration (train/train_cogvideox_inpainting_i2v_video.py:1856-1892 with the
 launch script train/VideoPainter.sh: 49 frames 480x720 -> latent 13x60x90, batch 1, bf16, branch_layer_num 2,
@@ -10,7 +10,9 @@ launch script train/VideoPainter.sh: 49 frames 480x720 -> latent 13x60x90, batch
 parameter.  --optimizer torch adds torch's AdamW (foreach) stepped directly on the bf16 branch parameters (PyTorch's
 kernels, and no master weights: most of an lr = 1e-5 update is lost below the bf16 ulp); --optimizer fused adds
 videopainter_amd.FusedAdamW(max_grad_norm=1.0): gradient norm + clip + AdamW with fp32 master weights on the HIP
-kernels (csrc/optim.hip); --optimizer sharded runs videopainter_amd.ShardedFusedAdamW(max_grad_norm=1.0), the
+kernels (csrc/optim.hip); --optimizer adam and --optimizer prodigy add videopainter_amd.FusedAdam and
+videopainter_amd.FusedProdigy (lr 1.0, csrc/prodigy.hip) with the same clip, the script's other two --optimizer
+choices; --optimizer sharded runs videopainter_amd.ShardedFusedAdamW(max_grad_norm=1.0), the
 data-parallel step (csrc/zero.hip): alone it forms a one-rank group, under `torchrun --nproc_per_node N` one rank per
 GPU (the group is initialised as bench.py does, the branch replicated from rank 0 with broadcast_module, every rank
 draws its own latents, and verify_replicas runs after the last step: "replicas_identical" in the JSON line, which
@@ -52,7 +54,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--height", type=int, default=60)
     ap.add_argument("--width", type=int, default=90)
-    ap.add_argument("--optimizer", choices=("none", "torch", "fused", "sharded"), default="none")
+    ap.add_argument("--optimizer", choices=("none", "torch", "fused", "adam", "prodigy", "sharded"), default="none")
     ap.add_argument("--loss", action="store_true",
                     help="inpainting_v_loss(...).backward() instead of out.backward(dout)")
     ap.add_argument("--classes", action="store_true", help="per-class HIP-event timing pass afterwards")
@@ -98,6 +100,12 @@ def main():
     elif args.optimizer == "fused":
         from videopainter_amd import FusedAdamW
         opt = FusedAdamW(params, lr=1e-5, betas=(0.9, 0.95), weight_decay=1e-4, max_grad_norm=1.0)
+    elif args.optimizer == "adam":
+        from videopainter_amd import FusedAdam
+        opt = FusedAdam(params, lr=1e-5, betas=(0.9, 0.95), weight_decay=1e-4, max_grad_norm=1.0)
+    elif args.optimizer == "prodigy":
+        from videopainter_amd import FusedProdigy
+        opt = FusedProdigy(params, lr=1.0, betas=(0.9, 0.95), weight_decay=1e-4, max_grad_norm=1.0)
     elif args.optimizer == "sharded":
         from videopainter_amd import ShardedFusedAdamW
         VD.broadcast_module(br, src=0, always=True)  # the replicas start from rank 0's bytes
@@ -162,7 +170,8 @@ def main():
     res = dict(metric="training steps/sec (VideoPainter branch, 5b-I2V frozen, 49f 480x720, B=1)",
                value=1.0 / el, unit="steps/s", ms_per_step=el * 1e3, steps=args.steps, warmup=args.warmup,
                optimizer={"none": None, "torch": "torch AdamW foreach",
-                          "fused": "FusedAdamW(max_grad_norm=1.0)",
+                          "fused": "FusedAdamW(max_grad_norm=1.0)", "adam": "FusedAdam(max_grad_norm=1.0)",
+                          "prodigy": "FusedProdigy(lr=1.0, max_grad_norm=1.0)",
                           "sharded": "ShardedFusedAdamW(max_grad_norm=1.0)"}[args.optimizer],
                optimizer_ms=(sum(a.elapsed_time(b) for a, b in opt_events) / len(opt_events)) if opt_events else None,
                loss="inpainting_v_loss" if args.loss else None,

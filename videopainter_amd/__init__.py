@@ -31,7 +31,7 @@ def __getattr__(name):
     if name in ("CogVideoXI2VDualInpaintAnyLHarness",):
         from . import pipeline
         return getattr(pipeline, name)
-    if name in ("FusedAdamW", "clip_grad_norm_", "get_gradient_norm"):
+    if name in ("FusedAdamW", "FusedAdam", "FusedProdigy", "clip_grad_norm_", "get_gradient_norm"):
         from . import optim
         return getattr(optim, name)
     if name in ("ShardedFusedAdamW",):

@@ -11,7 +11,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VP_HIP_LIB", os.path.join(_HERE, "_lib", "libvp_hip.so"))
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 vp = C.c_void_p
 i32 = C.c_int32
@@ -113,6 +113,11 @@ class MtChunk(C.Structure):
 class OptimScalars(C.Structure):
     _fields_ = [("grad_norm", f32), ("clip_coef", f32), ("nonfinite", i32), ("step", i32), ("bias_c1", f32),
                 ("bias_c2", f32), ("skipped", i32), ("pad", i32)]
+
+
+class ProdigyScalars(C.Structure):
+    _fields_ = [("d", C.c_double), ("d_max", C.c_double), ("d_hat", C.c_double), ("d_numerator", C.c_double),
+                ("d_denom", C.c_double), ("dlr", C.c_double), ("no_progress", i32), ("pad", i32)]
 
 
 class ZeroRange(C.Structure):
@@ -218,6 +223,13 @@ _SIGS = {
     "vp_mt_scale_bf16": (i32, [vp, vp, i32, vp, vp]),
     "vp_mt_adamw_bf16": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double,
                                C.c_double, i32, i32, vp]),
+    "vp_mt_adam_bf16": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double,
+                              C.c_double, i32, i32, vp]),
+    "vp_prodigy_finalize": (i32, [i32, vp, i32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                  C.c_double, C.c_double, i32, vp, vp, vp]),
+    "vp_mt_prodigy_moments_bf16": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_double,
+                                         C.c_double, C.c_double, C.c_double, i32, i32, vp]),
+    "vp_mt_prodigy_update_bf16": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, vp, C.c_double, C.c_double, i32, vp]),
     "vp_scale_dev_bf16": (i32, [vp, vp, i64, vp, vp]),
     "vp_v_loss_partials": (i64, [i32, i32, i32, i32]),
     "vp_v_loss_bf16": (i32, [vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp]),
@@ -278,12 +290,12 @@ def lib():
         if src is not None and built.split(":")[0] != src:
             raise HipLibraryError(f"{LIB_PATH} was built from other sources (digest {built[:12]}.. != "
                                   f"{src[:12]}..); rebuild with `python -m videopainter_amd.build`")
-        sizes = (i64 * 14)()
+        sizes = (i64 * 15)()
         L.vp_struct_sizes(sizes)
         want = (C.sizeof(GemmDesc), C.sizeof(AttnDesc), C.sizeof(DpmDesc), C.sizeof(GemmMxDesc),
                 C.sizeof(AttnFp8Desc), C.sizeof(Conv3dDesc), C.sizeof(AttnBwdDesc), C.sizeof(MtTensor),
                 C.sizeof(MtChunk), C.sizeof(OptimScalars), C.sizeof(ZeroRange), C.sizeof(ZeroRecord),
-                C.sizeof(AttnMergeDesc), C.sizeof(LinearGroup))
+                C.sizeof(AttnMergeDesc), C.sizeof(LinearGroup), C.sizeof(ProdigyScalars))
         if tuple(sizes) != want:
             raise HipLibraryError(f"descriptor size mismatch lib={tuple(sizes)} python={want}; rebuild")
         knob_values.update({k: os.environ.get(k) for k in KNOBS})  # what the library read at load

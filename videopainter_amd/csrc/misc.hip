@@ -301,6 +301,7 @@ extern "C" void vp_struct_sizes(int64_t* out) {
   out[11] = (int64_t)sizeof(vp_zero_record);
   out[12] = (int64_t)sizeof(vp_attn_merge_desc);
   out[13] = (int64_t)sizeof(vp_linear_group);
+  out[14] = (int64_t)sizeof(vp_prodigy_scalars);
 }
 
 // M <= 2 rows (the CFG pair's AdaLN / time-embedding vectors), K <= 512: a weight-streaming kernel.  Each wave owns

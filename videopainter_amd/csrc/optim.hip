@@ -1,7 +1,7 @@
 // The tail of the training step (gfx950): the fused v-prediction loss + its gradient, the multi-tensor gradient norm /
-// clip, and AdamW with fp32 master weights behind the bf16 parameters (include/vp_hip.h "Training tail").  All of it
-// is memory-bound streaming: one workgroup per VP_MT_CHUNK elements of one tensor, 16-byte loads / stores in the
-// body, scalar head / tail.  Reductions are two-stage (a partial per chunk in its own slot, then one workgroup that
+// clip, and AdamW / plain Adam with fp32 master weights behind the bf16 parameters (include/vp_hip.h "Training tail").
+// All of it is memory-bound streaming: one workgroup per VP_MT_CHUNK elements of one tensor, 16-byte loads / stores in
+// the body, scalar head / tail.  Reductions are two-stage (a partial per chunk in its own slot, then one workgroup that
 // sums the slots in a fixed order): no float atomics, bit-identical run to run.
 #include "optim_common.h"  // shared with csrc/zero.hip: stream_piece, sqnorm_piece, adam_piece, the finaliser
 
@@ -45,7 +45,9 @@ __global__ __launch_bounds__(OT) void mt_scale_kernel(const vp_mt_tensor* __rest
       });
 }
 
-// ---- c. AdamW with fp32 master weights (adam_piece: optim_common.h) ----
+// ---- c. AdamW (L2 = false) and plain Adam (L2 = true: the decay as an L2 term on the gradient) with fp32 master
+// weights (adam_piece: optim_common.h) ----
+template <bool L2>
 __global__ __launch_bounds__(OT) void mt_adamw_kernel(const vp_mt_tensor* __restrict__ tensors,
                                                       const vp_mt_chunk* __restrict__ chunks, int chunk_begin,
                                                       float* __restrict__ master, float* __restrict__ exp_avg,
@@ -66,7 +68,7 @@ __global__ __launch_bounds__(OT) void mt_adamw_kernel(const vp_mt_tensor* __rest
     if (a.zero_grads) zero_piece(g, head, r.n);
     return;
   }
-  adam_piece(g, pm, mm, vm, w, head, r.n, a, adam_coef(a, sc));
+  adam_piece<L2>(g, pm, mm, vm, w, head, r.n, a, adam_coef(a, sc));
 }
 
 // ---- y = bf16(x * *s) ----
@@ -204,19 +206,36 @@ extern "C" int vp_mt_scale_bf16(const vp_mt_tensor* tensors, const vp_mt_chunk* 
   return VP_OK;
 }
 
-extern "C" int vp_mt_adamw_bf16(const vp_mt_tensor* tensors, const vp_mt_chunk* chunks, int32_t chunk_begin,
-                                int32_t n_chunks, float* master, float* exp_avg, float* exp_avg_sq,
-                                const vp_optim_scalars* scalars, double lr, double beta1, double beta2, double eps,
-                                double weight_decay, int32_t use_clip, int32_t zero_grads, void* stream) {
+template <bool L2>
+static int mt_adam_launch(const vp_mt_tensor* tensors, const vp_mt_chunk* chunks, int32_t chunk_begin,
+                          int32_t n_chunks, float* master, float* exp_avg, float* exp_avg_sq,
+                          const vp_optim_scalars* scalars, double lr, double beta1, double beta2, double eps,
+                          double weight_decay, int32_t use_clip, int32_t zero_grads, void* stream) {
   if (n_chunks < 0 || chunk_begin < 0 || !scalars || !master || !exp_avg || !exp_avg_sq) return VP_ERR_ARG;
   if (!adam_hyper_ok(lr, beta1, beta2, eps, weight_decay)) return VP_ERR_ARG;
   if (n_chunks == 0) return VP_OK;
   if (!tensors || !chunks) return VP_ERR_ARG;
   const AdamArgs a = adam_args(lr, beta1, beta2, eps, weight_decay, use_clip, zero_grads);
-  hipLaunchKernelGGL(mt_adamw_kernel, dim3(n_chunks), dim3(OT), 0, (hipStream_t)stream, tensors, chunks, chunk_begin,
-                     master, exp_avg, exp_avg_sq, scalars, a);
+  hipLaunchKernelGGL(mt_adamw_kernel<L2>, dim3(n_chunks), dim3(OT), 0, (hipStream_t)stream, tensors, chunks,
+                     chunk_begin, master, exp_avg, exp_avg_sq, scalars, a);
   VP_CHECK_LAUNCH();
   return VP_OK;
+}
+
+extern "C" int vp_mt_adamw_bf16(const vp_mt_tensor* tensors, const vp_mt_chunk* chunks, int32_t chunk_begin,
+                                int32_t n_chunks, float* master, float* exp_avg, float* exp_avg_sq,
+                                const vp_optim_scalars* scalars, double lr, double beta1, double beta2, double eps,
+                                double weight_decay, int32_t use_clip, int32_t zero_grads, void* stream) {
+  return mt_adam_launch<false>(tensors, chunks, chunk_begin, n_chunks, master, exp_avg, exp_avg_sq, scalars, lr, beta1,
+                               beta2, eps, weight_decay, use_clip, zero_grads, stream);
+}
+
+extern "C" int vp_mt_adam_bf16(const vp_mt_tensor* tensors, const vp_mt_chunk* chunks, int32_t chunk_begin,
+                               int32_t n_chunks, float* master, float* exp_avg, float* exp_avg_sq,
+                               const vp_optim_scalars* scalars, double lr, double beta1, double beta2, double eps,
+                               double weight_decay, int32_t use_clip, int32_t zero_grads, void* stream) {
+  return mt_adam_launch<true>(tensors, chunks, chunk_begin, n_chunks, master, exp_avg, exp_avg_sq, scalars, lr, beta1,
+                              beta2, eps, weight_decay, use_clip, zero_grads, stream);
 }
 
 extern "C" int vp_scale_dev_bf16(const void* x, void* y, int64_t n, const float* s, void* stream) {

@@ -1,8 +1,9 @@
 // What the optimizer kernels of csrc/optim.hip (one GPU) and csrc/zero.hip (data-parallel, sharded state) share —
 // everything but the decoding of their tables and the choice of each piece's scalar head: the workgroup shape and its
 // fixed-order sum, stream_piece (scalar head / 16-byte body / scalar tail of one piece), the zero fill, the gradient
-// norm's first stage (sqnorm_piece) and finaliser, the AdamW update of one piece (adam_piece) and the host-side
-// argument checks.  Both AdamW kernels are adam_piece around the SAME adam_element(), and every multiply-add in it is
+// norm's first stage (sqnorm_piece) and finaliser, the AdamW update of one piece (adam_piece), the two passes of
+// Prodigy over one piece (prodigy_moments_piece, prodigy_update_piece: csrc/prodigy.hip) and the host-side argument
+// checks.  Both AdamW kernels are adam_piece around the SAME adam_element(), and every multiply-add in it is
 // spelled out with contraction off, so they cannot drift apart by a fused multiply-add: a world-1 sharded step is
 // bit-identical to the single-GPU step.
 #pragma once
@@ -137,6 +138,7 @@ VP_DEV void sqnorm_piece(const T* __restrict__ g, int head, int n, float* __rest
 struct AdamArgs {
   float lr, decay, omb1, beta2, omb2, eps;  // decay = 1 - lr * weight_decay, omb = 1 - beta
   int use_clip, zero_grads;
+  float wd;  // weight_decay itself: the L2 term of plain Adam (adam_element<true>)
 };
 
 struct AdamCoef {
@@ -155,6 +157,7 @@ inline AdamArgs adam_args(double lr, double beta1, double beta2, double eps, dou
   a.eps = (float)eps;
   a.use_clip = use_clip;
   a.zero_grads = zero_grads;
+  a.wd = (float)weight_decay;
   return a;
 }
 
@@ -175,11 +178,17 @@ VP_DEV AdamCoef adam_coef(const AdamArgs& a, const vp_optim_scalars* __restrict_
   return k;
 }
 
+// L2 = false: AdamW, the decay as a factor on the parameter.  L2 = true: torch.optim.Adam, the decay as an L2 term on
+// the gradient (and no factor on the parameter); the lines below the first two are the same code for both.
+template <bool L2 = false>
 VP_DEV void adam_element(float g, float& p, float& m, float& v, const AdamArgs& a, const AdamCoef& k) {
   // torch.optim.adamw._single_tensor_adamw, one rounded operation per torch op (no contraction across them)
 #pragma clang fp contract(off)
   g *= k.clip;
-  p *= a.decay;                               // param.mul_(1 - lr * weight_decay)
+  if constexpr (L2)
+    g = __builtin_fmaf(a.wd, p, g);           // grad.add(param, alpha=weight_decay)
+  else
+    p *= a.decay;                             // param.mul_(1 - lr * weight_decay)
   m = __builtin_fmaf(a.omb1, g - m, m);       // exp_avg.lerp_(grad, 1 - beta1)
   v = v * a.beta2 + a.omb2 * g * g;           // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
   const float denom = sqrtf(v) / k.bc2_sqrt + a.eps;
@@ -189,7 +198,7 @@ VP_DEV void adam_element(float g, float& p, float& m, float& v, const AdamArgs& 
 // ---- the update of one piece: gradient g[0, n) (bf16, or fp32 from the reduce-scatter), master and moments in and
 // out, bf16(master) into w.  The caller picks `head` (every stream 16-byte aligned at `head`, or head == n); that
 // decides which path an element takes, not its value.  Only a bf16 gradient can be zeroed in the same pass. ----
-template <class G>
+template <bool L2 = false, class G>
 VP_DEV void adam_piece(G* __restrict__ g, float* __restrict__ pm, float* __restrict__ mm, float* __restrict__ vm,
                        bf16* __restrict__ w, int head, int n, const AdamArgs& a, const AdamCoef& k) {
   constexpr bool can_zero = std::is_same_v<G, bf16>;
@@ -197,7 +206,7 @@ VP_DEV void adam_piece(G* __restrict__ g, float* __restrict__ pm, float* __restr
       head, n,
       [&](int i) {
         float p = pm[i], m = mm[i], v = vm[i];
-        adam_element(to_f32(g[i]), p, m, v, a, k);
+        adam_element<L2>(to_f32(g[i]), p, m, v, a, k);
         pm[i] = p;
         mm[i] = m;
         vm[i] = v;
@@ -212,13 +221,154 @@ VP_DEV void adam_piece(G* __restrict__ g, float* __restrict__ pm, float* __restr
         load8(mm + o, m);
         load8(vm + o, v);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) adam_element(g8[e], p[e], m[e], v[e], a, k);
+        for (int e = 0; e < 8; ++e) adam_element<L2>(g8[e], p[e], m[e], v[e], a, k);
         store8(pm + o, p);
         store8(mm + o, m);
         store8(vm + o, v);
         store8(w + o, p);
         if constexpr (can_zero)
           if (a.zero_grads) *(bf16x8*)(g + o) = bf16x8{};
+      });
+}
+
+// ---- Prodigy with fp32 master weights (prodigyopt 1.0's step(), slice_p = 1): the per-element work of its two
+// passes.  The distance estimate is a block of doubles on the device; each pass rounds the products it needs to fp32
+// once per thread (the reference forms them in Python floats and torch rounds them to the tensors' fp32). ----
+struct ProdigyMomentArgs {
+  float beta1, beta2, beta3, wd;  // wd: the coupled decay (0 when decoupled)
+  double omb1, omb2, d0;          // omb = 1 - beta
+  int safeguard, use_clip;
+};
+
+struct ProdigyMomentCoef {
+  float clip, c1, c2, c3;  // d (1 - beta1), d^2 (1 - beta2), (d / d0) (safeguard ? d : dlr)
+};
+
+inline ProdigyMomentArgs prodigy_moment_args(double beta1, double beta2, double beta3, double weight_decay, double d0,
+                                             int safeguard, int use_clip) {
+  ProdigyMomentArgs a;
+  a.beta1 = (float)beta1;
+  a.beta2 = (float)beta2;
+  a.beta3 = (float)beta3;
+  a.wd = (float)weight_decay;
+  a.omb1 = 1.0 - beta1;
+  a.omb2 = 1.0 - beta2;
+  a.d0 = d0;
+  a.safeguard = safeguard;
+  a.use_clip = use_clip;
+  return a;
+}
+
+inline bool prodigy_hyper_ok(double beta1, double beta2, double beta3, double d0) {
+  return betas_ok(beta1, beta2) && beta3 >= 0.0 && beta3 < 1.0 && d0 > 0.0;
+}
+
+VP_DEV ProdigyMomentCoef prodigy_moment_coef(const ProdigyMomentArgs& a, const vp_optim_scalars* __restrict__ sc,
+                                             const vp_prodigy_scalars* __restrict__ ds) {
+#pragma clang fp contract(off)
+  const double d = ds->d, dlr = ds->dlr;
+  ProdigyMomentCoef k;
+  k.clip = a.use_clip ? sc->clip_coef : 1.f;
+  k.c1 = (float)(d * a.omb1);
+  k.c2 = (float)(d * d * a.omb2);
+  k.c3 = (float)((d / a.d0) * (a.safeguard ? d : dlr));
+  return k;
+}
+
+VP_DEV void prodigy_moment_element(float g, float p, float p0, float& m, float& v, float& s, float& dot, float& den,
+                                   const ProdigyMomentArgs& a, const ProdigyMomentCoef& k) {
+  // one rounded operation per torch op of the reference's first loop (no contraction across them)
+#pragma clang fp contract(off)
+  g *= k.clip;
+  if (a.wd != 0.f) g = __builtin_fmaf(a.wd, p, g);  // grad.add_(p, alpha=decay)
+  dot = __builtin_fmaf(g, p0 - p, dot);             // torch.dot(grad, p0 - p)
+  m = m * a.beta1 + k.c1 * g;                       // exp_avg.mul_(beta1).add_(grad, alpha=d * (1 - beta1))
+  v = v * a.beta2 + k.c2 * g * g;                   // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=d d (1 - b2))
+  s = s * a.beta3 + k.c3 * g;                       // s.mul_(beta3).add_(grad, alpha=(d / d0) * dlr)
+  den += fabsf(s);                                  // s.abs().sum()
+}
+
+// pass 1 of one piece: moments and s in and out, master and p0 read only, the piece's (dot, sum |s|) into
+// partials[0], partials[1] (thread t folds its elements in index order, then the fixed block sum)
+template <class G>
+VP_DEV void prodigy_moments_piece(const G* __restrict__ g, const float* __restrict__ pm, const float* __restrict__ p0m,
+                                  float* __restrict__ mm, float* __restrict__ vm, float* __restrict__ sm, int head,
+                                  int n, float* __restrict__ partials, const ProdigyMomentArgs& a,
+                                  const ProdigyMomentCoef& k) {
+  float dot = 0.f, den = 0.f;
+  stream_piece<8>(
+      head, n,
+      [&](int i) {
+        float m = mm[i], v = vm[i], s = sm[i];
+        prodigy_moment_element(to_f32(g[i]), pm[i], p0m[i], m, v, s, dot, den, a, k);
+        mm[i] = m;
+        vm[i] = v;
+        sm[i] = s;
+      },
+      [&](int o) {
+        float g8[8], p[8], p0[8], m[8], v[8], s[8];
+        load8(g + o, g8);
+        load8(pm + o, p);
+        load8(p0m + o, p0);
+        load8(mm + o, m);
+        load8(vm + o, v);
+        load8(sm + o, s);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) prodigy_moment_element(g8[e], p[e], p0[e], m[e], v[e], s[e], dot, den, a, k);
+        store8(mm + o, m);
+        store8(vm + o, v);
+        store8(sm + o, s);
+      });
+  const float sd = block_sum(dot);
+  const float sn = block_sum(den);
+  if (threadIdx.x == 0) {
+    partials[0] = sd;
+    partials[1] = sn;
+  }
+}
+
+struct ProdigyUpdateCoef {
+  float deps, wdl, dlr;  // d eps with the NEW d, -weight_decay dlr (0: no decoupled decay), dlr
+};
+
+VP_DEV ProdigyUpdateCoef prodigy_update_coef(double eps, double weight_decay,
+                                             const vp_prodigy_scalars* __restrict__ ds) {
+#pragma clang fp contract(off)
+  ProdigyUpdateCoef k;
+  k.deps = (float)(ds->d * eps);
+  k.wdl = (float)(-weight_decay * ds->dlr);
+  k.dlr = (float)ds->dlr;
+  return k;
+}
+
+VP_DEV void prodigy_update_element(float& p, float m, float v, const ProdigyUpdateCoef& k) {
+  // the reference's second loop, one rounded operation per torch op
+#pragma clang fp contract(off)
+  const float denom = sqrtf(v) + k.deps;              // exp_avg_sq.sqrt().add_(d * eps)
+  if (k.wdl != 0.f) p = __builtin_fmaf(p, k.wdl, p);  // p.add_(p, alpha=-decay * dlr)
+  p = p - k.dlr * (m / denom);                        // p.addcdiv_(exp_avg, denom, value=-dlr)
+}
+
+// pass 2 of one piece: master in and out, moments read only, bf16(master) into w
+VP_DEV void prodigy_update_piece(float* __restrict__ pm, const float* __restrict__ mm, const float* __restrict__ vm,
+                                 bf16* __restrict__ w, int head, int n, const ProdigyUpdateCoef& k) {
+  stream_piece<8>(
+      head, n,
+      [&](int i) {
+        float p = pm[i];
+        prodigy_update_element(p, mm[i], vm[i], k);
+        pm[i] = p;
+        w[i] = f2bf(p);
+      },
+      [&](int o) {
+        float p[8], m[8], v[8];
+        load8(pm + o, p);
+        load8(mm + o, m);
+        load8(vm + o, v);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) prodigy_update_element(p[e], m[e], v[e], k);
+        store8(pm + o, p);
+        store8(w + o, p);
       });
 }
 

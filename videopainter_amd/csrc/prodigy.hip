@@ -1,0 +1,186 @@
+// Prodigy with fp32 master weights behind the bf16 parameters (gfx950; include/vp_hip.h "Plain Adam and Prodigy"):
+// two streaming passes over the chunk tables of csrc/optim.hip with a one-workgroup finaliser before and between
+// them.  The new d enters the update through d * eps, so the update cannot be folded into the pass that measures d.
+// The passes are the piece functions of optim_common.h; the distance estimate is a block of doubles that only the
+// finaliser writes, with ordinary stores from one thread.  No float atomics: one (dot, sum |s|) pair per chunk, summed
+// in a fixed order in double, so a step is bit-identical run to run.
+#include "optim_common.h"
+
+namespace {
+
+using namespace vp_optim;
+
+// fixed-order sum of doubles over the workgroup, as block_sum; valid in thread 0
+VP_DEV double block_sum_f64(double v) {
+  __shared__ double red64[OT / 64];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  if ((threadIdx.x & 63) == 0) red64[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = 0.0;
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int w = 0; w < OT / 64; ++w) s += red64[w];
+  }
+  __syncthreads();
+  return s;
+}
+
+struct FinalizeArgs {
+  double lr, beta1, beta2, beta3, d0, d_coef, growth_rate;
+  int use_bias_correction;
+};
+
+// ---- phase 0: dlr of the step from the OLD d and the counter vp_optim_finalize has advanced already ----
+__global__ __launch_bounds__(OT) void prodigy_begin_kernel(const FinalizeArgs a,
+                                                           const vp_optim_scalars* __restrict__ sc,
+                                                           vp_prodigy_scalars* __restrict__ ds) {
+#pragma clang fp contract(off)
+  if (threadIdx.x != 0 || sc->skipped) return;
+  double bc = 1.0;
+  if (a.use_bias_correction) {
+    const double step = (double)sc->step;  // k + 1
+    bc = sqrt(1.0 - pow(a.beta2, step)) / (1.0 - pow(a.beta1, step));
+  }
+  ds->dlr = ds->d * a.lr * bc;
+}
+
+// ---- phase 1: the two sums (thread t takes chunks t, t + OT, ... in order, then the fixed block sum) and the d
+// update ----
+__global__ __launch_bounds__(OT) void prodigy_end_kernel(const float* __restrict__ partials, int n,
+                                                         const FinalizeArgs a, vp_optim_scalars* __restrict__ sc,
+                                                         vp_prodigy_scalars* __restrict__ ds) {
+#pragma clang fp contract(off)
+  if (sc->skipped) return;  // (uniform: every thread reads the same word)
+  double dot = 0.0, den = 0.0;
+  for (int i = threadIdx.x; i < n; i += OT) {
+    dot += (double)partials[2 * (int64_t)i];
+    den += (double)partials[2 * (int64_t)i + 1];
+  }
+  dot = block_sum_f64(dot);
+  den = block_sum_f64(den);
+  if (threadIdx.x != 0) return;
+  if (den == 0.0) {  // no progress: pass 2 writes nothing, the counter goes back, d and its numerator stay
+    ds->d_denom = 0.0;
+    ds->no_progress = 1;
+    sc->step = sc->step - 1;
+    return;
+  }
+  double d = ds->d, d_max = ds->d_max;
+  const double num = ds->d_numerator * a.beta3 + (d / a.d0) * ds->dlr * dot;
+  ds->d_numerator = num;
+  ds->d_denom = den;
+  ds->no_progress = 0;
+  if (a.lr > 0.0) {
+    const double d_hat = a.d_coef * num / den;
+    if (d == a.d0) d = d > d_hat ? d : d_hat;
+    d_max = d_max > d_hat ? d_max : d_hat;
+    const double grown = d * a.growth_rate;
+    d = d_max < grown ? d_max : grown;
+    ds->d_hat = d_hat;
+    ds->d_max = d_max;
+    ds->d = d;
+  }
+}
+
+// ---- pass 1 ----
+__global__ __launch_bounds__(OT) void mt_prodigy_moments_kernel(
+    const vp_mt_tensor* __restrict__ tensors, const vp_mt_chunk* __restrict__ chunks, int chunk_begin,
+    const float* __restrict__ master, const float* __restrict__ p0, float* __restrict__ exp_avg,
+    float* __restrict__ exp_avg_sq, float* __restrict__ s, float* __restrict__ partials,
+    const vp_optim_scalars* __restrict__ sc, const vp_prodigy_scalars* __restrict__ ds, const ProdigyMomentArgs a) {
+  if (sc->skipped) return;  // a skipped step writes no state (the finaliser does not read the partials then)
+  const int c = chunk_begin + blockIdx.x;
+  const ChunkRange r = chunk_range(tensors, chunks, c);
+  const bf16* g = (const bf16*)r.t.grad + r.start;
+  const int64_t so = r.t.state_off + r.start;
+  const float* pm = master + so;
+  const float* p0m = p0 + so;
+  float* mm = exp_avg + so;
+  float* vm = exp_avg_sq + so;
+  float* sm = s + so;
+  // one 16-byte phase for every stream of the chunk, else the whole chunk runs scalar
+  int head = head_of(g, r.n);
+  if (((uintptr_t)(pm + head) | (uintptr_t)(p0m + head) | (uintptr_t)(mm + head) | (uintptr_t)(vm + head) |
+       (uintptr_t)(sm + head)) & 15)
+    head = r.n;
+  prodigy_moments_piece(g, pm, p0m, mm, vm, sm, head, r.n, partials + 2 * (int64_t)c, a,
+                        prodigy_moment_coef(a, sc, ds));
+}
+
+// ---- pass 2 ----
+__global__ __launch_bounds__(OT) void mt_prodigy_update_kernel(
+    const vp_mt_tensor* __restrict__ tensors, const vp_mt_chunk* __restrict__ chunks, int chunk_begin,
+    float* __restrict__ master, const float* __restrict__ exp_avg, const float* __restrict__ exp_avg_sq,
+    const vp_optim_scalars* __restrict__ sc, const vp_prodigy_scalars* __restrict__ ds, double eps,
+    double weight_decay, int zero_grads) {
+  const ChunkRange r = chunk_range(tensors, chunks, chunk_begin + blockIdx.x);
+  bf16* g = (bf16*)r.t.grad + r.start;
+  if (zero_grads) zero_piece(g, head_of(g, r.n), r.n);  // (the gradient is not read here: a phase of its own)
+  if (sc->skipped || ds->no_progress) return;           // no state and no parameter is written
+  bf16* w = (bf16*)r.t.param + r.start;
+  const int64_t so = r.t.state_off + r.start;
+  float* pm = master + so;
+  const float* mm = exp_avg + so;
+  const float* vm = exp_avg_sq + so;
+  int head = head_of(w, r.n);
+  if (((uintptr_t)(pm + head) | (uintptr_t)(mm + head) | (uintptr_t)(vm + head)) & 15) head = r.n;
+  prodigy_update_piece(pm, mm, vm, w, head, r.n, prodigy_update_coef(eps, weight_decay, ds));
+}
+
+bool finite_nonneg(double x) { return x >= 0.0 && x <= 1.79769313486231570e308; }
+
+}  // namespace
+
+extern "C" int vp_prodigy_finalize(int32_t phase, const float* partials, int32_t n_chunks, double lr, double beta1,
+                                   double beta2, double beta3, double d0, double d_coef, double growth_rate,
+                                   int32_t use_bias_correction, vp_optim_scalars* scalars, vp_prodigy_scalars* dstate,
+                                   void* stream) {
+  if (!scalars || !dstate || (phase != 0 && phase != 1)) return VP_ERR_ARG;
+  if (!finite_nonneg(lr) || !prodigy_hyper_ok(beta1, beta2, beta3, d0) || !finite_nonneg(d0) || !(d_coef > 0.0) ||
+      !finite_nonneg(d_coef) || !(growth_rate >= 1.0))  // (growth_rate may be +inf: no limit)
+    return VP_ERR_ARG;
+  if (phase == 1 && (n_chunks < 0 || (n_chunks > 0 && !partials))) return VP_ERR_ARG;
+  const FinalizeArgs a{lr, beta1, beta2, beta3, d0, d_coef, growth_rate, use_bias_correction};
+  if (phase == 0)
+    hipLaunchKernelGGL(prodigy_begin_kernel, dim3(1), dim3(OT), 0, (hipStream_t)stream, a, scalars, dstate);
+  else
+    hipLaunchKernelGGL(prodigy_end_kernel, dim3(1), dim3(OT), 0, (hipStream_t)stream, partials, n_chunks, a, scalars,
+                       dstate);
+  VP_CHECK_LAUNCH();
+  return VP_OK;
+}
+
+extern "C" int vp_mt_prodigy_moments_bf16(const vp_mt_tensor* tensors, const vp_mt_chunk* chunks, int32_t chunk_begin,
+                                          int32_t n_chunks, const float* master, const float* p0, float* exp_avg,
+                                          float* exp_avg_sq, float* s, float* partials,
+                                          const vp_optim_scalars* scalars, const vp_prodigy_scalars* dstate,
+                                          double beta1, double beta2, double beta3, double weight_decay, double d0,
+                                          int32_t safeguard_warmup, int32_t use_clip, void* stream) {
+  if (n_chunks < 0 || chunk_begin < 0 || !scalars || !dstate || !master || !p0 || !exp_avg || !exp_avg_sq || !s)
+    return VP_ERR_ARG;
+  if (!prodigy_hyper_ok(beta1, beta2, beta3, d0) || !finite_nonneg(d0) || !finite_nonneg(weight_decay))
+    return VP_ERR_ARG;
+  if (n_chunks == 0) return VP_OK;
+  if (!tensors || !chunks || !partials) return VP_ERR_ARG;
+  const ProdigyMomentArgs a = prodigy_moment_args(beta1, beta2, beta3, weight_decay, d0, safeguard_warmup, use_clip);
+  hipLaunchKernelGGL(mt_prodigy_moments_kernel, dim3(n_chunks), dim3(OT), 0, (hipStream_t)stream, tensors, chunks,
+                     chunk_begin, master, p0, exp_avg, exp_avg_sq, s, partials, scalars, dstate, a);
+  VP_CHECK_LAUNCH();
+  return VP_OK;
+}
+
+extern "C" int vp_mt_prodigy_update_bf16(const vp_mt_tensor* tensors, const vp_mt_chunk* chunks, int32_t chunk_begin,
+                                         int32_t n_chunks, float* master, const float* exp_avg,
+                                         const float* exp_avg_sq, const vp_optim_scalars* scalars,
+                                         const vp_prodigy_scalars* dstate, double eps, double weight_decay,
+                                         int32_t zero_grads, void* stream) {
+  if (n_chunks < 0 || chunk_begin < 0 || !scalars || !dstate || !master || !exp_avg || !exp_avg_sq) return VP_ERR_ARG;
+  if (!finite_nonneg(eps) || !finite_nonneg(weight_decay)) return VP_ERR_ARG;
+  if (n_chunks == 0) return VP_OK;
+  if (!tensors || !chunks) return VP_ERR_ARG;
+  hipLaunchKernelGGL(mt_prodigy_update_kernel, dim3(n_chunks), dim3(OT), 0, (hipStream_t)stream, tensors, chunks,
+                     chunk_begin, master, exp_avg, exp_avg_sq, scalars, dstate, eps, weight_decay, zero_grads);
+  VP_CHECK_LAUNCH();
+  return VP_OK;
+}

@@ -1668,6 +1668,82 @@ def mt_adamw(tensors: torch.Tensor, chunks: torch.Tensor, chunk_begin: int, n_ch
                                      int(use_clip), int(zero_grads), _stream()), "vp_mt_adamw_bf16")
 
 
+def mt_adam(tensors: torch.Tensor, chunks: torch.Tensor, chunk_begin: int, n_chunks: int, master: torch.Tensor,
+            exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, scalars: torch.Tensor, *, lr: float, betas, eps: float,
+            weight_decay: float, use_clip: bool, zero_grads: bool) -> None:
+    """mt_adamw with torch.optim.Adam's decay: an L2 term on the gradient instead of the factor on the master."""
+    for t, n in ((master, "master"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+        _chk(t, n, torch.float32)
+    _chk_scalars(scalars, "mt_adam")
+    N.check(N.lib().vp_mt_adam_bf16(_p(tensors), _p(chunks), chunk_begin, n_chunks, _p(master), _p(exp_avg),
+                                    _p(exp_avg_sq), _p(scalars), lr, betas[0], betas[1], eps, weight_decay,
+                                    int(use_clip), int(zero_grads), _stream()), "vp_mt_adam_bf16")
+
+
+# Prodigy (csrc/prodigy.hip): two passes over the same tables and a one-workgroup finaliser before and between them
+
+def _chk_dstate(dstate: torch.Tensor, who: str) -> None:
+    _chk(dstate, "dstate", torch.float64)
+    if dstate.numel() * 8 < C.sizeof(N.ProdigyScalars) or not dstate.is_contiguous():
+        raise ValueError(f"{who}: the d block is too small")
+
+
+def _chk_pairs(partials: torch.Tensor, n: int, who: str) -> None:
+    _chk(partials, "partials", torch.float32)
+    if n < 0 or partials.numel() < 2 * n or not partials.is_contiguous():
+        raise ValueError(f"{who}: partials hold fewer than 2 x {n} slots")
+
+
+def prodigy_finalize(phase: int, partials: Optional[torch.Tensor], n_chunks: int, scalars: torch.Tensor,
+                     dstate: torch.Tensor, *, lr: float, betas, beta3: float, d0: float, d_coef: float,
+                     growth_rate: float, use_bias_correction: bool) -> None:
+    """phase 0: the step's dlr from the old d.  phase 1: the fixed-order sums of the (dot, sum |s|) pairs of chunks
+    [0, n_chunks) and the d update, into the float64[7] `dstate` block (N.ProdigyScalars)."""
+    if phase not in (0, 1):
+        raise ValueError("prodigy_finalize: phase must be 0 or 1")
+    _chk_scalars(scalars, "prodigy_finalize")
+    _chk_dstate(dstate, "prodigy_finalize")
+    if phase == 1:
+        _chk_pairs(partials, n_chunks, "prodigy_finalize")
+    N.check(N.lib().vp_prodigy_finalize(phase, _p(partials), n_chunks, lr, betas[0], betas[1], beta3, d0, d_coef,
+                                        growth_rate, int(use_bias_correction), _p(scalars), _p(dstate), _stream()),
+            "vp_prodigy_finalize")
+
+
+def mt_prodigy_moments(tensors: torch.Tensor, chunks: torch.Tensor, chunk_begin: int, n_chunks: int,
+                       master: torch.Tensor, p0: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor,
+                       s: torch.Tensor, partials: torch.Tensor, scalars: torch.Tensor, dstate: torch.Tensor, *, betas,
+                       beta3: float, weight_decay: float, d0: float, safeguard_warmup: bool, use_clip: bool) -> None:
+    """Pass 1 of chunks [chunk_begin, chunk_begin + n_chunks) (one parameter group): moments, s and the chunks'
+    (dot, sum |s|) pairs.  `weight_decay` is the coupled decay (0 when decoupled)."""
+    for t, n in ((master, "master"), (p0, "p0"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq"), (s, "s")):
+        _chk(t, n, torch.float32)
+    _chk_scalars(scalars, "mt_prodigy_moments")
+    _chk_dstate(dstate, "mt_prodigy_moments")
+    if chunk_begin < 0:
+        raise ValueError("mt_prodigy_moments: negative chunk_begin")
+    _chk_pairs(partials, chunk_begin + n_chunks, "mt_prodigy_moments")
+    N.check(N.lib().vp_mt_prodigy_moments_bf16(_p(tensors), _p(chunks), chunk_begin, n_chunks, _p(master), _p(p0),
+                                               _p(exp_avg), _p(exp_avg_sq), _p(s), _p(partials), _p(scalars),
+                                               _p(dstate), betas[0], betas[1], beta3, weight_decay, d0,
+                                               int(safeguard_warmup), int(use_clip), _stream()),
+            "vp_mt_prodigy_moments_bf16")
+
+
+def mt_prodigy_update(tensors: torch.Tensor, chunks: torch.Tensor, chunk_begin: int, n_chunks: int,
+                      master: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, scalars: torch.Tensor,
+                      dstate: torch.Tensor, *, eps: float, weight_decay: float, zero_grads: bool) -> None:
+    """Pass 2 of the same chunks: the update with the new d, bf16(master) into the parameters.  `weight_decay` is the
+    decoupled decay (0 when coupled)."""
+    for t, n in ((master, "master"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+        _chk(t, n, torch.float32)
+    _chk_scalars(scalars, "mt_prodigy_update")
+    _chk_dstate(dstate, "mt_prodigy_update")
+    N.check(N.lib().vp_mt_prodigy_update_bf16(_p(tensors), _p(chunks), chunk_begin, n_chunks, _p(master), _p(exp_avg),
+                                              _p(exp_avg_sq), _p(scalars), _p(dstate), eps, weight_decay,
+                                              int(zero_grads), _stream()), "vp_mt_prodigy_update_bf16")
+
+
 # sharded training tail (csrc/zero.hip; videopainter_amd/zero.py builds the tables and runs the collectives between)
 
 def _flat1(t: torch.Tensor, name: str, dtype) -> None:

@@ -1,18 +1,22 @@
-"""The optimizer tail of the training step on the HIP kernels (csrc/optim.hip): gradient norm, clip, and AdamW with
-fp32 master weights behind the bf16 parameters.
+"""The optimizer tail of the training step on the HIP kernels (csrc/optim.hip, csrc/prodigy.hip): gradient norm, clip,
+and the three optimizers the reference's get_optimizer offers (--optimizer adam | adamw | prodigy,
+train/train_cogvideox_inpainting_i2v_video.py:1283-1361), each with fp32 master weights behind the bf16 parameters.
 
 The reference trains under accelerate + DeepSpeed bf16 (train/VideoPainter.sh: --mixed_precision bf16 --optimizer
 AdamW --learning_rate 1e-5 --max_grad_norm 1.0), which keeps fp32 master weights and fp32 moments behind the bf16
 model.  This package's branch parameters are bf16 device tensors with bf16 gradients; stepping a plain optimizer on
-them loses most of an lr = 1e-5 update below half a bf16 ulp.  `FusedAdamW` owns the fp32 masters and moments and
-writes the bf16 parameters back every step.
+them loses most of an lr = 1e-5 update below half a bf16 ulp, and Prodigy's distance estimate, built from p0 - p,
+would be mostly rounding noise.  The optimizers here own the fp32 masters and state and write the bf16 parameters
+back every step.
 
     FusedAdamW(params, ..., max_grad_norm=1.0)   norm + clip + update in three launches (people who own their loop)
+    FusedAdam(params, ...)                       the same with torch.optim.Adam's decay (an L2 term on the gradient)
+    FusedProdigy(params, lr=1.0, ...)            prodigyopt.Prodigy: two passes around the update of d, on the device
     clip_grad_norm_(parameters, max_norm)        norm + in-place scale (accelerator.clip_grad_norm_'s job, :1897)
     get_gradient_norm(parameters)                norm only (the script's helper, :80-90, without its host loop)
 
 Nothing here copies device memory to the host or synchronises: the norm, the clip coefficient, the non-finite flag,
-the step counter and the bias corrections live in a small device block the kernels read.
+the step counter and the bias corrections live in a small device block the kernels read, and so does Prodigy's d.
 
 The data-parallel optimizer (zero.ShardedFusedAdamW) is built on the same parts: `_FlatAdamW` (validation, the flat
 layout of `flat_offsets`, the scalars block, the state-dict checks, the step prologue) and `DeviceTables` (the table
@@ -347,9 +351,9 @@ class _FlatAdamW(torch.optim.Optimizer):
                                                         for a, b in zip(groups, self.param_groups)):
             raise ValueError("loaded state dict has different parameter groups")
 
-    def _full_state(self, state_dict):
-        """[(trainable parameter, its {master, exp_avg, exp_avg_sq})] of a full-format state dict, every shape
-        checked before anything is copied."""
+    def _full_state(self, state_dict, keys=_STATE_KEYS):
+        """[(trainable parameter, its {master, exp_avg, exp_avg_sq, ...: `keys`})] of a full-format state dict, every
+        shape checked before anything is copied."""
         state, out = state_dict["state"], []
         for i, p in self._indexed():
             if p not in self._offs:
@@ -357,7 +361,9 @@ class _FlatAdamW(torch.optim.Optimizer):
             s = state.get(i, state.get(str(i)))
             if s is None:
                 raise ValueError(f"loaded state dict has no state for parameter {i}")
-            for k in _STATE_KEYS:
+            for k in keys:
+                if k not in s:
+                    raise ValueError(f"loaded state dict has no {k} for parameter {i}")
                 if tuple(s[k].shape) != tuple(p.shape):
                     raise ValueError(f"loaded {k} of parameter {i} has shape {tuple(s[k].shape)}")
             out.append((p, s))
@@ -393,6 +399,8 @@ class FusedAdamW(_FlatAdamW):
     not exist.  `load_state_dict` restores masters, moments and the step counter and leaves the bf16 parameters as
     they are (a checkpoint's model weights are bf16(master) already)."""
 
+    _UPDATE = "mt_adamw"  # the kernels.py wrapper of the update pass (FusedAdam: "mt_adam")
+
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
                  *, max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, zero_grads: bool = False):
         super().__init__(params, lr, betas, eps, weight_decay, max_grad_norm, skip_nonfinite, zero_grads)
@@ -420,15 +428,15 @@ class FusedAdamW(_FlatAdamW):
             K.mt_grad_sqnorm(t.tensors, t.chunks, t.n_chunks, t.partials, t.flags)
             K.optim_finalize(t.partials, t.flags, t.n_chunks, self._scalars, max_norm=self.max_grad_norm or 0.0,
                              betas=betas, skip_nonfinite=self.skip_nonfinite, advance_step=True)
-            first = 0
+            first, update = 0, getattr(K, self._UPDATE)
             for group in self.param_groups:  # the active tensors of a group are one run of the list
                 n = sum(p.grad is not None for p in group["params"])
                 c0, nc = t.chunks_of(first, n)
                 first += n
-                K.mt_adamw(t.tensors, t.chunks, c0, nc, self._master, self._exp_avg, self._exp_avg_sq, self._scalars,
-                           lr=float(group["lr"]), betas=betas, eps=float(group["eps"]),
-                           weight_decay=float(group["weight_decay"]), use_clip=self.max_grad_norm is not None,
-                           zero_grads=self.zero_grads)
+                update(t.tensors, t.chunks, c0, nc, self._master, self._exp_avg, self._exp_avg_sq, self._scalars,
+                       lr=float(group["lr"]), betas=betas, eps=float(group["eps"]),
+                       weight_decay=float(group["weight_decay"]), use_clip=self.max_grad_norm is not None,
+                       zero_grads=self.zero_grads)
         return loss
 
     def state_dict(self):
@@ -447,3 +455,200 @@ class FusedAdamW(_FlatAdamW):
         self._restore_options(state_dict)
 
 
+class FusedAdam(FusedAdamW):
+    """torch.optim.Adam (amsgrad=False, maximize=False) for bf16 device parameters with fp32 master weights: the
+    reference's `--optimizer adam`.  Everything is `FusedAdamW`'s — state, launches, keyword-only options, state dict
+    and the differences from torch's — except where the weight decay enters: as an L2 term on the gradient,
+    g = grad (* clip) + weight_decay * master, before the moments (vp_mt_adam_bf16), not as a factor on the master."""
+
+    _UPDATE = "mt_adam"
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
+                 *, max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, zero_grads: bool = False):
+        super().__init__(params, lr, betas, eps, weight_decay, max_grad_norm=max_grad_norm,
+                         skip_nonfinite=skip_nonfinite, zero_grads=zero_grads)
+
+
+_PRODIGY_KEYS = ("master", "exp_avg", "exp_avg_sq", "s", "p0")
+_D_FIELDS = ("d", "d_max", "d_hat", "d_numerator", "d_denom", "dlr")  # N.ProdigyScalars, its doubles in order
+
+
+class FusedProdigy(_FlatAdamW):
+    """prodigyopt.Prodigy (1.0, slice_p = 1, no FSDP) for bf16 device parameters with fp32 master weights: the
+    reference's `--optimizer prodigy`.  Its distance estimate is built from p0 - p, which on bf16 parameters is mostly
+    rounding noise; here p is the fp32 master.
+
+    State lives in five flat fp32 device buffers (master, exp_avg, exp_avg_sq, s, p0 — the initial master);
+    `state[p]` exposes per-parameter views of them plus the shared device step counter.  d, d_max, d_hat,
+    d_numerator, d_denom and the dlr of the last step are doubles in a device block (`d_block`, N.ProdigyScalars; the
+    reference keeps them in Python floats), read through the properties of the same names; `no_progress` is 1 after
+    a step that found d_denom == 0.  `step()` is gradient norm, its finaliser, dlr from the old d, pass 1 per group
+    (moments, s, one (dot, sum |s|) pair per chunk), the d update, pass 2 per group (the update with the new d in
+    d * eps) — no device-to-host copy, no synchronisation, bit-identical run to run.
+
+    `max_grad_norm`, `skip_nonfinite` and `zero_grads` mean what they mean on `FusedAdamW`; a skipped step leaves all
+    five buffers, the d block and the counter as they were.
+
+    Differences from prodigyopt's: lr, betas and beta3 must be the same in every parameter group, checked every step
+    (prodigyopt also lets a group sit at lr = 0; that is not built), weight_decay and eps may differ; one step
+    counter; decouple, use_bias_correction, safeguard_warmup, d0, d_coef and growth_rate belong to the optimizer, not
+    to a group; a step with d_denom == 0 changes no parameter, not the counter and nothing of the d block but d_denom
+    and `no_progress` (the moments and s were updated, as there); parameters must be bf16, contiguous, on one
+    device; slice_p and fsdp_in_use do not exist."""
+
+    def __init__(self, params, lr: float = 1.0, betas=(0.9, 0.999), beta3: Optional[float] = None, eps: float = 1e-8,
+                 weight_decay: float = 0.0, decouple: bool = True, use_bias_correction: bool = False,
+                 safeguard_warmup: bool = False, d0: float = 1e-6, d_coef: float = 1.0,
+                 growth_rate: float = float("inf"), *, max_grad_norm: Optional[float] = None,
+                 skip_nonfinite: bool = False, zero_grads: bool = False):
+        if not 0.0 < d0 < float("inf"):
+            raise ValueError(f"Invalid d0 value: {d0}")
+        if not 0.0 < d_coef < float("inf"):
+            raise ValueError(f"Invalid d_coef value: {d_coef}")
+        if not growth_rate >= 1.0:
+            raise ValueError(f"Invalid growth_rate value: {growth_rate}")
+        if beta3 is not None and not 0.0 <= beta3 < 1.0:
+            raise ValueError(f"Invalid beta3 value: {beta3}")
+        params = list(params)
+        groups = [g for g in params if isinstance(g, dict)]
+        if len({float(g.get("lr", lr)) for g in groups}) > 1 or len({g.get("beta3", beta3) for g in groups}) > 1:
+            raise ValueError("FusedProdigy: lr and beta3 must be the same in every parameter group")
+        super().__init__(params, lr, betas, eps, weight_decay, max_grad_norm, skip_nonfinite, zero_grads)
+        self.defaults["beta3"] = beta3
+        for g in self.param_groups:
+            g.setdefault("beta3", beta3)
+        self.decouple, self.use_bias_correction = bool(decouple), bool(use_bias_correction)
+        self.safeguard_warmup = bool(safeguard_warmup)
+        self.d0, self.d_coef, self.growth_rate = float(d0), float(d_coef), float(growth_rate)
+        self._check_shared()
+        self._alloc_scalars()
+        self._d_block = torch.tensor([self.d0] * 3 + [0.0] * 4, dtype=torch.float64).to(self._device)
+        self._master = torch.zeros(max(self.total, 1), device=self._device, dtype=torch.float32)
+        self._exp_avg = torch.zeros_like(self._master)
+        self._exp_avg_sq = torch.zeros_like(self._master)
+        self._s = torch.zeros_like(self._master)
+        self._tables = MultiTensorTables(self._device)
+        self._pairs = None  # fp32 [2 * chunks]: pass 1's (dot, sum |s|) of every chunk
+        with torch.no_grad():
+            for p in self._params:
+                o, n = self._offs[p], p.numel()
+                self._master[o:o + n].copy_(p.detach().reshape(-1))
+            self._p0 = self._master.clone()
+            for p in self._params:
+                o, n = self._offs[p], p.numel()
+                self.state[p] = dict(step=self._scalars[3], **{k: getattr(self, "_" + k)[o:o + n].view(p.shape)
+                                                               for k in _PRODIGY_KEYS})
+
+    def _check_shared(self) -> Tuple[float, float]:
+        """(lr, beta3) of the step: what every group must share besides the betas."""
+        g0 = self.param_groups[0]
+        for g in self.param_groups:
+            if float(g["lr"]) != float(g0["lr"]) or g["beta3"] != g0["beta3"]:
+                raise ValueError("FusedProdigy: lr and beta3 must be the same in every parameter group")
+        lr = float(g0["lr"])
+        beta3 = float(g0["betas"][1]) ** 0.5 if g0["beta3"] is None else float(g0["beta3"])
+        if not 0.0 <= lr < float("inf"):
+            raise ValueError(f"Invalid learning rate: {lr}")
+        return lr, beta3
+
+    # the d block of the last step (0-dim float64 device tensors)
+    @property
+    def d(self) -> torch.Tensor:
+        return self._d_block[0]
+
+    @property
+    def d_max(self) -> torch.Tensor:
+        return self._d_block[1]
+
+    @property
+    def d_hat(self) -> torch.Tensor:
+        return self._d_block[2]
+
+    @property
+    def d_numerator(self) -> torch.Tensor:
+        return self._d_block[3]
+
+    @property
+    def d_denom(self) -> torch.Tensor:
+        return self._d_block[4]
+
+    @property
+    def dlr(self) -> torch.Tensor:
+        return self._d_block[5]
+
+    @property
+    def no_progress(self) -> torch.Tensor:
+        return self._d_block.view(torch.int32)[12]
+
+    @property
+    def d_block(self) -> torch.Tensor:
+        """The whole float64[7] block (N.ProdigyScalars; the last slot holds the int32 `no_progress`)."""
+        return self._d_block
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        from . import kernels as K
+        loss, betas = self._begin_step(closure)
+        lr, beta3 = self._check_shared()
+        params = [p for g in self.param_groups for p in g["params"] if p.grad is not None]
+        t = self._tables
+        use_clip = self.max_grad_norm is not None
+        fin = dict(lr=lr, betas=betas, beta3=beta3, d0=self.d0, d_coef=self.d_coef, growth_rate=self.growth_rate,
+                   use_bias_correction=self.use_bias_correction)
+        with torch.cuda.device(self._device):
+            t.update([p.grad for p in params], params, [self._offs[p] for p in params])
+            if self._pairs is None or self._pairs.numel() < 2 * t.n_chunks:
+                self._pairs = torch.empty(max(2 * t.n_chunks, 2048), device=self._device, dtype=torch.float32)
+            K.mt_grad_sqnorm(t.tensors, t.chunks, t.n_chunks, t.partials, t.flags)
+            K.optim_finalize(t.partials, t.flags, t.n_chunks, self._scalars, max_norm=self.max_grad_norm or 0.0,
+                             betas=betas, skip_nonfinite=self.skip_nonfinite, advance_step=True)
+            K.prodigy_finalize(0, None, 0, self._scalars, self._d_block, **fin)
+            runs, first = [], 0
+            for group in self.param_groups:  # the active tensors of a group are one run of the list
+                n = sum(p.grad is not None for p in group["params"])
+                runs.append((group, *t.chunks_of(first, n)))
+                first += n
+            for group, c0, nc in runs:
+                K.mt_prodigy_moments(t.tensors, t.chunks, c0, nc, self._master, self._p0, self._exp_avg,
+                                     self._exp_avg_sq, self._s, self._pairs, self._scalars, self._d_block,
+                                     betas=betas, beta3=beta3,
+                                     weight_decay=0.0 if self.decouple else float(group["weight_decay"]), d0=self.d0,
+                                     safeguard_warmup=self.safeguard_warmup, use_clip=use_clip)
+            K.prodigy_finalize(1, self._pairs, t.n_chunks, self._scalars, self._d_block, **fin)
+            for group, c0, nc in runs:
+                K.mt_prodigy_update(t.tensors, t.chunks, c0, nc, self._master, self._exp_avg, self._exp_avg_sq,
+                                    self._scalars, self._d_block, eps=float(group["eps"]),
+                                    weight_decay=float(group["weight_decay"]) if self.decouple else 0.0,
+                                    zero_grads=self.zero_grads)
+        return loss
+
+    def state_dict(self):
+        """{"state": {index: {master, exp_avg, exp_avg_sq, s, p0}}, "param_groups": [...], "step": int, "prodigy":
+        {the d block's values and the optimizer-wide options}} — clones; reading the step counter and the d block are
+        the device-to-host copies of this class (not on the step path)."""
+        state = {i: {k: self.state[p][k].detach().clone() for k in _PRODIGY_KEYS}
+                 for i, p in self._indexed() if p in self._offs}
+        block = self._d_block.cpu()
+        prodigy = dict(zip(_D_FIELDS, block[:6].tolist()), no_progress=int(block.view(torch.int32)[12]),
+                       decouple=self.decouple, use_bias_correction=self.use_bias_correction,
+                       safeguard_warmup=self.safeguard_warmup, d0=self.d0, d_coef=self.d_coef,
+                       growth_rate=self.growth_rate)
+        return {"state": state, "param_groups": self._groups_dict(), "step": int(self._scalars[3].item()),
+                "prodigy": prodigy}
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict):
+        self._check_groups(state_dict)
+        if "prodigy" not in state_dict:
+            raise ValueError("loaded state dict has no d block (not a FusedProdigy state dict)")
+        pr = state_dict["prodigy"]
+        for p, s in self._full_state(state_dict, _PRODIGY_KEYS):
+            for k in _PRODIGY_KEYS:
+                self.state[p][k].copy_(s[k])
+        self._restore_options(state_dict)
+        self.decouple, self.use_bias_correction = bool(pr["decouple"]), bool(pr["use_bias_correction"])
+        self.safeguard_warmup = bool(pr["safeguard_warmup"])
+        self.d0, self.d_coef, self.growth_rate = float(pr["d0"]), float(pr["d_coef"]), float(pr["growth_rate"])
+        block = torch.tensor([float(pr[k]) for k in _D_FIELDS] + [0.0], dtype=torch.float64)
+        block.view(torch.int32)[12] = int(pr["no_progress"])
+        self._d_block.copy_(block.to(self._device))
