@@ -734,29 +734,39 @@ int vp_transpose_bf16(const void* x, int64_t ldx, int64_t x_bs, void* y, int64_t
 int vp_colsum_bf16(const void* a, int64_t lda, const void* b, int64_t ldb, int32_t rows, int32_t cols, int32_t Ntok,
                    int32_t text_len, float* out, void* stream);
 /* CogVideoXLayerNormZero backward (normalization.py:373-379): with n = bf16(LN(x) w + b) and the forward's
- * y = bf16(bf16(n (1 + scale)) + shift) (scale / shift = chunks scale_v / shift_v of mod for video rows, _t for
- * text rows), dx += LN'(dy (1 + scale) w) (bf16 in place); optionally writes n, dn = dy (1 + scale) and LN(x) (bf16
- * [rows, D]) for the parameter column sums. */
+ * y = bf16(bf16(n s1) + shift), s1 = bf16(1 + scale) (scale / shift = chunks scale_v / shift_v of mod for video
+ * rows, _t for text rows), dx += LN'(dy s1 w) (bf16 in place, one rounding of old + delta); optionally writes n,
+ * dn = dy s1 and LN(x) without the affine (bf16 [rows, D]) for the parameter column sums.  x, dy, dx and the three
+ * outputs are contiguous [B * Ntok, D]; D % 8 == 0, D <= 4096, mod_bstride % 8 == 0 (else VP_ERR_ARG). */
 int vp_adaln_bwd_bf16(const void* x, const void* dy, void* dx, int32_t B, int32_t Ntok, int32_t D, int32_t text_len,
                       const void* ln_w, const void* ln_b, float eps, const void* mod, int64_t mod_bstride,
                       int32_t shift_v, int32_t scale_v, int32_t shift_t, int32_t scale_t, void* n_out, void* dn_out,
                       void* xhat_out, void* stream);
 /* y = bf16(x * gate) with gate = chunk chunk_v (video rows) / chunk_t (text rows) of mod [B, *] (the gated
- * residual's gradient into its branch, cogvideox_transformer_3d.py:161-162, 179-180) */
+ * residual's gradient into its branch, cogvideox_transformer_3d.py:161-162, 179-180); D, ldx, ldy and mod_bstride
+ * are multiples of 8 (else VP_ERR_ARG) */
 int vp_rowscale_bf16(const void* x, int64_t ldx, void* y, int64_t ldy, int32_t rows, int32_t Ntok, int32_t D,
                      int32_t text_len, const void* mod, int64_t mod_bstride, int32_t chunk_v, int32_t chunk_t,
                      void* stream);
-/* GELU(tanh) forward h = gelu(z) and backward dz = dh * gelu'(z) (activations.py:65-90), elementwise bf16 */
+/* GELU(tanh) forward h = gelu(z) and backward dz = dh * gelu'(z) (activations.py:65-90), elementwise bf16,
+ * n % 8 == 0.  With u = sqrt(2 / pi) (z + 0.044715 z^3) and s = 1 / (1 + exp(-2 u)):  gelu = z s,
+ * gelu' = s + z s (1 - s) 2 sqrt(2 / pi) (1 + 3 * 0.044715 z^2), each to the bf16 rounding of the exact value
+ * (relative, also where the value is tiny: z << 0).  Domain: vp_gelu_bf16 takes every finite z (it saturates to z /
+ * -0); vp_gelu_bwd_bf16 is defined for |z| <= 2^60 (gelu' is exactly 1 / 0 from |z| ~ 10 on); beyond that the
+ * result is unspecified: once z^2 overflows fp32 (|z| >= 2^64) the polynomial factor is inf against a zero and the
+ * result is NaN, as with torch's own fp32 formula.  A pre-activation of that size is not a trained network's. */
 int vp_gelu_bf16(const void* z, void* h, int64_t n, void* stream);
 int vp_gelu_bwd_bf16(const void* dh, const void* z, void* dz, int64_t n, void* stream);
 /* y = bf16(a + alpha b) (gradient accumulation), n % 8 == 0 */
 int vp_axpy_bf16(const void* a, const void* b, float alpha, void* y, int64_t n, void* stream);
-/* y = silu(x) and y = dy * silu'(x) (the AdaLN / time-embedding SiLU) */
+/* y = silu(x) = x s and y = dy * silu'(x) = dy s (1 + x (1 - s)), s = 1 / (1 + exp(-x)) (the AdaLN / time-embedding
+ * SiLU); every finite x: both saturate (silu to x / -0, silu' to 1 / 0) without forming inf * 0 */
 int vp_silu_bf16(const void* x, void* y, int64_t n, void* stream);
 int vp_silu_bwd_bf16(const void* dy, const void* x, void* y, int64_t n, void* stream);
 /* backward of vp_head_norm_rope_bf16 (LayerNorm(64) + RoPE on rows >= text_len; no token mask): x_in = the
- * pre-norm q or k, dy = the gradient of the normed + rotated output, dx = the gradient of x_in; dln_w / dln_b: fp32
- * [64] accumulated (atomics) or both NULL */
+ * pre-norm q or k, dy = the gradient of the normed + rotated output, dx = the gradient of x_in (dx may be dy: each
+ * head vector is read before it is written, by the same lanes); dln_w / dln_b: fp32 [64] accumulated (atomics) or
+ * both NULL.  Every row and batch stride is a multiple of 4 elements (else VP_ERR_ARG). */
 int vp_head_norm_rope_bwd_bf16(const void* x_in, int64_t ld_in, int64_t bs_in, const void* dy, int64_t ld_dy,
                                int64_t bs_dy, void* dx, int64_t ld_dx, int64_t bs_dx, int32_t B, int32_t Ntok,
                                int32_t H, int32_t text_len, const void* ln_w, const void* ln_b, float eps,

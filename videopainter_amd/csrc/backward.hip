@@ -376,6 +376,7 @@ extern "C" int vp_adaln_bwd_bf16(const void* x, const void* dy, void* dx, int32_
                                  int32_t scale_t, void* n_out, void* dn_out, void* xhat_out, void* stream) {
   if (!x || !dy || !dx || !ln_w || !ln_b || !mod || B <= 0 || Ntok <= 0 || D <= 0 || (D % 8) || D > 4096)
     return VP_ERR_ARG;
+  if (mod_bstride % 8) return VP_ERR_ARG;  // mod rows are read as 16-byte chunks
   const int rows = B * Ntok;
   const int nch = (D / 8 + 63) / 64;
   hipStream_t s = (hipStream_t)stream;
@@ -397,6 +398,7 @@ extern "C" int vp_rowscale_bf16(const void* x, int64_t ldx, void* y, int64_t ldy
                                 int32_t D, int32_t text_len, const void* mod, int64_t mod_bstride, int32_t chunk_v,
                                 int32_t chunk_t, void* stream) {
   if (!x || !y || !mod || rows <= 0 || Ntok <= 0 || D <= 0 || (D % 8) || (ldx % 8) || (ldy % 8)) return VP_ERR_ARG;
+  if (mod_bstride % 8) return VP_ERR_ARG;  // mod rows are read as 16-byte chunks
   hipLaunchKernelGGL(rowscale_kernel, dim3(grid_for((int64_t)rows * (D / 8))), dim3(256), 0, (hipStream_t)stream,
                      (const bf16*)x, ldx, (bf16*)y, ldy, rows, Ntok, D, text_len, (const bf16*)mod, mod_bstride,
                      chunk_v, chunk_t);
@@ -451,6 +453,7 @@ extern "C" int vp_head_norm_rope_bwd_bf16(const void* x_in, int64_t ld_in, int64
   if (!x_in || !dy || !dx || !ln_w || !ln_b || B <= 0 || Ntok <= 0 || H <= 0) return VP_ERR_ARG;
   if ((dln_w == nullptr) != (dln_b == nullptr)) return VP_ERR_ARG;
   if ((ld_in % 4) || (ld_dy % 4) || (ld_dx % 4)) return VP_ERR_ARG;
+  if ((bs_in % 4) || (bs_dy % 4) || (bs_dx % 4)) return VP_ERR_ARG;  // 8-byte loads / stores at every batch row
   const int64_t nvec = (int64_t)B * Ntok * H;
   const int64_t grid = (nvec + 63) / 64;
   if (grid > 0x7fffffff) return VP_ERR_ARG;

@@ -41,21 +41,26 @@ VP_DEV float gelu_tanh(float x) {
 }
 
 // d/dx of the tanh-form GELU (torch's gelu_backward, approximate="tanh"), fp32 from the bf16 pre-activation.
-// tanh(u) = 1 - 2 / (1 + 2^(2 u log2 e)) on v_exp_f32 + v_rcp_f32 (absolute error ~1e-7, far below the bf16 output's
-// ulp; saturates to +-1 through inf / 0): the libm tanhf it replaces cost ~10x the VALU, which in the FF2 dgrad GEMM's
-// epilogue (VP_EPI_GELU_BWD, not overlapped with MFMA) was as slow as the separate elementwise pass.
+// With u = k0 (x + k1 x^3) and s = sigmoid(2 u) = (1 + tanh u) / 2:  gelu = x s,  gelu' = s + x s (1 - s) 2 u'.
+// s = 1 / (1 + 2^(-2 u log2 e)) on v_exp_f32 + v_rcp_f32 keeps its RELATIVE accuracy on the negative side, where
+// gelu' itself is tiny: the textbook 0.5 (1 + tanh u) + 0.5 x (1 - tanh^2 u) u' cancels there (1 + tanh u is 0 in
+// fp32 below x ~ -4.9 and has lost the bf16 output's 8 bits by x ~ -4.2, while gelu' is still ~1e-5 .. 1e-6: small
+// against 1, not against the other gradients it is multiplied with).  On the positive side 1 - s carries the ~1e-7
+// absolute error next to a result of ~1.  Saturates through 0 / inf: s = 1, 1 - s = 0 -> 1;  s = 0 -> -0.
+// The product is ordered ((x (1 - s)) s) u' so that no intermediate overflows while x^2 is finite; from
+// |x| >= 2^64 on u' = inf meets a zero and the result is NaN (domain: include/vp_hip.h, vp_gelu_bwd_bf16).
+// The libm tanhf form cost ~10x the VALU, which in the FF2 dgrad GEMM's epilogue (VP_EPI_GELU_BWD, not overlapped
+// with MFMA) was as slow as the separate elementwise pass.
 // Every fused multiply-add is explicit and contraction is off, so the standalone pass and the GEMM epilogue compile
 // to the same arithmetic whatever the surrounding code (they are compared bit for bit).
 VP_DEV float gelu_grad(float x) {
 #pragma clang fp contract(off)
   const float k0 = 0.7978845608028654f, k1 = 0.044715f;
   const float x2 = x * x;
-  const float u = k0 * __builtin_fmaf(k1 * x2, x, x);  // k0 (x + k1 x^3)
-  const float t = __builtin_fmaf(-2.f, __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(u * (2.f * 1.4426950408889634f))),
-                                 1.f);
-  const float dt = __builtin_fmaf(-t, t, 1.f);                 // 1 - t^2
-  const float pd = k0 * __builtin_fmaf(3.f * k1, x2, 1.f);     // k0 (1 + 3 k1 x^2)
-  return __builtin_fmaf(0.5f, 1.f + t, (0.5f * x) * dt * pd);
+  const float v = __builtin_fmaf(k1 * x2, x, x);  // x + k1 x^3
+  const float s = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(v * (-2.f * k0 * 1.4426950408889634f)));
+  const float pd = (2.f * k0) * __builtin_fmaf(3.f * k1, x2, 1.f);  // 2 k0 (1 + 3 k1 x^2)
+  return __builtin_fmaf((x * (1.f - s)) * s, pd, s);
 }
 
 VP_DEV float silu(float x) { return x / (1.f + __expf(-x)); }
