@@ -33,7 +33,7 @@ extern "C" {
 #define VP_ERR_UNSUPPORTED 1001
 
 /* ABI version: bump when any struct layout or signature below changes. */
-#define VP_ABI_VERSION 27
+#define VP_ABI_VERSION 28
 int vp_abi_version(void);
 /* "<sha256 of sources + flags>:<sha256 of the compiler version>" of the build (no reference counterpart) */
 const char* vp_build_digest(void);
@@ -138,7 +138,8 @@ typedef struct vp_gemm_desc {
   /* Optional second output for the training forward (ABI 17; NULL: none), bf16, row m of the GEMM at aux + m * ld_aux
    * (no row remap): VP_EPI_BIAS_GELU writes the pre-activation rnd(acc + bias) there (the GELU's backward input, so
    * no separate vp_gelu_bf16 pass); VP_EPI_BIAS_QKNORM_ROPE writes the pre-norm rnd(acc + bias) of segments 0 / 1
-   * (q | k, columns [0, 2 n_seg)) there (the LayerNorm backward's input).  Other epilogues: VP_ERR_ARG. */
+   * (q | k, columns [0, 2 n_seg)) there (the LayerNorm backward's input); vp_gemm_mx_fp8's VP_EPI_BIAS_GELU_MXFP8
+   * writes the pre-activation as VP_EPI_BIAS_GELU does (ABI 28).  Other epilogues: VP_ERR_ARG. */
   void* aux;
   int64_t ld_aux;
 } vp_gemm_desc;
@@ -193,8 +194,16 @@ int vp_mx_quantize_heads_bf16(const void* x, void* q, int64_t ld_out, void* scal
 /* out = epilogue(A · Wᵀ) with A and W in MX-FP8.  base: as vp_gemm_desc with A / W[] pointing at the e4m3
  * elements (lda in BYTES; W rows are K bytes), epilogues VP_EPI_BIAS .. VP_EPI_BIAS_ADDROWS writing bf16 C, or
  * VP_EPI_BIAS_GELU_MXFP8: C = MX-quantise(rnd(gelu_tanh(rnd(acc + bias)))) written as e4m3 [M][N] (ldc in bytes)
- * plus c_scale (the FF1 -> FF2 hand-off stays in fp8).  K % 128 == 0, N % 256 == 0. */
+ * plus c_scale (the FF1 -> FF2 hand-off stays in fp8).  K % 128 == 0, N % 256 == 0.
+ * ABI 28, the training step through frozen fp8 blocks (forward and dgrad run against constant weights):
+ *   - VP_EPI_BIAS_GELU_MXFP8 with base.aux / ld_aux set also stores the bf16 pre-activation z = rnd(acc + bias) to
+ *     aux (ld_aux >= N, % 8), bit-equal to what VP_EPI_BIAS writes; the MX C / c_scale bytes are those without aux.
+ *     aux with any other epilogue: VP_ERR_ARG.
+ *   - VP_EPI_GELU_BWD_MXFP8: C = MX-quantise(rnd(rnd(acc + bias) * gelu_tanh'(Z[m, n]))) as e4m3 [M][N] plus c_scale,
+ *     Z = base.R (bf16 [M][N], row m at ldr >= N, % 8; no row remap) as VP_EPI_GELU_BWD reads it: the FF2 dgrad whose
+ *     output is the FF1 dgrad's MX operand, byte for byte vp_mx_quantize_bf16 of the bf16 VP_EPI_GELU_BWD result. */
 #define VP_EPI_BIAS_GELU_MXFP8 5
+#define VP_EPI_GELU_BWD_MXFP8 8
 typedef struct vp_gemm_mx_desc {
   vp_gemm_desc base;
   const void* a_scale;
@@ -748,6 +757,13 @@ int vp_adaln_bwd_bf16(const void* x, const void* dy, void* dx, int32_t B, int32_
 int vp_rowscale_bf16(const void* x, int64_t ldx, void* y, int64_t ldy, int32_t rows, int32_t Ntok, int32_t D,
                      int32_t text_len, const void* mod, int64_t mod_bstride, int32_t chunk_v, int32_t chunk_t,
                      void* stream);
+/* vp_rowscale_bf16 writing MX rows (ABI 28): q (e4m3 [rows][D], row stride ld_out bytes) and scales (the MX tile
+ * layout above) are byte for byte vp_mx_quantize_bf16(vp_rowscale_bf16(x)) — the gated residual's branch gradient as
+ * the operand of an MX dgrad GEMM.  D % 128 == 0, ldx and mod_bstride multiples of 8, ld_out >= D and a multiple of
+ * 8, x and mod 16-byte aligned (else VP_ERR_ARG). */
+int vp_rowscale_mx_fp8(const void* x, int64_t ldx, void* q, int64_t ld_out, void* scales, int32_t rows, int32_t Ntok,
+                       int32_t D, int32_t text_len, const void* mod, int64_t mod_bstride, int32_t chunk_v,
+                       int32_t chunk_t, void* stream);
 /* GELU(tanh) forward h = gelu(z) and backward dz = dh * gelu'(z) (activations.py:65-90), elementwise bf16,
  * n % 8 == 0.  With u = sqrt(2 / pi) (z + 0.044715 z^3) and s = 1 / (1 + exp(-2 u)):  gelu = z s,
  * gelu' = s + z s (1 - s) 2 sqrt(2 / pi) (1 + 3 * 0.044715 z^2), each to the bf16 rounding of the exact value

@@ -2,6 +2,7 @@
 
     python tools/bench_train.py [--steps K] [--warmup W] [--height 60 --width 90]
                                 [--optimizer none|torch|fused|adam|prodigy|sharded] [--loss]
+                                [--fp8-gemm [ffn,qkv,out]] [--rounds R]
 
 One step = the reference's training iteration (train/train_cogvideox_inpainting_i2v_video.py:1856-1892 with the
 launch script train/VideoPainter.sh: 49 frames 480x720 -> latent 13x60x90, batch 1, bf16, branch_layer_num 2,
@@ -19,6 +20,14 @@ draws its own latents, and verify_replicas runs after the last step: "replicas_i
 rank 0 prints).  --loss replaces the synthetic loss gradient with inpainting_v_loss(...).backward()
 (:1879-1892).  Default: neither.  Random-init weights, synthetic latents.  Prints one JSON line; optimizer_ms = HIP
 events around optimizer.step().
+
+--fp8-gemm [SUBSET] (default when given: ffn,qkv,out) is the A/B of training through the frozen transformer on the
+MX-FP8 GEMMs (forward and dgrad; the attention stays bf16): the bf16 arm and the fp8 arm run INTERLEAVED in this one
+process, --rounds rounds (at least 5) of --steps steps per arm after --warmup steps of each, and the JSON line holds
+per arm the step time (median, min, max over all timed steps), the per-class HIP-event split of one more step (gemm,
+gemm_mx, attention, attention_bwd) and the peak memory of the arm's timed steps, plus whether the two arms' ranges
+overlap.  Both arms' cached transposed dgrad weights (bf16 and MX) stay resident throughout, so the peaks compare
+the arms' activations, not their weight caches.
 """
 from __future__ import annotations
 
@@ -48,6 +57,63 @@ def flops(ntok: int, nv: int) -> dict:
     return dict(forward=float(fwd), backward=float(dgrad + wgrad), total=float(fwd + dgrad + wgrad))
 
 
+def fp8_gemm_ab(args, tr, step, K) -> dict:
+    """The interleaved A/B of --fp8-gemm: the arms differ in the blocks' MX weights alone (quantised once, then
+    attached and detached per arm)."""
+    import statistics
+    which = set(filter(None, args.fp8_gemm.split(",")))
+    if not which or which - {"ffn", "qkv", "out"}:
+        raise SystemExit(f"--fp8-gemm takes a subset of ffn,qkv,out, got {args.fp8_gemm!r}")
+    if args.optimizer == "sharded":
+        raise SystemExit("--fp8-gemm is a single-process A/B")
+    rounds = max(5, args.rounds)
+    tr.requires_grad_(False)
+    tr.enable_fp8(ffn="ffn" in which, attention=False, qkv="qkv" in which, out="out" in which)
+    blocks = list(tr.transformer_blocks)
+    mx = [(b.ff_mx, b.qkv_mx, b.out_mx) for b in blocks]
+
+    def arm(fp8: bool):
+        for b, m in zip(blocks, mx):
+            b.ff_mx, b.qkv_mx, b.out_mx = m if fp8 else (None, None, None)
+
+    arms = (("bf16", False), ("fp8", True))
+    for name, fp8 in arms:  # warm-up: also builds each arm's transposed dgrad weights
+        arm(fp8)
+        for _ in range(max(1, args.warmup)):
+            step()
+    torch.cuda.synchronize()
+    ms = {n: [] for n, _ in arms}
+    peak = {n: 0.0 for n, _ in arms}
+    for r in range(rounds):
+        for name, fp8 in arms:
+            arm(fp8)
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            for _ in range(args.steps):
+                t0 = time.perf_counter()
+                step()
+                torch.cuda.synchronize()
+                ms[name].append((time.perf_counter() - t0) * 1e3)
+            peak[name] = max(peak[name], torch.cuda.max_memory_allocated() / 2 ** 30)
+            print(f"round {r} {name}: {ms[name][-args.steps:]}", file=sys.stderr, flush=True)
+    res = dict(metric="training step, bf16 against the frozen transformer on the MX-FP8 GEMMs (49f 480x720, B=1)",
+               fp8_gemm=sorted(which), rounds=rounds, steps_per_round=args.steps, unit="ms/step", arms={})
+    classes = ("gemm", "gemm_mx", "attention", "attention_bwd")
+    for name, fp8 in arms:
+        arm(fp8)
+        a = dict(median=statistics.median(ms[name]), min=min(ms[name]), max=max(ms[name]), peak_mem_gib=peak[name])
+        with K.timed_launches(*classes) as tl:
+            step()
+        torch.cuda.synchronize()
+        a["classes_ms"] = {n: tl.mean_ms(n) * tl.count(n) for n in classes}
+        a["counts"] = {n: tl.count(n) for n in classes}
+        res["arms"][name] = a
+    b, f = res["arms"]["bf16"], res["arms"]["fp8"]
+    res["ranges_overlap"] = not (f["max"] < b["min"] or b["max"] < f["min"])
+    res["fp8_minus_bf16_median_ms"] = f["median"] - b["median"]
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=3)
@@ -58,6 +124,10 @@ def main():
     ap.add_argument("--loss", action="store_true",
                     help="inpainting_v_loss(...).backward() instead of out.backward(dout)")
     ap.add_argument("--classes", action="store_true", help="per-class HIP-event timing pass afterwards")
+    ap.add_argument("--fp8-gemm", nargs="?", const="ffn,qkv,out", default=None, metavar="SUBSET",
+                    help="interleaved A/B: bf16 against the frozen transformer on the MX-FP8 GEMMs (subset of "
+                         "ffn,qkv,out; default all three)")
+    ap.add_argument("--rounds", type=int, default=5, help="--fp8-gemm: interleaved rounds (at least 5)")
     args = ap.parse_args()
     from videopainter_amd import CogVideoXTransformer3DModel, CogvideoXBranchModel, device_scope
     from videopainter_amd import kernels as K
@@ -151,6 +221,11 @@ def main():
         for p in params:
             p.grad = None
 
+    if args.fp8_gemm is not None:
+        res = fp8_gemm_ab(args, tr, step, K)
+        res.update(ntok=ntok, flop_per_step=flops(ntok, nv))
+        print(json.dumps(res))
+        return
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()

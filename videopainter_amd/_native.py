@@ -11,7 +11,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VP_HIP_LIB", os.path.join(_HERE, "_lib", "libvp_hip.so"))
-ABI_VERSION = 27
+ABI_VERSION = 28
 
 vp = C.c_void_p
 i32 = C.c_int32
@@ -130,6 +130,7 @@ class ZeroRecord(C.Structure):
 
 (EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_SCALE, EPI_GATED, EPI_BIAS_ADDROWS, EPI_BIAS_GELU_MXFP8, EPI_BIAS_QKNORM_ROPE,
  EPI_GELU_BWD) = range(8)
+EPI_GELU_BWD_MXFP8 = 8  # vp_gemm_mx_fp8 only (ABI 28): the FF2 dgrad writing the FF1 dgrad's MX operand
 
 # name -> (restype, argtypes)
 _SIGS = {
@@ -211,6 +212,7 @@ _SIGS = {
     "vp_adaln_bwd_bf16": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, f32, vp, i64, i32, i32, i32, i32, vp, vp, vp,
                                 vp]),
     "vp_rowscale_bf16": (i32, [vp, i64, vp, i64, i32, i32, i32, i32, vp, i64, i32, i32, vp]),
+    "vp_rowscale_mx_fp8": (i32, [vp, i64, vp, i64, vp, i32, i32, i32, i32, vp, i64, i32, i32, vp]),
     "vp_gelu_bf16": (i32, [vp, vp, i64, vp]),
     "vp_gelu_bwd_bf16": (i32, [vp, vp, vp, i64, vp]),
     "vp_axpy_bf16": (i32, [vp, vp, f32, vp, i64, vp]),

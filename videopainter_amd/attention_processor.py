@@ -165,6 +165,22 @@ def _qkv(attn, x: torch.Tensor, norm_rope=None, keep: Optional[dict] = None) -> 
     return out
 
 
+def keep_handed_qkv(attn, qkv: torch.Tensor, text_len: int, rope, keep: dict):
+    """A keep-all forward (or the backward's recompute) on a pre-norm `qkv` [B, N, 3D] the block handed over (its
+    MX-FP8 projection): the two norm launches of the inference path, written beside qkv instead of over it, so the
+    pre-norm q | k the LayerNorm backward reads survive.  Fills "qpre" / "kpre" / "v" / "q" / "k" as `_qkv` names
+    them and returns (q, k, v), normed + rotated."""
+    B, Ntok, D3 = qkv.shape
+    D, H = D3 // 3, attn.heads
+    nq, nk = attn.norm_q, attn.norm_k
+    qk = torch.empty(B, Ntok, 2 * D, device=qkv.device, dtype=BF16)
+    q, k, v = qk[..., :D], qk[..., D:], qkv[..., 2 * D:]
+    K.head_norm_rope(qkv[..., :D], q, H, text_len, nq.weight, nq.bias, nq.eps, rope)
+    K.head_norm_rope(qkv[..., D:2 * D], k, H, text_len, nk.weight, nk.bias, nk.eps, rope)
+    keep.update(qpre=qkv[..., :D], kpre=qkv[..., D:2 * D], v=v, q=q, k=k)
+    return q, k, v
+
+
 def _kv(attn, x: torch.Tensor) -> torch.Tensor:
     B, Ntok, D = x.shape
     out = torch.empty(B, Ntok, 2 * D, device=x.device, dtype=BF16)
@@ -263,12 +279,13 @@ class CogVideoXAttnProcessor2_0:
                qkv: Optional[torch.Tensor] = None, keep: Optional[dict] = None) -> torch.Tensor:
         """keep: a dict that receives the attention output "o" and its softmax statistics "lse" (fp32 [B, H, N]) —
         a training forward keeps them for the backward (autograd.SAVE_ATTENTION) — and at the level "all" what the
-        projection keeps (_qkv); the single-segment bf16 attention only."""
+        projection keeps (_qkv; of a handed-over `qkv`, the block's fp8 projection: keep_handed_qkv); the
+        single-segment bf16 attention only."""
         B, Ntok, D = x.shape
         H = attn.heads
         rope = _rope_dev(image_rotary_emb, x.device)
         fp8 = getattr(attn, "fp8_qk_exp", None)
-        if keep is not None and (fp8 is not None or prev_hidden_states is not None or qkv is not None):
+        if keep is not None and (fp8 is not None or prev_hidden_states is not None):
             raise ValueError("keep: the single-segment bf16 attention only")
         # (the pre-norm q | k a keep-all forward stores are the fused epilogue's second output: it runs that epilogue
         # whatever VP_NO_QKV_FUSION says — the same bits as the separate launches)
@@ -276,6 +293,9 @@ class CogVideoXAttnProcessor2_0:
         if qkv is None:  # (the block may hand over an fp8 projection)
             qkv = _qkv(attn, x, (text_len, rope) if fused else None, keep)
         q, k, v = qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:]
+        if not fused and keeps_all(keep):  # (a handed-over qkv: the norms out of place, the same launches otherwise)
+            q, k, v = keep_handed_qkv(attn, qkv, text_len, rope, keep)
+            fused = True
         if fp8 is None:
             o = augmented_rows((attn.to_out[0],), B, Ntok, D, x.device)
             lse = None

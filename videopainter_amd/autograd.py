@@ -49,7 +49,14 @@ lse_i = log2(sum_real 2^s_ij + 2^lx_i) (lx: the null keys' closed-form mass), D_
   bias, which is not built;
   dK_normed[n] = dK1[n] + dK2c[dst[n]] and dV[n] += dV2c[dst[n]] on the masked rows (kernels.gather_add_rows: a
   masked row's K2 / V2 row is the same function of the same k / v row), then ONE (LN + RoPE)' for k.
-Out of scope for the backward (NotImplementedError): the fp8 modes, the previous-clip blend (windows > 0) and
+Frozen blocks on the MX-FP8 GEMMs (`enable_fp8_ffn / _qkv / _out`): the forward is the fp8 inference forward (FF1's
+aux output z the one addition), and the four dgrad GEMMs — the same projections against constant weights — run on
+vp_gemm_mx_fp8 too, against transposed weights quantised along the forward's output dimension (`_wt_mx`, `_qkv_t_mx`:
+built at the first backward), each dY quantised after its gate row-scale (kernels.rowscale_mx), the FF2 dgrad handing
+dz to the FF1 dgrad in MX (EPI_GELU_BWD_MXFP8).  FP8_DGRAD names the dgrads that do; the attention stays bf16 both ways.
+Such a block is refused with a trainable parameter or a wanted temb gradient (weight gradients and the modulation path
+are bf16-only), and qkv / out fp8 with the resample forms.
+Out of scope for the backward (NotImplementedError): the fp8 attention, the previous-clip blend (windows > 0) and
 `return_hidden_states` — inference-only in the reference.
 """
 from __future__ import annotations
@@ -61,7 +68,7 @@ import torch
 from . import _native as NAT
 from . import kernels as K
 from .attention_processor import (CogVideoXAttnProcessor2_0, CogVideoXAttnProcessor2_0_resample, _qkv,
-                                  bounded_scores, keeps_all, project_out)
+                                  bounded_scores, keep_handed_qkv, keeps_all, project_out)
 from .lora import AugmentedProjection, augmented_rows
 
 BF16 = torch.bfloat16
@@ -94,6 +101,38 @@ def _qkv_t(attn) -> torch.Tensor:
             K.transpose(w.detach(), out=wt[:, s * n:(s + 1) * n])
         c = (key, wt)
         attn._vp_qkv_t = c
+    return c[1]
+
+
+# The dgrad GEMMs of a block's MX-FP8 projections that run on the fp8 GEMM too: "ff2" (with GELU'), "ff1", "out",
+# "qkv".  A name taken out keeps that dgrad on the bf16 GEMM against the bf16 transposed weight, while the forward
+# stays fp8 (the A/B arm, and the fallback should one GEMM's e4m3 dgrad cost too much accuracy).
+FP8_DGRAD = {"ff2", "ff1", "out", "qkv"}
+
+
+def _wt_mx(w: torch.Tensor) -> "K.MXTensor":
+    """MX-quantise(W^T): the fp8 dgrad's weight, quantised along the forward's OUTPUT dimension (the dgrad's K) —
+    another quantisation than the forward's weight, not a re-layout of it.  Cached like `_wt`."""
+    key = (w.data_ptr(), w._version, tuple(w.shape))
+    c = getattr(w, "_vp_wt_mx", None)
+    if c is None or c[0] != key:
+        c = (key, K.mx_quantize(K.transpose(w.detach())))
+        w._vp_wt_mx = c
+    return c[1]
+
+
+def _qkv_t_mx(attn) -> "K.MXTensor":
+    """MX-quantise(cat(W_q, W_k, W_v)^T) [D, 3D]: the fused QKV dgrad's fp8 weight (cached like `_qkv_t`)."""
+    ws = (attn.to_q.weight, attn.to_k.weight, attn.to_v.weight)
+    key = tuple((w.data_ptr(), w._version) for w in ws)
+    c = getattr(attn, "_vp_qkv_t_mx", None)
+    if c is None or c[0] != key:
+        n = ws[0].shape[0]
+        wt = torch.empty(ws[0].shape[1], 3 * n, device=ws[0].device, dtype=BF16)
+        for s, w in enumerate(ws):
+            K.transpose(w.detach(), out=wt[:, s * n:(s + 1) * n])
+        c = (key, K.mx_quantize(wt))
+        attn._vp_qkv_t_mx = c
     return c[1]
 
 
@@ -290,12 +329,15 @@ class _SingleSegment(_AttentionForm):
             return "attention"
         return None
 
-    def recompute(self, block, xn: torch.Tensor, T: int, rope, keep: dict) -> None:
-        """The block's attention stage — its projection alone where the forward kept "o" / "lse"."""
-        if "o" in keep:
-            _qkv(self.a, xn, (T, rope), keep)
+    def recompute(self, block, xn: torch.Tensor, T: int, rope, keep: dict, qkv=None) -> None:
+        """The block's attention stage — its projection alone where the forward kept "o" / "lse".  qkv: the block's
+        fp8 projection's output (xn is then any [B, N, D] tensor, for its shape)."""
+        if "o" not in keep:
+            block._attention(xn, T, rope, qkv=qkv, keep=keep)
+        elif qkv is not None:
+            keep_handed_qkv(self.a, qkv, T, rope, keep)
         else:
-            block._attention(xn, T, rope, keep=keep)
+            _qkv(self.a, xn, (T, rope), keep)
 
     def backward(self, s: dict, T: int, rope, train: bool, G: _Grads) -> torch.Tensor:
         a = self.a
@@ -340,7 +382,7 @@ class _Explicit2N(_TwoSegment):
     def keep_level(self, block, x, train):
         return None  # (its backward recomputes the attention over the 2N keys)
 
-    def recompute(self, block, xn, T, rope, keep):
+    def recompute(self, block, xn, T, rope, keep, qkv=None):
         a, nk, Ntok = self.a, self.a.norm_k, xn.shape[1]
 
         def second(k, v, kc, vc):
@@ -397,7 +439,7 @@ class _ClosedForm(_TwoSegment):
     def keep_level(self, block, x, train):
         return "attention"  # (the two-segment launch's o / lse, the null-key mass included)
 
-    def recompute(self, block, xn, T, rope, keep):
+    def recompute(self, block, xn, T, rope, keep, qkv=None):
         """No attention launch (the forward kept "o" / "lse"): compact copies, as the fused forward makes them."""
         Ntok = xn.shape[1]
         keep["plan"] = m, dst, _, _, _, _ = _closed_form_plan(self.a, T, rope, self.mask)
@@ -437,13 +479,29 @@ def _attention_form(a, resample_mask=None):
     return _SingleSegment(a)
 
 
-def _trainable_form(block, resample_mask=None, rope=None):
-    """The attention form of a block call the backward can run; raises what it refuses."""
+def _mx_gemms(block) -> bool:
+    """The block runs a projection on the MX-FP8 GEMM (enable_fp8_ffn / _qkv / _out)."""
+    return block.ff_mx is not None or block.qkv_mx is not None or getattr(block, "out_mx", None) is not None
+
+
+def _trainable_form(block, resample_mask=None, rope=None, temb=None):
+    """The attention form of a block call the backward can run; raises what it refuses.  temb: the call's time
+    embedding (whether its gradient is wanted)."""
     a = block.attn1
-    if (block.ff_mx is not None or block.qkv_mx is not None or getattr(block, "out_mx", None) is not None
-            or getattr(a, "fp8_qk_exp", None) is not None):
+    if getattr(a, "fp8_qk_exp", None) is not None:
         raise NotImplementedError("the backward runs the bf16 path: disable the fp8 modes for training")
     form = _attention_form(a, resample_mask)
+    if _mx_gemms(block):
+        # the dgrad GEMMs run against constant weights; weight gradients and the modulation path are bf16-only
+        if any(p.requires_grad for p in block.parameters()):
+            raise NotImplementedError("a block on the fp8 GEMMs trains no parameter of its own (its weight gradients "
+                                      "are bf16-only): freeze the block, or disable enable_fp8_ffn / _qkv / _out on it")
+        if temb is not None and temb.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError("a block on the fp8 GEMMs builds no time-embedding gradient (the modulation "
+                                      "path is bf16-only): detach temb, or disable enable_fp8_ffn / _qkv / _out on it")
+        if (block.qkv_mx is not None or block.out_mx is not None) and not isinstance(form, _SingleSegment):
+            raise NotImplementedError("the fp8 QKV / output projections have no backward with the resample "
+                                      "processor: enable_fp8_ffn alone trains with it")
     form.check(rope)
     return form
 
@@ -461,10 +519,11 @@ def _block_front(block, x: torch.Tensor, T: int, temb: torch.Tensor, rope, resam
         form = _attention_form(block.attn1, resample_mask)
     keep = dict(level="all", train=True)
     keep["mod1"], keep["mod2"] = mod1, mod2 = block.norm1.modulation(temb), block.norm2.modulation(temb)
-    xn, _, _ = block._attn_input(x, T, mod1, keep=keep)
+    xn, qkv, _ = block._attn_input(x, T, mod1, keep=keep)
     if attn_saved is not None:
         keep["o"], keep["lse"] = attn_saved
-    form.recompute(block, xn, T, rope, keep)
+    form.recompute(block, xn if xn is not None else x, T, rope, keep, qkv)
+    del xn, qkv
     block._ff_front(block._attn_output(x, keep["o"], mod1, T, keep), mod2, T, keep, activate=with_h)
     return keep
 
@@ -508,12 +567,33 @@ def _ff_bwd(block, s: dict, dout: torch.Tensor, g: torch.Tensor, T: int, mod2: t
     ff0, ff2 = block.ff.net[0].proj, block.ff.net[2]
     x_mid, z, xn2, h = s.pop("x_mid"), s.pop("z"), s.pop("xn2", None), s.pop("h", None)
     dout2 = dout.view(M, D)
-    df = torch.empty(M, D, device=dout.device, dtype=BF16)
-    K.rowscale(dout2, df, Ntok, T, mod2, 2, 5)
-    dz = torch.empty(M, ff0.weight.shape[0], device=dout.device, dtype=BF16)
-    K.gemm(df, [_wt(ff2.weight)], [None], dz, epilogue=NAT.EPI_GELU_BWD, z=z)  # (df W2) * GELU'(z), one pass
+    F4 = ff0.weight.shape[0]
+    mx2, mx1 = (block.ff_mx is not None and n in FP8_DGRAD for n in ("ff2", "ff1"))
+    df = None
+    if mx2:
+        # dY quantised after its gate row-scale, in one pass; dz stays in MX where the FF1 dgrad takes it
+        dfq = K.rowscale_mx(dout2, Ntok, T, mod2, 2, 5)
+        if mx1:
+            dz = K.gemm_mx(dfq, [_wt_mx(ff2.weight)], [None], K.MXTensor(M, F4, dout.device, zero=False),
+                           epilogue=NAT.EPI_GELU_BWD_MXFP8, z=z)
+        else:
+            dh = torch.empty(M, F4, device=dout.device, dtype=BF16)
+            K.gemm_mx(dfq, [_wt_mx(ff2.weight)], [None], dh)
+            dz = K.gelu_bwd(dh, z)
+            del dh
+        del dfq
+    else:
+        df = torch.empty(M, D, device=dout.device, dtype=BF16)
+        K.rowscale(dout2, df, Ntok, T, mod2, 2, 5)
+        dz = torch.empty(M, F4, device=dout.device, dtype=BF16)
+        K.gemm(df, [_wt(ff2.weight)], [None], dz, epilogue=NAT.EPI_GELU_BWD, z=z)  # (df W2) * GELU'(z), one pass
+        if mx1:
+            dz = K.mx_quantize(dz, out=K.MXTensor(M, F4, dout.device, zero=False))
     dxn2 = torch.empty(B, Ntok, D, device=dout.device, dtype=BF16)
-    _dgrad(dz, ff0.weight, dxn2.view(M, D))
+    if mx1:
+        K.gemm_mx(dz, [_wt_mx(ff0.weight)], [None], dxn2.view(M, D))
+    else:
+        _dgrad(dz, ff0.weight, dxn2.view(M, D))
     ad = _AdaLNBwd(block.norm2, x_mid, dxn2, g, T, mod2, need_dmod)
     if not need_dmod:
         return None
@@ -543,6 +623,11 @@ def _attn_output_bwd(block, s: dict, g: torch.Tensor, T: int, mod1: torch.Tensor
     to_out = block.attn1.to_out[0]
     oaug = AugmentedProjection.of((to_out,))
     o2 = s["o"].view(M, D)
+    if block.out_mx is not None and "out" in FP8_DGRAD:
+        # (a frozen block without adapters — `_trainable_form`, enable_fp8_out: nothing below but the dgrad)
+        s["do"] = do = torch.empty(B, Ntok, D, device=g.device, dtype=BF16)
+        K.gemm_mx(K.rowscale_mx(g.view(M, D), Ntok, T, mod1, 2, 5), [_wt_mx(to_out.weight)], [None], do.view(M, D))
+        return None
     dao = torch.empty(M, D, device=g.device, dtype=BF16)
     K.rowscale(g.view(M, D), dao, Ntok, T, mod1, 2, 5)
     o_aug = gate1 = None
@@ -565,14 +650,19 @@ def _attn_output_bwd(block, s: dict, g: torch.Tensor, T: int, mod1: torch.Tensor
     return gate1
 
 
-def _qkv_bwd(a, s: dict, train: bool, G: _Grads) -> torch.Tensor:
-    """The fused QKV projection: "dqkv" -> d xn [B, N, D], and the weight / bias / LoRA gradients."""
+def _qkv_bwd(a, s: dict, train: bool, G: _Grads, mx: bool = False) -> torch.Tensor:
+    """The fused QKV projection: "dqkv" -> d xn [B, N, D], and the weight / bias / LoRA gradients.  mx: the dgrad on
+    the fp8 GEMM (a frozen block without adapters: the dgrad alone)."""
     dqkv, xn, xq = s.pop("dqkv"), s.pop("xn", None), s.pop("xq", None)
     B, Ntok, D3 = dqkv.shape
     D, M = D3 // 3, B * Ntok
     lins = (a.to_q, a.to_k, a.to_v)
     qaug = AugmentedProjection.of(lins)
     dxn = torch.empty(B, Ntok, D, device=dqkv.device, dtype=BF16)
+    if mx:
+        dq8 = K.mx_quantize(dqkv.view(M, D3), out=K.MXTensor(M, D3, dqkv.device, zero=False))
+        K.gemm_mx(dq8, [_qkv_t_mx(a)], [None], dxn.view(M, D))
+        return dxn
     K.gemm(dqkv.view(M, D3), [_qkv_t(a)], [None], dxn.view(M, D))
     if train:
         db = _total(dqkv.view(M, D3))
@@ -636,7 +726,7 @@ def block_backward(block, form, x: torch.Tensor, T: int, temb: torch.Tensor, rop
     dmod2 = _ff_bwd(block, s, dout, g, T, mod2, need_dmod, train, G)
     gate1 = _attn_output_bwd(block, s, g, T, mod1, need_dmod, train, G)
     s["dqkv"] = form.backward(s, T, rope, train, G)
-    dxn = _qkv_bwd(block.attn1, s, train, G)
+    dxn = _qkv_bwd(block.attn1, s, train, G, block.qkv_mx is not None and "qkv" in FP8_DGRAD)
     dtemb = _attn_input_bwd(block, x, dxn, g, T, temb, mod1, gate1, dmod2, need_dmod, want_dtemb, train, G)
     return g, dtemb, dinj, G
 
@@ -707,7 +797,7 @@ def block_apply(block, x: torch.Tensor, T: int, temb: torch.Tensor, rope, inject
                 resample_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Differentiable `block.forward_joint` (gradient-checkpointed).  resample_mask: the uint8 token mask of the
     blocks' resample processor (window 0 of VideoPainterID training)."""
-    form = _trainable_form(block, resample_mask, rope)
+    form = _trainable_form(block, resample_mask, rope, temb)
     params = [p for p in block.parameters()]
     return _BlockFn.apply(block, T, rope, inject_mask, form, x, temb, inject, *params)
 

@@ -166,17 +166,23 @@ VP_DEV void mfma_mx(f32x4& acc, const i32x8& w, const i32x8& a, int sw, int sa) 
 // into the other half of the LDS meanwhile. ----
 // Internal instance kinds (not ABI values): an epilogue with the aux output (vp_gemm_desc.aux) is its own instance,
 // so the inference instances carry none of its code or registers.
-constexpr int EPI_QKNORM_AUX = 8, EPI_GELU_AUX = 9;
+// EPI_GELU_MX_AUX: vp_gemm_mx_fp8's VP_EPI_BIAS_GELU_MXFP8 with the aux output.  (Numbered clear of the ABI values.)
+constexpr int EPI_QKNORM_AUX = 16, EPI_GELU_AUX = 17, EPI_GELU_MX_AUX = 18;
+// instance-table slots of vp_gemm_bf16: the ABI epilogues 0 .. 8, then the two aux kinds
+constexpr int EPI_KINDS = 11, SLOT_QKNORM_AUX = 9, SLOT_GELU_AUX = 10;
 // the ABI epilogue of an instance kind, and whether the instance writes aux (EPI = -1: both from the descriptor)
 template <int EPI>
 VP_DEV int epi_kind(const vp_gemm_desc& d) {
   if constexpr (EPI < 0) return d.epilogue;
-  return EPI == EPI_QKNORM_AUX ? VP_EPI_BIAS_QKNORM_ROPE : EPI == EPI_GELU_AUX ? VP_EPI_BIAS_GELU : EPI;
+  return EPI == EPI_QKNORM_AUX    ? VP_EPI_BIAS_QKNORM_ROPE
+         : EPI == EPI_GELU_AUX    ? VP_EPI_BIAS_GELU
+         : EPI == EPI_GELU_MX_AUX ? VP_EPI_BIAS_GELU_MXFP8
+                                  : EPI;
 }
 template <int EPI>
 VP_DEV bool epi_aux(const vp_gemm_desc& d) {
   if constexpr (EPI < 0) return d.aux != nullptr;
-  return EPI == EPI_QKNORM_AUX || EPI == EPI_GELU_AUX;
+  return EPI == EPI_QKNORM_AUX || EPI == EPI_GELU_AUX || EPI == EPI_GELU_MX_AUX;
 }
 
 // EPI >= 0: the epilogue kind as a compile-time constant (the persistent kernel is instantiated per kind; with the
@@ -322,7 +328,8 @@ VP_DEV void epi_values(const vp_gemm_desc& d, const f32x4 (&acc)[FN][FM], Sink&&
         for (int r = 0; r < 4; ++r) {
           float v = rbf(acc[j][i][r] + bv[r]);
           // (with an aux output the GELU runs in the row pass, on the bf16 pre-activation it stores: the same bits)
-          if ((epi == VP_EPI_BIAS_GELU && !aux) || epi == VP_EPI_BIAS_GELU_MXFP8) v = gelu_tanh(v);
+          if ((epi == VP_EPI_BIAS_GELU && !aux) || (epi == VP_EPI_BIAS_GELU_MXFP8 && EPI != EPI_GELU_MX_AUX))
+            v = gelu_tanh(v);
           else if (epi == VP_EPI_BIAS_SCALE) v = v * d.alpha;
           o[r] = f2bf(v);
         }
@@ -374,8 +381,20 @@ VP_DEV void epi_rows_out(const vp_gemm_desc& d, const MxExt& mx, const char* sme
       ++grp;
     }
     const int64_t orow = (int64_t)grp * d.group_stride + d.row_offset + gin;
-    if (FP8 && epi == VP_EPI_BIAS_GELU_MXFP8) {
-      // MX-quantise the GELU output: the 4 lanes holding one 32-column block agree on its scale (N % 256 == 0, so
+    if (FP8 && (epi == VP_EPI_BIAS_GELU_MXFP8 || EPI == VP_EPI_GELU_BWD_MXFP8)) {
+      // (the training instances are compile-time kinds only: the runtime-switch instance carries none of their code)
+      if constexpr (EPI == EPI_GELU_MX_AUX) {
+        // the training forward's FF1: the pre-activation z to aux, GELU(z) quantised to C
+        *(bf16x8*)((bf16*)d.aux + (int64_t)m * d.ld_aux + ncol) = v;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = f2bf(gelu_tanh(bf2f(v[e])));
+      } else if constexpr (EPI == VP_EPI_GELU_BWD_MXFP8) {
+        // the FF2 dgrad: VP_EPI_GELU_BWD's row, quantised as the FF1 dgrad's operand
+        const bf16x8 z = *(const bf16x8*)((const bf16*)d.R + (int64_t)m * d.ldr + ncol);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = f2bf(bf2f(v[e]) * gelu_grad(bf2f(z[e])));
+      }
+      // MX-quantise the row: the 4 lanes holding one 32-column block agree on its scale (N % 256 == 0, so
       // a block's lanes are all in or all out of range)
       float f[8];
 #pragma unroll
@@ -1249,7 +1268,7 @@ static int check_aux(const vp_gemm_desc* d) {
 // the instance-table slot of a descriptor: the ABI epilogue, or the aux instance of its kind
 static int kernel_index(const vp_gemm_desc* d) {
   if (d->aux == nullptr) return d->epilogue;
-  return d->epilogue == VP_EPI_BIAS_QKNORM_ROPE ? EPI_QKNORM_AUX : EPI_GELU_AUX;
+  return d->epilogue == VP_EPI_BIAS_QKNORM_ROPE ? SLOT_QKNORM_AUX : SLOT_GELU_AUX;
 }
 
 // main_tiles > 0: launch only the first main_tiles tiles of the grouped order (tail mode's main launch)
@@ -1279,12 +1298,12 @@ static int gemm_bf16_launch(const vp_gemm_desc* d, void* stream, int main_tiles)
   mx.group = gemm_group(d);
   if (d->a_tail_k != 0) {
     // the per-segment A tail (unfused LoRA): the default main loop only, on whole K-tiles and whole-tile segments
-    static const void* const k13t[10] = {(const void*)gemm_bf16_kernel<13, false, 4, VP_EPI_BIAS, false, true>,
+    static const void* const k13t[EPI_KINDS] = {(const void*)gemm_bf16_kernel<13, false, 4, VP_EPI_BIAS, false, true>,
                                         nullptr, nullptr,
                                         (const void*)gemm_bf16_kernel<13, false, 4, VP_EPI_GATED, false, true>,
                                         nullptr, nullptr,
                                         (const void*)gemm_bf16_kernel<13, false, 4, VP_EPI_BIAS_QKNORM_ROPE, false, true>,
-                                        nullptr,
+                                        nullptr, nullptr,
                                         (const void*)gemm_bf16_kernel<13, false, 4, EPI_QKNORM_AUX, false, true>,
                                         nullptr};
     static bool attr_t = false;
@@ -1319,19 +1338,20 @@ static int gemm_bf16_launch(const vp_gemm_desc* d, void* stream, int main_tiles)
   // 283.7 against 295.4 ms of GEMM per step, profiles/r04_gemm13_ab.log), 11 = the same with the reads after the DMA
   // (VP_GEMM_VARIANT=11, A/B), 5 = the unstaggered pipeline (A/B; also K < 512), 1 = the 2-stage ring (K % 64 != 0,
   // e.g. the patch-embed im2col K = 132)
-  static const void* const k11[10] = {
+  static const void* const k11[EPI_KINDS] = {
       (const void*)gemm_bf16_kernel<11, false, 4, VP_EPI_BIAS>, (const void*)gemm_bf16_kernel<11, false, 4, VP_EPI_BIAS_GELU>,
       (const void*)gemm_bf16_kernel<11, false, 4, VP_EPI_BIAS_SCALE>, (const void*)gemm_bf16_kernel<11, false, 4, VP_EPI_GATED>,
       (const void*)gemm_bf16_kernel<11, false, 4, VP_EPI_BIAS_ADDROWS>, nullptr,
       (const void*)gemm_bf16_kernel<11, false, 4, VP_EPI_BIAS_QKNORM_ROPE>,
       (const void*)gemm_bf16_kernel<11, false, 4, VP_EPI_GELU_BWD>,
-      nullptr, nullptr};
-  static const void* const k13[10] = {
+      nullptr, nullptr, nullptr};
+  static const void* const k13[EPI_KINDS] = {
       (const void*)gemm_bf16_kernel<13, false, 4, VP_EPI_BIAS>, (const void*)gemm_bf16_kernel<13, false, 4, VP_EPI_BIAS_GELU>,
       (const void*)gemm_bf16_kernel<13, false, 4, VP_EPI_BIAS_SCALE>, (const void*)gemm_bf16_kernel<13, false, 4, VP_EPI_GATED>,
       (const void*)gemm_bf16_kernel<13, false, 4, VP_EPI_BIAS_ADDROWS>, nullptr,
       (const void*)gemm_bf16_kernel<13, false, 4, VP_EPI_BIAS_QKNORM_ROPE>,
       (const void*)gemm_bf16_kernel<13, false, 4, VP_EPI_GELU_BWD>,
+      nullptr,
       (const void*)gemm_bf16_kernel<13, false, 4, EPI_QKNORM_AUX>,
       (const void*)gemm_bf16_kernel<13, false, 4, EPI_GELU_AUX>};
   static bool attr_set = false;
@@ -1450,8 +1470,17 @@ extern "C" int vp_gemm_mx_fp8(const vp_gemm_mx_desc* x, void* stream) {
   if (d->n_seg <= 0 || d->n_seg * nsegs != d->N || (d->n_seg % 256) != 0) return VP_ERR_ARG;
   for (int s = 0; s < nsegs; ++s)
     if (x->w_scale[s] == nullptr) return VP_ERR_ARG;
-  if (d->epilogue < VP_EPI_BIAS || d->epilogue > VP_EPI_BIAS_GELU_MXFP8 || d->aux != nullptr) return VP_ERR_ARG;
-  if (d->epilogue == VP_EPI_BIAS_GELU_MXFP8) {
+  const bool mx_out = d->epilogue == VP_EPI_BIAS_GELU_MXFP8 || d->epilogue == VP_EPI_GELU_BWD_MXFP8;
+  if ((d->epilogue < VP_EPI_BIAS || d->epilogue > VP_EPI_BIAS_GELU_MXFP8) && d->epilogue != VP_EPI_GELU_BWD_MXFP8)
+    return VP_ERR_ARG;
+  // the aux output (the training forward's z): VP_EPI_BIAS_GELU_MXFP8 only
+  if (d->aux != nullptr &&
+      (d->epilogue != VP_EPI_BIAS_GELU_MXFP8 || d->ld_aux < d->N || (d->ld_aux % 8) != 0 || ((uintptr_t)d->aux & 15) != 0))
+    return VP_ERR_ARG;
+  if (d->epilogue == VP_EPI_GELU_BWD_MXFP8 &&
+      (d->R == nullptr || d->ldr < d->N || (d->ldr % 8) != 0 || ((uintptr_t)d->R & 15) != 0))
+    return VP_ERR_ARG;
+  if (mx_out) {
     if (x->c_scale == nullptr || (d->ldc % 16) != 0 || d->ldc < d->N || d->rows_per_group != d->M) return VP_ERR_ARG;
   } else if (d->ldc < d->N || (d->ldc % 8) != 0) {
     return VP_ERR_ARG;
@@ -1466,15 +1495,20 @@ extern "C" int vp_gemm_mx_fp8(const vp_gemm_mx_desc* x, void* stream) {
   if ((int64_t)d->M * d->lda >= ((int64_t)1 << 31) || (int64_t)d->n_seg * d->K >= ((int64_t)1 << 31)) return VP_ERR_ARG;
   // instantiated per epilogue kind for the block's fp8 GEMMs (QKV: BIAS, FF1: GELU_MXFP8, FF2: GATED); the others
   // take the runtime switch of variant 5
-  static const void* const kf[6] = {(const void*)gemm_bf16_kernel<5, true, 4, VP_EPI_BIAS>, nullptr, nullptr,
+  // (slots 6 / 7: FF1 with the aux output and the FF2 dgrad VP_EPI_GELU_BWD_MXFP8, the training step's)
+  static const void* const kf[8] = {(const void*)gemm_bf16_kernel<5, true, 4, VP_EPI_BIAS>, nullptr, nullptr,
                                     (const void*)gemm_bf16_kernel<5, true, 4, VP_EPI_GATED>, nullptr,
-                                    (const void*)gemm_bf16_kernel<5, true, 4, VP_EPI_BIAS_GELU_MXFP8>};
+                                    (const void*)gemm_bf16_kernel<5, true, 4, VP_EPI_BIAS_GELU_MXFP8>,
+                                    (const void*)gemm_bf16_kernel<5, true, 4, EPI_GELU_MX_AUX>,
+                                    (const void*)gemm_bf16_kernel<5, true, 4, VP_EPI_GELU_BWD_MXFP8>};
   // 13 (default, nk >= 8): the staggered read-first pipeline of the bf16 default on the e4m3 operands — config 5's
   // fp8 GEMMs 446.7 against 466.3 ms per step with 5 (profiles/r04_c5_gemm8_ab.log); VP_GEMM8_VARIANT=5: the
   // unstaggered loop (A/B; also nk < 8)
-  static const void* const kf13[6] = {(const void*)gemm_bf16_kernel<13, true, 4, VP_EPI_BIAS>, nullptr, nullptr,
+  static const void* const kf13[8] = {(const void*)gemm_bf16_kernel<13, true, 4, VP_EPI_BIAS>, nullptr, nullptr,
                                       (const void*)gemm_bf16_kernel<13, true, 4, VP_EPI_GATED>, nullptr,
-                                      (const void*)gemm_bf16_kernel<13, true, 4, VP_EPI_BIAS_GELU_MXFP8>};
+                                      (const void*)gemm_bf16_kernel<13, true, 4, VP_EPI_BIAS_GELU_MXFP8>,
+                                      (const void*)gemm_bf16_kernel<13, true, 4, EPI_GELU_MX_AUX>,
+                                      (const void*)gemm_bf16_kernel<13, true, 4, VP_EPI_GELU_BWD_MXFP8>};
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute((const void*)gemm_bf16_kernel<5, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1486,15 +1520,15 @@ extern "C" int vp_gemm_mx_fp8(const vp_gemm_mx_desc* x, void* stream) {
     attr_set = true;
   }
   const char* e8 = vp_knob(VPK_GEMM8_VARIANT);  // (A/B knob)
-  const bool use13 = (e8 == nullptr || atoi(e8) != 5) && d->K / 128 >= 8 && kf13[d->epilogue] != nullptr;
+  const int ki = d->epilogue == VP_EPI_GELU_BWD_MXFP8 ? 7 : d->aux != nullptr ? 6 : d->epilogue;
+  const bool use13 = (e8 == nullptr || atoi(e8) != 5) && d->K / 128 >= 8 && kf13[ki] != nullptr;
   MxExt mx = {};  // no split; the grouped tile order of the bf16 path (VP_GEMM_GROUP, default 4)
   mx.group = gemm_group(d);
   mx.a_scale = (const uint8_t*)x->a_scale;
   for (int s = 0; s < 3; ++s) mx.w_scale[s] = (const uint8_t*)x->w_scale[s];
   mx.c_scale = (uint8_t*)x->c_scale;
   const int tiles = ((d->M + BM - 1) / BM) * (d->N / BN);
-  const void* fn = use13 ? kf13[d->epilogue]
-                   : kf[d->epilogue] != nullptr ? kf[d->epilogue] : (const void*)gemm_bf16_kernel<5, true>;
+  const void* fn = use13 ? kf13[ki] : kf[ki] != nullptr ? kf[ki] : (const void*)gemm_bf16_kernel<5, true>;
   void* args[] = {(void*)d, (void*)&mx};
   const hipError_t le = hipLaunchKernel(fn, dim3(tiles), dim3(NTHREADS), args, LDS_BYTES_FP8, (hipStream_t)stream);
   if (le != hipSuccess) return (int)le;
@@ -1545,6 +1579,31 @@ __global__ __launch_bounds__(256) void mx_quantize_heads_kernel(const bf16* __re
   mx_quantize_chunk(x + (((int64_t)j * n + row) * B + b) * Dp + (c * 8 - j * Dp), q, ld_out, scales, r, c, K);
 }
 
+// vp_rowscale_mx_fp8: the quantiser's thread scheme on rnd(x * mod[b, text / video chunk]) (rowscale_kernel's
+// product, backward.hip) instead of x: one pass where the MX dgrad took vp_rowscale_bf16 + vp_mx_quantize_bf16
+__global__ __launch_bounds__(256) void rowscale_mx_kernel(const bf16* __restrict__ x, int64_t ldx,
+                                                          uint8_t* __restrict__ q, int64_t ld_out,
+                                                          uint8_t* __restrict__ scales, int rows, int Ntok, int D,
+                                                          int text_len, const bf16* __restrict__ mod, int64_t mod_bs,
+                                                          int ch_v, int ch_t) {
+  const int cpr = D / 8;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t r = i / cpr;
+  const int c = (int)(i - r * cpr);
+  if (r >= rows) return;  // whole 4-lane groups leave together (cpr % 4 == 0)
+  const int b = (int)(r / Ntok);
+  const bool text = (int)(r - (int64_t)b * Ntok) < text_len;
+  const bf16x8 g = *(const bf16x8*)(mod + (int64_t)b * mod_bs + (int64_t)(text ? ch_t : ch_v) * D + c * 8);
+  const bf16x8 v = *(const bf16x8*)(x + r * ldx + c * 8);
+  float f[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) f[e] = rbf(bf2f(v[e]) * bf2f(g[e]));
+  uint8_t sb;
+  const u32x2 pk = mx_quantize_quarter(f, sb);
+  *(u32x2*)(q + r * ld_out + c * 8) = pk;
+  if ((c & 3) == 0) scales[mx_scale_off(r, c >> 2, D)] = sb;
+}
+
 extern "C" int64_t vp_mx_scale_bytes(int64_t rows, int64_t K) { return ((rows + 255) / 256) * (K / 128) * 1024; }
 
 extern "C" int vp_mx_quantize_bf16(const void* x, int64_t ld_in, void* q, int64_t ld_out, void* scales, int32_t rows,
@@ -1555,6 +1614,22 @@ extern "C" int vp_mx_quantize_bf16(const void* x, int64_t ld_in, void* q, int64_
   const int64_t n = (int64_t)rows * (K / 8);
   hipLaunchKernelGGL(mx_quantize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (const bf16*)x, ld_in, (uint8_t*)q, ld_out, (uint8_t*)scales, rows, K);
+  VP_CHECK_LAUNCH();
+  return VP_OK;
+}
+
+extern "C" int vp_rowscale_mx_fp8(const void* x, int64_t ldx, void* q, int64_t ld_out, void* scales, int32_t rows,
+                                  int32_t Ntok, int32_t D, int32_t text_len, const void* mod, int64_t mod_bstride,
+                                  int32_t chunk_v, int32_t chunk_t, void* stream) {
+  if (!x || !q || !scales || !mod || rows <= 0 || Ntok <= 0 || D <= 0 || (D % 128) || ldx < D || (ldx % 8) ||
+      ld_out < D || (ld_out % 8) || (mod_bstride % 8) || chunk_v < 0 || chunk_t < 0 || text_len < 0)
+    return VP_ERR_ARG;
+  if (((uintptr_t)x % 16) || ((uintptr_t)mod % 16) || ((uintptr_t)q % 8)) return VP_ERR_ARG;
+  const int64_t grid = ((int64_t)rows * (D / 8) + 255) / 256;
+  if (grid > 0x7fffffff) return VP_ERR_ARG;
+  hipLaunchKernelGGL(rowscale_mx_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, ldx,
+                     (uint8_t*)q, ld_out, (uint8_t*)scales, rows, Ntok, D, text_len, (const bf16*)mod, mod_bstride,
+                     chunk_v, chunk_t);
   VP_CHECK_LAUNCH();
   return VP_OK;
 }

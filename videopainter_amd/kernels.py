@@ -277,9 +277,13 @@ def gemm_mx(a: "MXTensor", weights: Sequence["MXTensor"], biases: Sequence[Optio
             epilogue: int = N.EPI_BIAS, alpha: float = 1.0, resid: Optional[torch.Tensor] = None,
             mod: Optional[torch.Tensor] = None, gate_chunk: int = 2, gate_text_chunk: int = 5,
             tokens_per_batch: int = 1, text_len: int = 0, inject: Optional[torch.Tensor] = None,
-            inject_mask: Optional[torch.Tensor] = None):
+            inject_mask: Optional[torch.Tensor] = None, aux: Optional[torch.Tensor] = None,
+            z: Optional[torch.Tensor] = None):
     """out = epilogue(a @ cat(weights).T) on the block-scaled fp8 MFMA.  `out` is a bf16 [M, N] tensor, or an
-    MXTensor for EPI_BIAS_GELU_MXFP8 (the FF1 -> FF2 hand-off stays in fp8)."""
+    MXTensor for EPI_BIAS_GELU_MXFP8 (the FF1 -> FF2 hand-off stays in fp8) and EPI_GELU_BWD_MXFP8.
+    aux (the training forward): EPI_BIAS_GELU_MXFP8 also stores the bf16 pre-activation, [M, N] row-major, there.
+    z: EPI_GELU_BWD_MXFP8's GELU input, bf16 [M, N] row-major: out = MX(bf16(bf16(a @ W^T + b) * gelu'(z))) (the FF2
+    dgrad, whose output is the FF1 dgrad's operand)."""
     Kk = a.K
     for w in weights:
         if w.K != Kk or w.rows != weights[0].rows:
@@ -301,9 +305,9 @@ def gemm_mx(a: "MXTensor", weights: Sequence["MXTensor"], biases: Sequence[Optio
     d.n_seg = nseg
     d.rows_per_group = a.rows
     d.alpha = alpha
-    if epilogue == N.EPI_BIAS_GELU_MXFP8:
+    if epilogue in (N.EPI_BIAS_GELU_MXFP8, N.EPI_GELU_BWD_MXFP8):
         if not isinstance(out, MXTensor) or out.K != Ntot or out.rows != a.rows:
-            raise ValueError("EPI_BIAS_GELU_MXFP8 writes an MXTensor [M, N]")
+            raise ValueError("EPI_BIAS_GELU_MXFP8 / EPI_GELU_BWD_MXFP8 write an MXTensor [M, N]")
         d.C, d.ldc = _p(out.q), out.q.stride(0)
         x.c_scale = _p(out.scales)
     else:
@@ -324,6 +328,18 @@ def gemm_mx(a: "MXTensor", weights: Sequence["MXTensor"], biases: Sequence[Optio
                 _chk(inject_mask, "inject_mask", torch.uint8)
                 d.inject_mask = _p(inject_mask)
                 d.inject_mask_bstride = inject_mask.stride(0)
+    if aux is not None:
+        _chk(aux, "aux")
+        if epilogue != N.EPI_BIAS_GELU_MXFP8:
+            raise ValueError("aux output: EPI_BIAS_GELU_MXFP8 only")
+        if aux.numel() // aux.shape[-1] != a.rows or aux.shape[-1] < Ntot:
+            raise ValueError(f"aux must hold {a.rows} rows of >= {Ntot} columns, got {tuple(aux.shape)}")
+        d.aux, d.ld_aux = _p(aux), _rowmajor(aux, "aux")
+    if epilogue == N.EPI_GELU_BWD_MXFP8:
+        _chk(z, "z")
+        if z.numel() // z.shape[-1] != a.rows or z.shape[-1] != Ntot:
+            raise ValueError(f"z must be [{a.rows}, {Ntot}], got {tuple(z.shape)}")
+        d.R, d.ldr = _p(z), _rowmajor(z, "z")
     ev = _t0("gemm_mx")
     N.check(N.lib().vp_gemm_mx_fp8(C.byref(x), _stream()), "vp_gemm_mx_fp8")
     _t1("gemm_mx", ev)
@@ -1514,6 +1530,31 @@ def rowscale(x: torch.Tensor, out: torch.Tensor, tokens_per_batch: int, text_len
     N.check(N.lib().vp_rowscale_bf16(_p(x), _rowmajor(x, "x"), _p(out), _rowmajor(out, "out"), rows,
                                      tokens_per_batch, D, text_len, _p(mod), mod.stride(0), chunk_v, chunk_t,
                                      _stream()), "vp_rowscale_bf16")
+    return out
+
+
+def rowscale_mx(x: torch.Tensor, tokens_per_batch: int, text_len: int, mod: torch.Tensor, chunk_v: int,
+                chunk_t: int, out: Optional["MXTensor"] = None) -> "MXTensor":
+    """`rowscale` writing MX rows: mx_quantize(rowscale(x)) byte for byte, in one pass (the operand of an fp8 dgrad
+    GEMM behind a gated residual)."""
+    _chk(x, "x")
+    _chk(mod, "mod")
+    rows, D = x.numel() // x.shape[-1], x.shape[-1]
+    if D % 128:
+        raise ValueError(f"rowscale_mx needs D % 128 == 0, got {D}")
+    if rows % tokens_per_batch or mod.dim() != 2 or mod.shape[0] < rows // tokens_per_batch \
+            or mod.shape[1] < (max(chunk_v, chunk_t) + 1) * D or min(chunk_v, chunk_t) < 0 or mod.stride(1) != 1:
+        raise ValueError(f"rowscale_mx: mod {tuple(mod.shape)} does not hold chunks {chunk_v} / {chunk_t} of width {D} "
+                         f"for {rows} rows of {tokens_per_batch} per batch")
+    if x.dim() > 2 and not x.is_contiguous():
+        raise ValueError("rowscale_mx: x must be [rows, D] (last dim contiguous) or contiguous")
+    out = MXTensor(rows, D, x.device, zero=False) if out is None else out
+    if out.rows != rows or out.K != D:
+        raise ValueError(f"out must be MXTensor [{rows}, {D}], got {out}")
+    ldx = _rowmajor(x, "x") if x.dim() == 2 else D
+    N.check(N.lib().vp_rowscale_mx_fp8(_p(x), ldx, _p(out.q), out.q.stride(0), _p(out.scales), rows,
+                                       tokens_per_batch, D, text_len, _p(mod), mod.stride(0), chunk_v, chunk_t,
+                                       _stream()), "vp_rowscale_mx_fp8")
     return out
 
 

@@ -374,7 +374,7 @@ class CogVideoXBlock(nn.Module):
         -> o [B, N, D], through the `attend` hook or the processor.  The hook also gets the fp8 projection's `qkv` and
         whether the output projection is the fp8 one (it may then return o as the MXTensor `_attn_output` takes).
         keep: handed to the processor, which fills it (`attend` of either processor; a ValueError where it keeps
-        nothing: the fp8 forms, the prev-clip blend, a handed-over qkv).  Whether a training forward passes one is the
+        nothing: the fp8 attention, the prev-clip blend, the resample processor with a handed-over qkv).  Whether a training forward passes one is the
         rule of its attention's backward form (autograd: `keep_level`)."""
         a = self.attn1
         if attend is not None:
@@ -405,17 +405,25 @@ class CogVideoXBlock(nn.Module):
     def _ff_front(self, x_mid: torch.Tensor, mod2: torch.Tensor, text_len: int, keep: Optional[dict] = None,
                   activate: bool = True):
         """norm2 AdaLN + FF1 with its GELU epilogue -> h (bf16 [B, N, 4D], or MX-FP8 rows with the fp8 FeedForward).
-        keep, at the level "all", receives the pre-activation "z" — the epilogue's aux output, requested then only;
-        a backward that needs no h passes activate=False: FF1 then stores z alone, nothing is returned — and, for
-        trainable parameters, "xn2" and "h"."""
+        keep, at the level "all", receives the pre-activation "z" — the epilogue's aux output (of either GEMM),
+        requested then only; a backward that needs no h passes activate=False: FF1 then stores z alone (the fp8 FF1
+        under EPI_BIAS: the same bits), nothing is returned — and, for trainable parameters, "xn2" and "h" (bf16
+        FeedForward only: a block on the fp8 GEMMs trains none, autograd._trainable_form)."""
         B, Ntok, D = x_mid.shape
         M = B * Ntok
         n2, ff0 = self.norm2.norm, self.ff.net[0].proj
         if self.ff_mx is not None:
             w1 = self.ff_mx[0]
             xq = K.adaln_modulate_mx(x_mid, n2.weight, n2.bias, mod2, text_len, n2.eps)
+            # a frozen block (autograd refuses trainable parameters beside the MX GEMMs): z is all its backward reads
+            z = None
+            if keeps_all(keep):
+                keep["z"] = z = torch.empty(M, w1.rows, device=x_mid.device, dtype=BF16)
+            if not activate:
+                K.gemm_mx(xq, [w1], [ff0.bias], z)
+                return None
             h = K.MXTensor(M, w1.rows, x_mid.device, zero=False)
-            K.gemm_mx(xq, [w1], [ff0.bias], h, epilogue=NAT.EPI_BIAS_GELU_MXFP8)
+            K.gemm_mx(xq, [w1], [ff0.bias], h, epilogue=NAT.EPI_BIAS_GELU_MXFP8, aux=z)
             return h
         xn2 = K.adaln_modulate(x_mid, n2.weight, n2.bias, mod2, text_len, n2.eps)
         F4 = ff0.weight.shape[0]
