@@ -697,8 +697,10 @@ int vp_denormalize_bf16(const void* x, void* y, int64_t n, void* stream);
  * (vp_null_key_mass_bwd reads it).  All tensors [B, N, H*64]-strided bf16.
  * The keys are one buffer of Nk rows; a forward over two segments is differentiated over their concatenation.
  * k_len (ABI 26): device int32 [B] or NULL — batch row b has min(k_len[b], Nk) keys (the resample processor's compact
- * second segment behind the N own keys, vp_attn_desc.k2_len): K / V rows at or past the length are never read, and
- * rows at or past it of dK / dV are written as zeros.  lse may hold more mass than these keys give (the closed-form
+ * second segment behind the N own keys, vp_attn_desc.k2_len; a negative entry counts as 0): K / V rows at or past the
+ * length never affect a result (they may hold anything, NaN included; a batch row of length 0 has row 0 of its K and V
+ * loaded and discarded, no other row at or past a length is read), and rows at or past it of dK / dV are written as
+ * zeros.  lse may hold more mass than these keys give (the closed-form
  * null keys, vp_attn_desc.l_extra).  The default kernels only (VP_ATTN_BWD_VARIANT=0 with k_len: VP_ERR_UNSUPPORTED). */
 typedef struct vp_attn_bwd_desc {
   int32_t B, H, Nq, Nk, head_dim, pad0;

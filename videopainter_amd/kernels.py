@@ -528,8 +528,9 @@ def attention_bwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Te
                   k_len: Optional[torch.Tensor] = None, delta: Optional[torch.Tensor] = None):
     """Flash-attention backward (vp_attention_bwd_bf16) of `attention(q, k, v, o, heads, lse=lse)`: returns
     (dq, dk, dv), each [B, N, heads*64] bf16 (new contiguous tensors unless given).  k_len: optional int32 [B]
-    (device): batch row b has min(k_len[b], Nk) keys — k / v rows past it are not read, dk / dv rows past it come back
-    zero.  delta: optional fp32 [B, heads, Nq] receiving D = rowsum(dO * O) (null_key_mass_bwd reads it)."""
+    (device): batch row b has min(max(k_len[b], 0), Nk) keys — k / v rows past it never affect a result (they may hold
+    NaN), dk / dv rows past it come back zero.  delta: optional fp32 [B, heads, Nq] receiving D = rowsum(dO * O)
+    (null_key_mass_bwd reads it)."""
     for t, n in ((q, "q"), (k, "k"), (v, "v"), (o, "o"), (do, "do")):
         _chk(t, n)
         if t.dim() != 3 or t.stride(-1) != 1 or t.shape[-1] != heads * 64 or t.shape[0] != q.shape[0]:
