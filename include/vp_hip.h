@@ -33,7 +33,7 @@ extern "C" {
 #define VP_ERR_UNSUPPORTED 1001
 
 /* ABI version: bump when any struct layout or signature below changes. */
-#define VP_ABI_VERSION 28
+#define VP_ABI_VERSION 29
 int vp_abi_version(void);
 /* "<sha256 of sources + flags>:<sha256 of the compiler version>" of the build (no reference counterpart) */
 const char* vp_build_digest(void);
@@ -983,6 +983,65 @@ int vp_zero_shard_adamw(const vp_zero_range* ranges, int32_t range_begin, int32_
                         float* master, float* exp_avg, float* exp_avg_sq, void* param_shard, int64_t per,
                         const vp_optim_scalars* scalars, double lr, double beta1, double beta2, double eps,
                         double weight_decay, int32_t use_clip, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Sharded plain Adam and Prodigy (ABI 29; csrc/zero.hip): the other two optimizers on the sharded training tail
+ * above — the same pack, reduce-scatter, shard norm, record all-gather and vp_zero_finalize, the same range table and
+ * rules (one workgroup per range, 16-byte body, scalar head / tail, 64-bit offsets, no float atomics, fixed-order
+ * two-stage reductions, no host read, a skipped step writes nothing, a range that does not fit `per` is left out),
+ * the per-element arithmetic of vp_mt_adam_bf16 / vp_mt_prodigy_*_bf16 (the same device functions). */
+/* vp_zero_shard_adamw with torch.optim.Adam's decay: g = grad_shard (* clip_coef) + weight_decay * master, no factor
+ * on the master; everything else as there. */
+int vp_zero_shard_adam(const vp_zero_range* ranges, int32_t range_begin, int32_t n_ranges, const float* grad_shard,
+                       float* master, float* exp_avg, float* exp_avg_sq, void* param_shard, int64_t per,
+                       const vp_optim_scalars* scalars, double lr, double beta1, double beta2, double eps,
+                       double weight_decay, int32_t use_clip, void* stream);
+/* Sharded Prodigy: rank r keeps master / exp_avg / exp_avg_sq / s / p0 (fp32 [per] each) and its own copy of the
+ * vp_prodigy_scalars block.  The two sums of the d update are the only part that is not element-wise: every rank sums
+ * its ranges' pairs into a record of two doubles, the records are all-gathered (16 bytes per rank) and every rank
+ * runs the same finaliser over them in rank order.  After vp_zero_finalize, with the collectives left to the caller:
+ *   vp_zero_prodigy_finalize(phase 0)   dlr from the old d (vp_prodigy_finalize's phase 0)
+ *   vp_zero_shard_prodigy_moments       once per parameter group: pass 1 over the shard, one pair per range
+ *   vp_zero_prodigy_record              -> this rank's (sum dot, sum |s|) record
+ *   (all-gather)                        -> records [world][2], in rank order
+ *   vp_zero_prodigy_finalize(phase 1)   the d update: the same block on every rank, bit for bit
+ *   vp_zero_shard_prodigy_update        once per parameter group: pass 2, bf16(p) into the bf16 shard
+ *   (all-gather), vp_zero_unpack_gated_bf16
+ * pass 1 over ranges [range_begin, range_begin + n_ranges): vp_mt_prodigy_moments_bf16's arithmetic on g = grad_shard
+ * (fp32); exp_avg / exp_avg_sq / s updated in place, master and p0 read only; partials[2 c] = dot and partials[2 c + 1]
+ * = sum |s| of range c (its index in the whole table; (0, 0) for a range that does not fit).  24 bytes read and 12
+ * written per element of the shard.  A skipped step writes nothing. */
+int vp_zero_shard_prodigy_moments(const vp_zero_range* ranges, int32_t range_begin, int32_t n_ranges,
+                                  const float* grad_shard, const float* master, const float* p0, float* exp_avg,
+                                  float* exp_avg_sq, float* s, int64_t per, float* partials,
+                                  const vp_optim_scalars* scalars, const vp_prodigy_scalars* dstate, double beta1,
+                                  double beta2, double beta3, double weight_decay, double d0,
+                                  int32_t safeguard_warmup, int32_t use_clip, void* stream);
+/* One workgroup: record[0] = sum of partials[2 c], record[1] = sum of partials[2 c + 1] over c in [0, n_ranges), as
+ * vp_prodigy_finalize's phase 1 sums its chunks (thread t takes slots t, t + 256, ... in order, in double, then the
+ * fixed block sum).  n_ranges = 0 (a rank that owns only padding) and a skipped step still write (0, 0). */
+int vp_zero_prodigy_record(const float* partials, int32_t n_ranges, const vp_optim_scalars* scalars, double* record,
+                           void* stream);
+/* vp_prodigy_finalize over the ranks' records: phase 0 is its phase 0 (records and world are not used); phase 1 sums
+ * records[0 .. world) (double [world][2], rank order) with the same strided double sum and runs the same d update
+ * (d_numerator, d_denom, d_hat, d, d_max; all ranks' sum |s| == 0: no_progress = 1 and the counter goes back by one).
+ * Every rank that passes the same records and blocks gets the same vp_prodigy_scalars, bit for bit.  VP_ERR_ARG as
+ * vp_prodigy_finalize, and for world <= 0 or NULL records in phase 1. */
+int vp_zero_prodigy_finalize(int32_t phase, const double* records, int32_t world, double lr, double beta1,
+                             double beta2, double beta3, double d0, double d_coef, double growth_rate,
+                             int32_t use_bias_correction, vp_optim_scalars* scalars, vp_prodigy_scalars* dstate,
+                             void* stream);
+/* pass 2 over the same ranges: vp_mt_prodigy_update_bf16's arithmetic; master updated in place, param_shard[i] =
+ * bf16(p).  12 bytes read and 6 written per element of the shard.  A skipped or no-progress step writes nothing. */
+int vp_zero_shard_prodigy_update(const vp_zero_range* ranges, int32_t range_begin, int32_t n_ranges, float* master,
+                                 const float* exp_avg, const float* exp_avg_sq, void* param_shard, int64_t per,
+                                 const vp_optim_scalars* scalars, const vp_prodigy_scalars* dstate, double eps,
+                                 double weight_decay, void* stream);
+/* vp_zero_unpack_bf16 that also writes nothing in a no-progress step (dstate->no_progress): pass 2 left the bf16
+ * shards as they were then, so the gathered staging buffer does not hold this step's parameters. */
+int vp_zero_unpack_gated_bf16(const vp_mt_tensor* tensors, const vp_mt_chunk* chunks, int32_t n_chunks,
+                              const void* flat, int64_t flat_len, const vp_optim_scalars* scalars,
+                              const vp_prodigy_scalars* dstate, void* stream);
 
 
 #ifdef __cplusplus

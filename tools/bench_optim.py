@@ -1,6 +1,6 @@
 """Optimizer-step time at the real branch parameter set on one MI355X: FusedAdamW against the torch equivalents.
 
-    python tools/bench_optim.py [--rounds R] [--iters N] [--sharded] [--prodigy]
+    python tools/bench_optim.py [--rounds R] [--iters N] [--sharded] [--prodigy] [--sharded-prodigy]
 
 Parameters: the trainable VideoPainter branch (5b-I2V config, num_layers=2, init_synthetic_weights_), bf16, with
 random bf16 gradients N(0, 1e-3^2); the training script's hyper-parameters (lr 1e-5, betas (0.9, 0.95), weight decay
@@ -25,6 +25,12 @@ produced on one GPU.
 afterwards times its two passes one by one, round by round beside vp_mt_adamw_bf16's update pass (the yardstick of
 the same round): pass 1 (vp_mt_prodigy_moments_bf16) 22 B read + 12 B written per parameter, pass 2
 (vp_mt_prodigy_update_bf16) 12 + 6 B; with the norm pass's 2 B the step moves 54 B per parameter against AdamW's 30.
+
+--sharded-prodigy adds videopainter_amd.ShardedFusedProdigy(lr=1.0, max_grad_norm=1.0) at world size 1 over RCCL as a
+variant (give --prodigy too to have FusedProdigy beside it in the same rounds), and afterwards times the pieces of its
+step one by one: pass 1 (vp_zero_shard_prodigy_moments) 24 B read + 12 B written per parameter, pass 2
+(vp_zero_shard_prodigy_update) 12 + 6 B, the gated unpack 2 + 2 B, the record kernel, the d update over the records and
+the 16-byte all-gather.
 
 Prints ms per step per round (HIP events around N back-to-back steps), and for `fused` the effective bandwidth
 30 B x n_params / t (norm pass: 2 B read; update pass: 14 B read + 14 B written per parameter) as a fraction of
@@ -62,6 +68,8 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--sharded", action="store_true", help="add ShardedFusedAdamW at world 1 over RCCL")
     ap.add_argument("--prodigy", action="store_true", help="add FusedProdigy and time its two passes")
+    ap.add_argument("--sharded-prodigy", action="store_true",
+                    help="add ShardedFusedProdigy at world 1 over RCCL and time the pieces of its step")
     args = ap.parse_args()
     from videopainter_amd import CogvideoXBranchModel, FusedAdamW, device_scope
     from videopainter_amd import kernels as K
@@ -103,14 +111,13 @@ def main():
     opt16 = torch.optim.AdamW(p16, **HYP, foreach=True)
 
     variants = dict(fused=fused.step, torch_fp32=torch_fp32, torch_bf16=opt16.step)
-    sharded = prodigy = None
+    sharded = prodigy = sprodigy = None
     if args.prodigy:
         from videopainter_amd import FusedProdigy
         prodigy = FusedProdigy(with_grads(clone()), **dict(HYP, lr=1.0), max_grad_norm=1.0)
         variants["prodigy"] = prodigy.step
-    if args.sharded:
+    if args.sharded or args.sharded_prodigy:
         import socket
-        from videopainter_amd import ShardedFusedAdamW
         from videopainter_amd import distributed as VD
         sock = socket.socket()
         sock.bind(("127.0.0.1", 0))
@@ -120,8 +127,14 @@ def main():
             os.environ.setdefault(k, v)
         torch.cuda.set_device(0)
         VD.init("nccl", torch.device("cuda", 0))
+    if args.sharded:
+        from videopainter_amd import ShardedFusedAdamW
         sharded = ShardedFusedAdamW(with_grads(clone()), **HYP, max_grad_norm=1.0)
         variants["sharded"] = sharded.step
+    if args.sharded_prodigy:
+        from videopainter_amd import ShardedFusedProdigy
+        sprodigy = ShardedFusedProdigy(with_grads(clone()), **dict(HYP, lr=1.0), max_grad_norm=1.0)
+        variants["sharded_prodigy"] = sprodigy.step
     for fn in variants.values():  # warm-up (allocations, table upload)
         fn()
         fn()
@@ -213,6 +226,47 @@ def main():
         res["sharded_note"] = "world 1 over RCCL on one GPU: the collectives are device copies; world > 1 unmeasured"
         print(f"sharded step: {med['sharded']:.3f} ms against fused {med['fused']:.3f} ms "
               f"(about 50 B against 30 B of traffic per parameter)")
+    if sprodigy is not None:
+        z, zt, c = sprodigy, sprodigy._tables, sprodigy._comm
+        b3 = HYP["betas"][1] ** 0.5
+        fin = dict(lr=1.0, betas=HYP["betas"], beta3=b3, d0=z.d0, d_coef=z.d_coef, growth_rate=z.growth_rate,
+                   use_bias_correction=False)
+        d_steps = float(z.d)  # (the pieces below run out of their step's order: d means nothing afterwards)
+        pieces = dict(
+            pack=(6.0, lambda: K.zero_pack(zt.tensors, zt.chunks, zt.n_chunks, z._flat32, inv_world=1.0,
+                                           zero_grads=False)),
+            reduce_scatter_f32=(8.0, lambda: c.reduce_scatter_sum(0, z._grad_shard, z._flat32)),
+            shard_norm=(4.0, lambda: K.zero_shard_sqnorm(zt.ranges, zt.n_ranges, z._grad_shard, zt.partials, zt.flags,
+                                                         z._record)),
+            all_gather_norm_record=(0.0, lambda: c.all_gather(0, z._records, z._record)),
+            moments=(36.0, lambda: K.zero_shard_prodigy_moments(zt.ranges, 0, zt.n_ranges, z._grad_shard, z._master,
+                                                                z._p0, z._exp_avg, z._exp_avg_sq, z._s, z._pairs,
+                                                                z._scalars, z._d_block, betas=HYP["betas"], beta3=b3,
+                                                                weight_decay=0.0, d0=z.d0, safeguard_warmup=False,
+                                                                use_clip=True)),
+            record=(0.0, lambda: K.zero_prodigy_record(z._pairs, zt.n_ranges, z._scalars, z._d_record)),
+            all_gather_d_record=(0.0, lambda: c.all_gather(0, z._d_records, z._d_record)),
+            d_update=(0.0, lambda: K.zero_prodigy_finalize(1, z._d_records, 1, z._scalars, z._d_block, **fin)),
+            update=(18.0, lambda: K.zero_shard_prodigy_update(zt.ranges, 0, zt.n_ranges, z._master, z._exp_avg,
+                                                              z._exp_avg_sq, z._mine16, z._scalars, z._d_block,
+                                                              eps=HYP["eps"], weight_decay=HYP["weight_decay"])),
+            all_gather_bf16=(4.0, lambda: c.all_gather(0, z._flat16, z._mine16)),
+            unpack_gated=(4.0, lambda: K.zero_unpack_gated(zt.tensors, zt.chunks, zt.n_chunks, z._flat16, z._scalars,
+                                                           z._d_block)))
+        res["sharded_prodigy_pieces"] = {}
+        yard, total = res["update_pass_gb_per_s"], 0.0
+        for name, (nbytes, fn) in pieces.items():
+            t_ms = sorted(timed(fn, args.iters) for _ in range(args.rounds))[args.rounds // 2]
+            total += t_ms
+            gbs = nbytes * n_params / (t_ms * 1e-3) / 1e9
+            res["sharded_prodigy_pieces"][name] = dict(ms=t_ms, bytes_per_param=nbytes, gb_per_s=gbs,
+                                                       vs_mt_adamw=gbs / yard)
+            rate = f" = {gbs:.0f} GB/s ({gbs / yard:.2f} of vp_mt_adamw_bf16's {yard:.0f} GB/s)" if nbytes else ""
+            print(f"sharded prodigy {name}: {t_ms * 1e3:.1f} us{rate}")
+        other = f" against prodigy {med['prodigy']:.3f} ms" if prodigy is not None else ""
+        print(f"sharded prodigy step: {med['sharded_prodigy']:.3f} ms{other} (the pieces above add up to {total:.3f} "
+              f"ms; d = {d_steps:.3e} after the steps)")
+    if sharded is not None or sprodigy is not None:
         import torch.distributed as dist
         dist.destroy_process_group()
     print(f"fused: {med['fused']:.3f} ms = {bw / 1e9:.0f} GB/s = {bw / HBM:.2f} of 6.3 TB/s "

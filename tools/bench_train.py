@@ -1,7 +1,8 @@
 """Training-step throughput of the VideoPainter training path on one MI355X.
 
     python tools/bench_train.py [--steps K] [--warmup W] [--height 60 --width 90]
-                                [--optimizer none|torch|fused|adam|prodigy|sharded] [--loss]
+                                [--optimizer none|torch|fused|adam|prodigy|sharded|sharded-adam|sharded-prodigy]
+                                [--loss]
                                 [--fp8-gemm [ffn,qkv,out]] [--rounds R]
 
 One step = the reference's training iteration (train/train_cogvideox_inpainting_i2v_video.py:1856-1892 with the
@@ -17,7 +18,8 @@ choices; --optimizer sharded runs videopainter_amd.ShardedFusedAdamW(max_grad_no
 data-parallel step (csrc/zero.hip): alone it forms a one-rank group, under `torchrun --nproc_per_node N` one rank per
 GPU (the group is initialised as bench.py does, the branch replicated from rank 0 with broadcast_module, every rank
 draws its own latents, and verify_replicas runs after the last step: "replicas_identical" in the JSON line, which
-rank 0 prints).  --loss replaces the synthetic loss gradient with inpainting_v_loss(...).backward()
+rank 0 prints); --optimizer sharded-adam and --optimizer sharded-prodigy run videopainter_amd.ShardedFusedAdam and
+videopainter_amd.ShardedFusedProdigy (lr 1.0) on the same two paths, with the same clip.  --loss replaces the synthetic loss gradient with inpainting_v_loss(...).backward()
 (:1879-1892).  Default: neither.  Random-init weights, synthetic latents.  Prints one JSON line; optimizer_ms = HIP
 events around optimizer.step().
 
@@ -43,6 +45,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 T, F, D, L, LB = 226, 13, 3072, 42, 2
+# --optimizer choice -> (class in videopainter_amd, its options besides betas, weight_decay and max_grad_norm)
+SHARDED = {"sharded": ("ShardedFusedAdamW", dict(lr=1e-5)), "sharded-adam": ("ShardedFusedAdam", dict(lr=1e-5)),
+           "sharded-prodigy": ("ShardedFusedProdigy", dict(lr=1.0))}
 
 
 def flops(ntok: int, nv: int) -> dict:
@@ -64,7 +69,7 @@ def fp8_gemm_ab(args, tr, step, K) -> dict:
     which = set(filter(None, args.fp8_gemm.split(",")))
     if not which or which - {"ffn", "qkv", "out"}:
         raise SystemExit(f"--fp8-gemm takes a subset of ffn,qkv,out, got {args.fp8_gemm!r}")
-    if args.optimizer == "sharded":
+    if args.optimizer in SHARDED:
         raise SystemExit("--fp8-gemm is a single-process A/B")
     rounds = max(5, args.rounds)
     tr.requires_grad_(False)
@@ -120,7 +125,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--height", type=int, default=60)
     ap.add_argument("--width", type=int, default=90)
-    ap.add_argument("--optimizer", choices=("none", "torch", "fused", "adam", "prodigy", "sharded"), default="none")
+    ap.add_argument("--optimizer", choices=("none", "torch", "fused", "adam", "prodigy", *SHARDED), default="none")
     ap.add_argument("--loss", action="store_true",
                     help="inpainting_v_loss(...).backward() instead of out.backward(dout)")
     ap.add_argument("--classes", action="store_true", help="per-class HIP-event timing pass afterwards")
@@ -136,7 +141,7 @@ def main():
 
     dev = "cuda"
     rank, world = 0, 1
-    if args.optimizer == "sharded":
+    if args.optimizer in SHARDED:
         import torch.distributed as dist
         from videopainter_amd import distributed as VD
         rank, world, local = VD.env_rank_world()
@@ -176,10 +181,11 @@ def main():
     elif args.optimizer == "prodigy":
         from videopainter_amd import FusedProdigy
         opt = FusedProdigy(params, lr=1.0, betas=(0.9, 0.95), weight_decay=1e-4, max_grad_norm=1.0)
-    elif args.optimizer == "sharded":
-        from videopainter_amd import ShardedFusedAdamW
+    elif args.optimizer in SHARDED:
+        import videopainter_amd
+        name, kw = SHARDED[args.optimizer]
         VD.broadcast_module(br, src=0, always=True)  # the replicas start from rank 0's bytes
-        opt = ShardedFusedAdamW(params, lr=1e-5, betas=(0.9, 0.95), weight_decay=1e-4, max_grad_norm=1.0)
+        opt = getattr(videopainter_amd, name)(params, betas=(0.9, 0.95), weight_decay=1e-4, max_grad_norm=1.0, **kw)
 
     g = torch.Generator().manual_seed(7 + rank)  # (every rank its own data)
     lat = torch.randn(1, F, 16, HL, WL, generator=g).to(dev, torch.bfloat16)
@@ -237,7 +243,7 @@ def main():
         print(f"step {i}: {time.perf_counter() - t0:.2f}s", file=sys.stderr, flush=True)
     el = (time.perf_counter() - t0) / args.steps
     replicas = None
-    if args.optimizer == "sharded":
+    if args.optimizer in SHARDED:
         el = VD.max_over_ranks(el, dev)
         ok, n_buckets = VD.verify_replicas(br, always=True)
         replicas = dict(identical=ok, buckets=n_buckets, world=world)
@@ -247,7 +253,9 @@ def main():
                optimizer={"none": None, "torch": "torch AdamW foreach",
                           "fused": "FusedAdamW(max_grad_norm=1.0)", "adam": "FusedAdam(max_grad_norm=1.0)",
                           "prodigy": "FusedProdigy(lr=1.0, max_grad_norm=1.0)",
-                          "sharded": "ShardedFusedAdamW(max_grad_norm=1.0)"}[args.optimizer],
+                          "sharded": "ShardedFusedAdamW(max_grad_norm=1.0)",
+                          "sharded-adam": "ShardedFusedAdam(max_grad_norm=1.0)",
+                          "sharded-prodigy": "ShardedFusedProdigy(lr=1.0, max_grad_norm=1.0)"}[args.optimizer],
                optimizer_ms=(sum(a.elapsed_time(b) for a, b in opt_events) / len(opt_events)) if opt_events else None,
                loss="inpainting_v_loss" if args.loss else None,
                tflops_per_s=fl["total"] / el / 1e12, flop_per_step=fl, ntok=ntok,
@@ -264,7 +272,7 @@ def main():
         res["counts"] = {n: tl.count(n) for n in ("gemm", "attention", "attention_bwd")}
     if rank == 0:
         print(json.dumps(res))
-    if args.optimizer == "sharded":
+    if args.optimizer in SHARDED:
         dist.destroy_process_group()
 
 

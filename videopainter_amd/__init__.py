@@ -34,7 +34,7 @@ def __getattr__(name):
     if name in ("FusedAdamW", "FusedAdam", "FusedProdigy", "clip_grad_norm_", "get_gradient_norm"):
         from . import optim
         return getattr(optim, name)
-    if name in ("ShardedFusedAdamW",):
+    if name in ("ShardedFusedAdamW", "ShardedFusedAdam", "ShardedFusedProdigy"):
         from . import zero
         return getattr(zero, name)
     if name in ("inpainting_v_loss",):

@@ -11,7 +11,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VP_HIP_LIB", os.path.join(_HERE, "_lib", "libvp_hip.so"))
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 vp = C.c_void_p
 i32 = C.c_int32
@@ -241,6 +241,15 @@ _SIGS = {
     "vp_zero_finalize": (i32, [vp, i32, f32, C.c_double, C.c_double, i32, vp, vp]),
     "vp_zero_shard_adamw": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, i64, vp, C.c_double, C.c_double, C.c_double,
                                   C.c_double, C.c_double, i32, vp]),
+    "vp_zero_shard_adam": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, i64, vp, C.c_double, C.c_double, C.c_double,
+                                 C.c_double, C.c_double, i32, vp]),
+    "vp_zero_shard_prodigy_moments": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, C.c_double,
+                                            C.c_double, C.c_double, C.c_double, C.c_double, i32, i32, vp]),
+    "vp_zero_prodigy_record": (i32, [vp, i32, vp, vp, vp]),
+    "vp_zero_prodigy_finalize": (i32, [i32, vp, i32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                       C.c_double, C.c_double, i32, vp, vp, vp]),
+    "vp_zero_shard_prodigy_update": (i32, [vp, i32, i32, vp, vp, vp, vp, i64, vp, vp, C.c_double, C.c_double, vp]),
+    "vp_zero_unpack_gated_bf16": (i32, [vp, vp, i32, vp, i64, vp, vp, vp]),
 }
 
 EXPORTS = tuple(_SIGS)

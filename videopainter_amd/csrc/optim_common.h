@@ -2,10 +2,11 @@
 // everything but the decoding of their tables and the choice of each piece's scalar head: the workgroup shape and its
 // fixed-order sum, stream_piece (scalar head / 16-byte body / scalar tail of one piece), the zero fill, the gradient
 // norm's first stage (sqnorm_piece) and finaliser, the AdamW update of one piece (adam_piece), the two passes of
-// Prodigy over one piece (prodigy_moments_piece, prodigy_update_piece: csrc/prodigy.hip) and the host-side argument
-// checks.  Both AdamW kernels are adam_piece around the SAME adam_element(), and every multiply-add in it is
-// spelled out with contraction off, so they cannot drift apart by a fused multiply-add: a world-1 sharded step is
-// bit-identical to the single-GPU step.
+// Prodigy over one piece (prodigy_moments_piece, prodigy_update_piece), Prodigy's one-workgroup finaliser (the strided
+// double sum, dlr, the d update: over the chunks' pairs in csrc/prodigy.hip, over the ranks' records in csrc/zero.hip)
+// and the host-side argument checks.  Both AdamW kernels are adam_piece around the SAME adam_element(), and every
+// multiply-add in it is spelled out with contraction off, so they cannot drift apart by a fused multiply-add: a
+// world-1 sharded step is bit-identical to the single-GPU step.
 #pragma once
 #include <type_traits>
 
@@ -419,6 +420,92 @@ VP_DEV void optim_finalize_body(const float* __restrict__ partials, const int* _
   sc->step = step;
   sc->bias_c1 = (float)(1.0 - pow(beta1, (double)step));
   sc->bias_c2 = (float)(1.0 - pow(beta2, (double)step));
+}
+
+// ---- Prodigy's finaliser (one workgroup), shared by csrc/prodigy.hip (the sums run over the chunks' pairs) and
+// csrc/zero.hip (over the ranks' records): the fixed-order double sum, dlr of the step, and the d update ----
+
+// fixed-order sum of doubles over the workgroup, as block_sum; valid in thread 0
+VP_DEV double block_sum_f64(double v) {
+  __shared__ double red64[OT / 64];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  if ((threadIdx.x & 63) == 0) red64[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = 0.0;
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int w = 0; w < OT / 64; ++w) s += red64[w];
+  }
+  __syncthreads();
+  return s;
+}
+
+// (sum of x[0], x[2], ...; sum of x[1], x[3], ...) over n pairs of fp32 or double: thread t takes pairs t, t + OT, ...
+// in order, in double, then the fixed block sum; valid in thread 0
+template <class T>
+VP_DEV void sum_pairs_f64(const T* __restrict__ x, int n, double& a, double& b) {
+#pragma clang fp contract(off)
+  double sa = 0.0, sb = 0.0;
+  for (int i = threadIdx.x; i < n; i += OT) {
+    sa += (double)x[2 * (int64_t)i];
+    sb += (double)x[2 * (int64_t)i + 1];
+  }
+  a = block_sum_f64(sa);
+  b = block_sum_f64(sb);
+}
+
+struct ProdigyFinalizeArgs {
+  double lr, beta1, beta2, beta3, d0, d_coef, growth_rate;
+  int use_bias_correction;
+};
+
+inline bool finite_nonneg(double x) { return x >= 0.0 && x <= 1.79769313486231570e308; }
+inline bool prodigy_finalize_args_ok(double lr, double beta1, double beta2, double beta3, double d0, double d_coef,
+                                     double growth_rate) {
+  return finite_nonneg(lr) && prodigy_hyper_ok(beta1, beta2, beta3, d0) && finite_nonneg(d0) && d_coef > 0.0 &&
+         finite_nonneg(d_coef) && growth_rate >= 1.0;  // (growth_rate may be +inf: no limit)
+}
+
+// phase 0 (every thread may call; thread 0 writes): dlr of the step from the OLD d and the counter the norm's finaliser
+// has advanced already
+VP_DEV void prodigy_dlr_body(const ProdigyFinalizeArgs& a, const vp_optim_scalars* __restrict__ sc,
+                             vp_prodigy_scalars* __restrict__ ds) {
+#pragma clang fp contract(off)
+  if (threadIdx.x != 0 || sc->skipped) return;
+  double bc = 1.0;
+  if (a.use_bias_correction) {
+    const double step = (double)sc->step;  // k + 1
+    bc = sqrt(1.0 - pow(a.beta2, step)) / (1.0 - pow(a.beta1, step));
+  }
+  ds->dlr = ds->d * a.lr * bc;
+}
+
+// phase 1 after the sums (thread 0 only): the d update from dot = sum <g, p0 - p> and den = sum |s|
+VP_DEV void prodigy_d_update(double dot, double den, const ProdigyFinalizeArgs& a, vp_optim_scalars* __restrict__ sc,
+                             vp_prodigy_scalars* __restrict__ ds) {
+#pragma clang fp contract(off)
+  if (den == 0.0) {  // no progress: pass 2 writes nothing, the counter goes back, d and its numerator stay
+    ds->d_denom = 0.0;
+    ds->no_progress = 1;
+    sc->step = sc->step - 1;
+    return;
+  }
+  double d = ds->d, d_max = ds->d_max;
+  const double num = ds->d_numerator * a.beta3 + (d / a.d0) * ds->dlr * dot;
+  ds->d_numerator = num;
+  ds->d_denom = den;
+  ds->no_progress = 0;
+  if (a.lr > 0.0) {
+    const double d_hat = a.d_coef * num / den;
+    if (d == a.d0) d = d > d_hat ? d : d_hat;
+    d_max = d_max > d_hat ? d_max : d_hat;
+    const double grown = d * a.growth_rate;
+    d = d_max < grown ? d_max : grown;
+    ds->d_hat = d_hat;
+    ds->d_max = d_max;
+    ds->d = d;
+  }
 }
 
 }  // namespace vp_optim

@@ -10,77 +10,24 @@ namespace {
 
 using namespace vp_optim;
 
-// fixed-order sum of doubles over the workgroup, as block_sum; valid in thread 0
-VP_DEV double block_sum_f64(double v) {
-  __shared__ double red64[OT / 64];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  if ((threadIdx.x & 63) == 0) red64[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int w = 0; w < OT / 64; ++w) s += red64[w];
-  }
-  __syncthreads();
-  return s;
-}
-
-struct FinalizeArgs {
-  double lr, beta1, beta2, beta3, d0, d_coef, growth_rate;
-  int use_bias_correction;
-};
-
 // ---- phase 0: dlr of the step from the OLD d and the counter vp_optim_finalize has advanced already ----
-__global__ __launch_bounds__(OT) void prodigy_begin_kernel(const FinalizeArgs a,
+__global__ __launch_bounds__(OT) void prodigy_begin_kernel(const ProdigyFinalizeArgs a,
                                                            const vp_optim_scalars* __restrict__ sc,
                                                            vp_prodigy_scalars* __restrict__ ds) {
-#pragma clang fp contract(off)
-  if (threadIdx.x != 0 || sc->skipped) return;
-  double bc = 1.0;
-  if (a.use_bias_correction) {
-    const double step = (double)sc->step;  // k + 1
-    bc = sqrt(1.0 - pow(a.beta2, step)) / (1.0 - pow(a.beta1, step));
-  }
-  ds->dlr = ds->d * a.lr * bc;
+  prodigy_dlr_body(a, sc, ds);
 }
 
 // ---- phase 1: the two sums (thread t takes chunks t, t + OT, ... in order, then the fixed block sum) and the d
-// update ----
+// update (optim_common.h: the sharded finaliser runs the same body over the ranks' records) ----
 __global__ __launch_bounds__(OT) void prodigy_end_kernel(const float* __restrict__ partials, int n,
-                                                         const FinalizeArgs a, vp_optim_scalars* __restrict__ sc,
+                                                         const ProdigyFinalizeArgs a,
+                                                         vp_optim_scalars* __restrict__ sc,
                                                          vp_prodigy_scalars* __restrict__ ds) {
-#pragma clang fp contract(off)
   if (sc->skipped) return;  // (uniform: every thread reads the same word)
-  double dot = 0.0, den = 0.0;
-  for (int i = threadIdx.x; i < n; i += OT) {
-    dot += (double)partials[2 * (int64_t)i];
-    den += (double)partials[2 * (int64_t)i + 1];
-  }
-  dot = block_sum_f64(dot);
-  den = block_sum_f64(den);
+  double dot, den;
+  sum_pairs_f64(partials, n, dot, den);
   if (threadIdx.x != 0) return;
-  if (den == 0.0) {  // no progress: pass 2 writes nothing, the counter goes back, d and its numerator stay
-    ds->d_denom = 0.0;
-    ds->no_progress = 1;
-    sc->step = sc->step - 1;
-    return;
-  }
-  double d = ds->d, d_max = ds->d_max;
-  const double num = ds->d_numerator * a.beta3 + (d / a.d0) * ds->dlr * dot;
-  ds->d_numerator = num;
-  ds->d_denom = den;
-  ds->no_progress = 0;
-  if (a.lr > 0.0) {
-    const double d_hat = a.d_coef * num / den;
-    if (d == a.d0) d = d > d_hat ? d : d_hat;
-    d_max = d_max > d_hat ? d_max : d_hat;
-    const double grown = d * a.growth_rate;
-    d = d_max < grown ? d_max : grown;
-    ds->d_hat = d_hat;
-    ds->d_max = d_max;
-    ds->d = d;
-  }
+  prodigy_d_update(dot, den, a, sc, ds);
 }
 
 // ---- pass 1 ----
@@ -128,8 +75,6 @@ __global__ __launch_bounds__(OT) void mt_prodigy_update_kernel(
   prodigy_update_piece(pm, mm, vm, w, head, r.n, prodigy_update_coef(eps, weight_decay, ds));
 }
 
-bool finite_nonneg(double x) { return x >= 0.0 && x <= 1.79769313486231570e308; }
-
 }  // namespace
 
 extern "C" int vp_prodigy_finalize(int32_t phase, const float* partials, int32_t n_chunks, double lr, double beta1,
@@ -137,11 +82,9 @@ extern "C" int vp_prodigy_finalize(int32_t phase, const float* partials, int32_t
                                    int32_t use_bias_correction, vp_optim_scalars* scalars, vp_prodigy_scalars* dstate,
                                    void* stream) {
   if (!scalars || !dstate || (phase != 0 && phase != 1)) return VP_ERR_ARG;
-  if (!finite_nonneg(lr) || !prodigy_hyper_ok(beta1, beta2, beta3, d0) || !finite_nonneg(d0) || !(d_coef > 0.0) ||
-      !finite_nonneg(d_coef) || !(growth_rate >= 1.0))  // (growth_rate may be +inf: no limit)
-    return VP_ERR_ARG;
+  if (!prodigy_finalize_args_ok(lr, beta1, beta2, beta3, d0, d_coef, growth_rate)) return VP_ERR_ARG;
   if (phase == 1 && (n_chunks < 0 || (n_chunks > 0 && !partials))) return VP_ERR_ARG;
-  const FinalizeArgs a{lr, beta1, beta2, beta3, d0, d_coef, growth_rate, use_bias_correction};
+  const ProdigyFinalizeArgs a{lr, beta1, beta2, beta3, d0, d_coef, growth_rate, use_bias_correction};
   if (phase == 0)
     hipLaunchKernelGGL(prodigy_begin_kernel, dim3(1), dim3(OT), 0, (hipStream_t)stream, a, scalars, dstate);
   else

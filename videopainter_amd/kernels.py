@@ -1851,6 +1851,117 @@ def zero_shard_adamw(ranges: Optional[torch.Tensor], range_begin: int, n_ranges:
                                         eps, weight_decay, int(use_clip), _stream()), "vp_zero_shard_adamw")
 
 
+def zero_shard_adam(ranges: Optional[torch.Tensor], range_begin: int, n_ranges: int, grad_shard: torch.Tensor,
+                    master: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, param_shard: torch.Tensor,
+                    scalars: torch.Tensor, *, lr: float, betas, eps: float, weight_decay: float,
+                    use_clip: bool) -> None:
+    """zero_shard_adamw with torch.optim.Adam's decay: an L2 term on the gradient instead of the factor on the
+    master."""
+    per = grad_shard.numel()
+    for t, n in ((grad_shard, "grad_shard"), (master, "master"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+        _flat1(t, n, torch.float32)
+    _flat1(param_shard, "param_shard", BF16)
+    if any(t.numel() != per for t in (master, exp_avg, exp_avg_sq, param_shard)):
+        raise ValueError("zero_shard_adam: the shard buffers differ in length")
+    _chk_scalars(scalars, "zero_shard_adam")
+    N.check(N.lib().vp_zero_shard_adam(_p(ranges), range_begin, n_ranges, _p(grad_shard), _p(master), _p(exp_avg),
+                                       _p(exp_avg_sq), _p(param_shard), per, _p(scalars), lr, betas[0], betas[1],
+                                       eps, weight_decay, int(use_clip), _stream()), "vp_zero_shard_adam")
+
+
+def _chk_shards(who: str, shards, param_shard: Optional[torch.Tensor] = None) -> int:
+    """The fp32 [per] shard buffers (name, tensor) of one launch, and the bf16 one: 1-D, contiguous, one length."""
+    per = shards[0][1].numel()
+    for n, t in shards:
+        _flat1(t, n, torch.float32)
+    if param_shard is not None:
+        _flat1(param_shard, "param_shard", BF16)
+    if any(t.numel() != per for _, t in shards) or (param_shard is not None and param_shard.numel() != per):
+        raise ValueError(f"{who}: the shard buffers differ in length")
+    return per
+
+
+def zero_shard_prodigy_moments(ranges: Optional[torch.Tensor], range_begin: int, n_ranges: int,
+                               grad_shard: torch.Tensor, master: torch.Tensor, p0: torch.Tensor,
+                               exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, s: torch.Tensor,
+                               partials: torch.Tensor, scalars: torch.Tensor, dstate: torch.Tensor, *, betas,
+                               beta3: float, weight_decay: float, d0: float, safeguard_warmup: bool,
+                               use_clip: bool) -> None:
+    """Prodigy's pass 1 over ranges [range_begin, range_begin + n_ranges) of this rank's shard (one parameter group):
+    moments, s and the ranges' (dot, sum |s|) pairs.  `weight_decay` is the coupled decay (0 when decoupled)."""
+    who = "zero_shard_prodigy_moments"
+    per = _chk_shards(who, (("grad_shard", grad_shard), ("master", master), ("p0", p0), ("exp_avg", exp_avg),
+                            ("exp_avg_sq", exp_avg_sq), ("s", s)))
+    _chk_scalars(scalars, who)
+    _chk_dstate(dstate, who)
+    if range_begin < 0:
+        raise ValueError(f"{who}: negative range_begin")
+    _chk_pairs(partials, range_begin + n_ranges, who)
+    N.check(N.lib().vp_zero_shard_prodigy_moments(_p(ranges), range_begin, n_ranges, _p(grad_shard), _p(master),
+                                                  _p(p0), _p(exp_avg), _p(exp_avg_sq), _p(s), per, _p(partials),
+                                                  _p(scalars), _p(dstate), betas[0], betas[1], beta3, weight_decay,
+                                                  d0, int(safeguard_warmup), int(use_clip), _stream()),
+            "vp_zero_shard_prodigy_moments")
+
+
+def _chk_records(records: torch.Tensor, n: int, who: str) -> None:
+    _chk(records, "records", torch.float64)
+    if n < 0 or records.numel() < 2 * n or not records.is_contiguous():
+        raise ValueError(f"{who}: records hold fewer than {n} (dot, sum |s|) pairs of doubles")
+
+
+def zero_prodigy_record(partials: torch.Tensor, n_ranges: int, scalars: torch.Tensor, record: torch.Tensor) -> None:
+    """This rank's Prodigy record (float64[2]): the fixed-order double sums of its ranges' (dot, sum |s|) pairs."""
+    _chk_pairs(partials, n_ranges, "zero_prodigy_record")
+    _chk_scalars(scalars, "zero_prodigy_record")
+    _chk_records(record, 1, "zero_prodigy_record")
+    N.check(N.lib().vp_zero_prodigy_record(_p(partials), n_ranges, _p(scalars), _p(record), _stream()),
+            "vp_zero_prodigy_record")
+
+
+def zero_prodigy_finalize(phase: int, records: Optional[torch.Tensor], world: int, scalars: torch.Tensor,
+                          dstate: torch.Tensor, *, lr: float, betas, beta3: float, d0: float, d_coef: float,
+                          growth_rate: float, use_bias_correction: bool) -> None:
+    """prodigy_finalize over the ranks' records (float64 [world, 2], rank order): phase 0 the step's dlr, phase 1 the
+    d update — the same `dstate` block on every rank."""
+    if phase not in (0, 1):
+        raise ValueError("zero_prodigy_finalize: phase must be 0 or 1")
+    _chk_scalars(scalars, "zero_prodigy_finalize")
+    _chk_dstate(dstate, "zero_prodigy_finalize")
+    if phase == 1:
+        if world < 1:
+            raise ValueError("zero_prodigy_finalize: world must be positive")
+        _chk_records(records, world, "zero_prodigy_finalize")
+    N.check(N.lib().vp_zero_prodigy_finalize(phase, _p(records), world, lr, betas[0], betas[1], beta3, d0, d_coef,
+                                             growth_rate, int(use_bias_correction), _p(scalars), _p(dstate),
+                                             _stream()), "vp_zero_prodigy_finalize")
+
+
+def zero_shard_prodigy_update(ranges: Optional[torch.Tensor], range_begin: int, n_ranges: int, master: torch.Tensor,
+                              exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, param_shard: torch.Tensor,
+                              scalars: torch.Tensor, dstate: torch.Tensor, *, eps: float,
+                              weight_decay: float) -> None:
+    """Prodigy's pass 2 over the same ranges: the update with the new d, bf16(master) into the bf16 shard.
+    `weight_decay` is the decoupled decay (0 when coupled)."""
+    who = "zero_shard_prodigy_update"
+    per = _chk_shards(who, (("master", master), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)), param_shard)
+    _chk_scalars(scalars, who)
+    _chk_dstate(dstate, who)
+    N.check(N.lib().vp_zero_shard_prodigy_update(_p(ranges), range_begin, n_ranges, _p(master), _p(exp_avg),
+                                                 _p(exp_avg_sq), _p(param_shard), per, _p(scalars), _p(dstate), eps,
+                                                 weight_decay, _stream()), "vp_zero_shard_prodigy_update")
+
+
+def zero_unpack_gated(tensors: torch.Tensor, chunks: torch.Tensor, n_chunks: int, flat: torch.Tensor,
+                      scalars: torch.Tensor, dstate: torch.Tensor) -> None:
+    """zero_unpack that also leaves every parameter alone in a no-progress step of Prodigy (`dstate`)."""
+    _flat1(flat, "flat", BF16)
+    _chk_scalars(scalars, "zero_unpack_gated")
+    _chk_dstate(dstate, "zero_unpack_gated")
+    N.check(N.lib().vp_zero_unpack_gated_bf16(_p(tensors), _p(chunks), n_chunks, _p(flat), flat.numel(), _p(scalars),
+                                              _p(dstate), _stream()), "vp_zero_unpack_gated_bf16")
+
+
 def scale(x: torch.Tensor, s: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """bf16(x * s) with s a one-element fp32 DEVICE tensor (no host read)."""
     _flat(x, "x")

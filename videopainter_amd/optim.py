@@ -18,9 +18,10 @@ back every step.
 Nothing here copies device memory to the host or synchronises: the norm, the clip coefficient, the non-finite flag,
 the step counter and the bias corrections live in a small device block the kernels read, and so does Prodigy's d.
 
-The data-parallel optimizer (zero.ShardedFusedAdamW) is built on the same parts: `_FlatAdamW` (validation, the flat
-layout of `flat_offsets`, the scalars block, the state-dict checks, the step prologue) and `DeviceTables` (the table
-uploader over `pack_tables`).
+The data-parallel optimizers (zero.ShardedFusedAdamW, ShardedFusedAdam, ShardedFusedProdigy) are built on the same
+parts: `_FlatAdamW` (validation, the flat layout of `flat_offsets`, the scalars block, the state-dict checks, the step
+prologue), `_ProdigyCore` (Prodigy's options, its d block and state-dict entry) and `DeviceTables` (the table uploader
+over `pack_tables`).
 """
 from __future__ import annotations
 
@@ -473,34 +474,14 @@ _PRODIGY_KEYS = ("master", "exp_avg", "exp_avg_sq", "s", "p0")
 _D_FIELDS = ("d", "d_max", "d_hat", "d_numerator", "d_denom", "dlr")  # N.ProdigyScalars, its doubles in order
 
 
-class FusedProdigy(_FlatAdamW):
-    """prodigyopt.Prodigy (1.0, slice_p = 1, no FSDP) for bf16 device parameters with fp32 master weights: the
-    reference's `--optimizer prodigy`.  Its distance estimate is built from p0 - p, which on bf16 parameters is mostly
-    rounding noise; here p is the fp32 master.
+class _ProdigyCore:
+    """What `FusedProdigy` and `zero.ShardedFusedProdigy` share beside `_FlatAdamW`: the validation of Prodigy's own
+    options, the check of what every group must share, the float64[7] d block (N.ProdigyScalars) with its read-only
+    views, and the "prodigy" entry of a state dict.  A subclass allocates `_d_block` with `_alloc_d_block`."""
 
-    State lives in five flat fp32 device buffers (master, exp_avg, exp_avg_sq, s, p0 — the initial master);
-    `state[p]` exposes per-parameter views of them plus the shared device step counter.  d, d_max, d_hat,
-    d_numerator, d_denom and the dlr of the last step are doubles in a device block (`d_block`, N.ProdigyScalars; the
-    reference keeps them in Python floats), read through the properties of the same names; `no_progress` is 1 after
-    a step that found d_denom == 0.  `step()` is gradient norm, its finaliser, dlr from the old d, pass 1 per group
-    (moments, s, one (dot, sum |s|) pair per chunk), the d update, pass 2 per group (the update with the new d in
-    d * eps) — no device-to-host copy, no synchronisation, bit-identical run to run.
-
-    `max_grad_norm`, `skip_nonfinite` and `zero_grads` mean what they mean on `FusedAdamW`; a skipped step leaves all
-    five buffers, the d block and the counter as they were.
-
-    Differences from prodigyopt's: lr, betas and beta3 must be the same in every parameter group, checked every step
-    (prodigyopt also lets a group sit at lr = 0; that is not built), weight_decay and eps may differ; one step
-    counter; decouple, use_bias_correction, safeguard_warmup, d0, d_coef and growth_rate belong to the optimizer, not
-    to a group; a step with d_denom == 0 changes no parameter, not the counter and nothing of the d block but d_denom
-    and `no_progress` (the moments and s were updated, as there); parameters must be bf16, contiguous, on one
-    device; slice_p and fsdp_in_use do not exist."""
-
-    def __init__(self, params, lr: float = 1.0, betas=(0.9, 0.999), beta3: Optional[float] = None, eps: float = 1e-8,
-                 weight_decay: float = 0.0, decouple: bool = True, use_bias_correction: bool = False,
-                 safeguard_warmup: bool = False, d0: float = 1e-6, d_coef: float = 1.0,
-                 growth_rate: float = float("inf"), *, max_grad_norm: Optional[float] = None,
-                 skip_nonfinite: bool = False, zero_grads: bool = False):
+    @staticmethod
+    def _check_prodigy_args(name, params, lr, beta3, d0, d_coef, growth_rate):
+        """Validates the options `_FlatAdamW` does not know; returns the parameters as a list."""
         if not 0.0 < d0 < float("inf"):
             raise ValueError(f"Invalid d0 value: {d0}")
         if not 0.0 < d_coef < float("inf"):
@@ -512,8 +493,11 @@ class FusedProdigy(_FlatAdamW):
         params = list(params)
         groups = [g for g in params if isinstance(g, dict)]
         if len({float(g.get("lr", lr)) for g in groups}) > 1 or len({g.get("beta3", beta3) for g in groups}) > 1:
-            raise ValueError("FusedProdigy: lr and beta3 must be the same in every parameter group")
-        super().__init__(params, lr, betas, eps, weight_decay, max_grad_norm, skip_nonfinite, zero_grads)
+            raise ValueError(f"{name}: lr and beta3 must be the same in every parameter group")
+        return params
+
+    def _set_prodigy_options(self, beta3, decouple, use_bias_correction, safeguard_warmup, d0, d_coef, growth_rate):
+        """After `_FlatAdamW.__init__`: beta3 into the groups, the optimizer-wide options, the first shared check."""
         self.defaults["beta3"] = beta3
         for g in self.param_groups:
             g.setdefault("beta3", beta3)
@@ -521,35 +505,26 @@ class FusedProdigy(_FlatAdamW):
         self.safeguard_warmup = bool(safeguard_warmup)
         self.d0, self.d_coef, self.growth_rate = float(d0), float(d_coef), float(growth_rate)
         self._check_shared()
-        self._alloc_scalars()
+
+    def _alloc_d_block(self) -> None:
         self._d_block = torch.tensor([self.d0] * 3 + [0.0] * 4, dtype=torch.float64).to(self._device)
-        self._master = torch.zeros(max(self.total, 1), device=self._device, dtype=torch.float32)
-        self._exp_avg = torch.zeros_like(self._master)
-        self._exp_avg_sq = torch.zeros_like(self._master)
-        self._s = torch.zeros_like(self._master)
-        self._tables = MultiTensorTables(self._device)
-        self._pairs = None  # fp32 [2 * chunks]: pass 1's (dot, sum |s|) of every chunk
-        with torch.no_grad():
-            for p in self._params:
-                o, n = self._offs[p], p.numel()
-                self._master[o:o + n].copy_(p.detach().reshape(-1))
-            self._p0 = self._master.clone()
-            for p in self._params:
-                o, n = self._offs[p], p.numel()
-                self.state[p] = dict(step=self._scalars[3], **{k: getattr(self, "_" + k)[o:o + n].view(p.shape)
-                                                               for k in _PRODIGY_KEYS})
 
     def _check_shared(self) -> Tuple[float, float]:
         """(lr, beta3) of the step: what every group must share besides the betas."""
         g0 = self.param_groups[0]
         for g in self.param_groups:
             if float(g["lr"]) != float(g0["lr"]) or g["beta3"] != g0["beta3"]:
-                raise ValueError("FusedProdigy: lr and beta3 must be the same in every parameter group")
+                raise ValueError(f"{type(self).__name__}: lr and beta3 must be the same in every parameter group")
         lr = float(g0["lr"])
         beta3 = float(g0["betas"][1]) ** 0.5 if g0["beta3"] is None else float(g0["beta3"])
         if not 0.0 <= lr < float("inf"):
             raise ValueError(f"Invalid learning rate: {lr}")
         return lr, beta3
+
+    def _finalize_args(self, lr: float, betas, beta3: float) -> dict:
+        """The keyword arguments both phases of the d finaliser take."""
+        return dict(lr=lr, betas=betas, beta3=beta3, d0=self.d0, d_coef=self.d_coef, growth_rate=self.growth_rate,
+                    use_bias_correction=self.use_bias_correction)
 
     # the d block of the last step (0-dim float64 device tensors)
     @property
@@ -585,6 +560,79 @@ class FusedProdigy(_FlatAdamW):
         """The whole float64[7] block (N.ProdigyScalars; the last slot holds the int32 `no_progress`)."""
         return self._d_block
 
+    def _prodigy_dict(self) -> dict:
+        """The "prodigy" entry of a state dict: the d block's values and the optimizer-wide options (a device-to-host
+        copy; not on the step path)."""
+        block = self._d_block.cpu()
+        return dict(zip(_D_FIELDS, block[:6].tolist()), no_progress=int(block.view(torch.int32)[12]),
+                    decouple=self.decouple, use_bias_correction=self.use_bias_correction,
+                    safeguard_warmup=self.safeguard_warmup, d0=self.d0, d_coef=self.d_coef,
+                    growth_rate=self.growth_rate)
+
+    @staticmethod
+    def _prodigy_entry(state_dict) -> dict:
+        if "prodigy" not in state_dict:
+            raise ValueError("loaded state dict has no d block (not a FusedProdigy state dict)")
+        return state_dict["prodigy"]
+
+    def _load_prodigy_dict(self, pr: dict) -> None:
+        self.decouple, self.use_bias_correction = bool(pr["decouple"]), bool(pr["use_bias_correction"])
+        self.safeguard_warmup = bool(pr["safeguard_warmup"])
+        self.d0, self.d_coef, self.growth_rate = float(pr["d0"]), float(pr["d_coef"]), float(pr["growth_rate"])
+        block = torch.tensor([float(pr[k]) for k in _D_FIELDS] + [0.0], dtype=torch.float64)
+        block.view(torch.int32)[12] = int(pr["no_progress"])
+        self._d_block.copy_(block.to(self._device))
+
+
+class FusedProdigy(_ProdigyCore, _FlatAdamW):
+    """prodigyopt.Prodigy (1.0, slice_p = 1, no FSDP) for bf16 device parameters with fp32 master weights: the
+    reference's `--optimizer prodigy`.  Its distance estimate is built from p0 - p, which on bf16 parameters is mostly
+    rounding noise; here p is the fp32 master.
+
+    State lives in five flat fp32 device buffers (master, exp_avg, exp_avg_sq, s, p0 — the initial master);
+    `state[p]` exposes per-parameter views of them plus the shared device step counter.  d, d_max, d_hat,
+    d_numerator, d_denom and the dlr of the last step are doubles in a device block (`d_block`, N.ProdigyScalars; the
+    reference keeps them in Python floats), read through the properties of the same names; `no_progress` is 1 after
+    a step that found d_denom == 0.  `step()` is gradient norm, its finaliser, dlr from the old d, pass 1 per group
+    (moments, s, one (dot, sum |s|) pair per chunk), the d update, pass 2 per group (the update with the new d in
+    d * eps) — no device-to-host copy, no synchronisation, bit-identical run to run.
+
+    `max_grad_norm`, `skip_nonfinite` and `zero_grads` mean what they mean on `FusedAdamW`; a skipped step leaves all
+    five buffers, the d block and the counter as they were.
+
+    Differences from prodigyopt's: lr, betas and beta3 must be the same in every parameter group, checked every step
+    (prodigyopt also lets a group sit at lr = 0; that is not built), weight_decay and eps may differ; one step
+    counter; decouple, use_bias_correction, safeguard_warmup, d0, d_coef and growth_rate belong to the optimizer, not
+    to a group; a step with d_denom == 0 changes no parameter, not the counter and nothing of the d block but d_denom
+    and `no_progress` (the moments and s were updated, as there); parameters must be bf16, contiguous, on one
+    device; slice_p and fsdp_in_use do not exist."""
+
+    def __init__(self, params, lr: float = 1.0, betas=(0.9, 0.999), beta3: Optional[float] = None, eps: float = 1e-8,
+                 weight_decay: float = 0.0, decouple: bool = True, use_bias_correction: bool = False,
+                 safeguard_warmup: bool = False, d0: float = 1e-6, d_coef: float = 1.0,
+                 growth_rate: float = float("inf"), *, max_grad_norm: Optional[float] = None,
+                 skip_nonfinite: bool = False, zero_grads: bool = False):
+        params = self._check_prodigy_args("FusedProdigy", params, lr, beta3, d0, d_coef, growth_rate)
+        super().__init__(params, lr, betas, eps, weight_decay, max_grad_norm, skip_nonfinite, zero_grads)
+        self._set_prodigy_options(beta3, decouple, use_bias_correction, safeguard_warmup, d0, d_coef, growth_rate)
+        self._alloc_scalars()
+        self._alloc_d_block()
+        self._master = torch.zeros(max(self.total, 1), device=self._device, dtype=torch.float32)
+        self._exp_avg = torch.zeros_like(self._master)
+        self._exp_avg_sq = torch.zeros_like(self._master)
+        self._s = torch.zeros_like(self._master)
+        self._tables = MultiTensorTables(self._device)
+        self._pairs = None  # fp32 [2 * chunks]: pass 1's (dot, sum |s|) of every chunk
+        with torch.no_grad():
+            for p in self._params:
+                o, n = self._offs[p], p.numel()
+                self._master[o:o + n].copy_(p.detach().reshape(-1))
+            self._p0 = self._master.clone()
+            for p in self._params:
+                o, n = self._offs[p], p.numel()
+                self.state[p] = dict(step=self._scalars[3], **{k: getattr(self, "_" + k)[o:o + n].view(p.shape)
+                                                               for k in _PRODIGY_KEYS})
+
     @torch.no_grad()
     def step(self, closure=None):
         from . import kernels as K
@@ -593,8 +641,7 @@ class FusedProdigy(_FlatAdamW):
         params = [p for g in self.param_groups for p in g["params"] if p.grad is not None]
         t = self._tables
         use_clip = self.max_grad_norm is not None
-        fin = dict(lr=lr, betas=betas, beta3=beta3, d0=self.d0, d_coef=self.d_coef, growth_rate=self.growth_rate,
-                   use_bias_correction=self.use_bias_correction)
+        fin = self._finalize_args(lr, betas, beta3)
         with torch.cuda.device(self._device):
             t.update([p.grad for p in params], params, [self._offs[p] for p in params])
             if self._pairs is None or self._pairs.numel() < 2 * t.n_chunks:
@@ -628,27 +675,15 @@ class FusedProdigy(_FlatAdamW):
         the device-to-host copies of this class (not on the step path)."""
         state = {i: {k: self.state[p][k].detach().clone() for k in _PRODIGY_KEYS}
                  for i, p in self._indexed() if p in self._offs}
-        block = self._d_block.cpu()
-        prodigy = dict(zip(_D_FIELDS, block[:6].tolist()), no_progress=int(block.view(torch.int32)[12]),
-                       decouple=self.decouple, use_bias_correction=self.use_bias_correction,
-                       safeguard_warmup=self.safeguard_warmup, d0=self.d0, d_coef=self.d_coef,
-                       growth_rate=self.growth_rate)
         return {"state": state, "param_groups": self._groups_dict(), "step": int(self._scalars[3].item()),
-                "prodigy": prodigy}
+                "prodigy": self._prodigy_dict()}
 
     @torch.no_grad()
     def load_state_dict(self, state_dict):
         self._check_groups(state_dict)
-        if "prodigy" not in state_dict:
-            raise ValueError("loaded state dict has no d block (not a FusedProdigy state dict)")
-        pr = state_dict["prodigy"]
+        pr = self._prodigy_entry(state_dict)
         for p, s in self._full_state(state_dict, _PRODIGY_KEYS):
             for k in _PRODIGY_KEYS:
                 self.state[p][k].copy_(s[k])
         self._restore_options(state_dict)
-        self.decouple, self.use_bias_correction = bool(pr["decouple"]), bool(pr["use_bias_correction"])
-        self.safeguard_warmup = bool(pr["safeguard_warmup"])
-        self.d0, self.d_coef, self.growth_rate = float(pr["d0"]), float(pr["d_coef"]), float(pr["growth_rate"])
-        block = torch.tensor([float(pr[k]) for k in _D_FIELDS] + [0.0], dtype=torch.float64)
-        block.view(torch.int32)[12] = int(pr["no_progress"])
-        self._d_block.copy_(block.to(self._device))
+        self._load_prodigy_dict(pr)
