@@ -61,7 +61,9 @@ void vp_struct_sizes(int64_t* out);
  *   (DF/models/branch_cogvideox.py:415-421) and proj_out (cogvideox_transformer_3d.py:624).
  * A: bf16 [M, K] (row stride lda); W: up to 3 weight segments, each bf16 [n_seg, K] (nn.Linear layout), columns
  * [s*n_seg, (s+1)*n_seg) of C come from segment s (fused QKV without packing the weights).  K % 8 == 0
- * (a K tail is zero-filled on the device).
+ * (a K tail is zero-filled on the device), N % 8 == 0 and n_seg % 8 == 0 (VP_ERR_ARG otherwise, from vp_gemm_bf16 and
+ * vp_gemm_bf16_ws alike: two segments of n_seg % 8 == 4 have N % 8 == 0, but an 8-row weight block and an 8-column
+ * output chunk would straddle the segment boundary).
  * Output row remap: C row of GEMM row m = (m / rows_per_group) * group_stride + row_offset + (m % rows_per_group).
  * ------------------------------------------------------------------------------------------------------------- */
 enum {
@@ -155,8 +157,9 @@ int vp_gemm_variant_built(int variant);
  * projections at M = 2 x 226 token rows; reference callers: transformers T5EncoderModel, anyl.py:216-256): the K
  * range is cut into chunks of >= 512, each (tile, chunk) workgroup writes its fp32 partial tile to `workspace`, and a
  * reduce pass sums the chunks in a fixed order (deterministic) and applies the epilogue (VP_EPI_BIAS, _GELU, _SCALE,
- * _BIAS_ADDROWS; others never split).  vp_gemm_bf16_workspace_bytes: bytes this descriptor needs (0: no split, and
- * vp_gemm_bf16_ws then runs vp_gemm_bf16).  vp_gemm_bf16 never splits. */
+ * _GATED, _BIAS_ADDROWS, _GELU_BWD; VP_EPI_BIAS_QKNORM_ROPE and a_tail_k > 0 never split).
+ * vp_gemm_bf16_workspace_bytes: bytes this descriptor needs (0: no split, and vp_gemm_bf16_ws then runs
+ * vp_gemm_bf16).  vp_gemm_bf16 never splits. */
 int64_t vp_gemm_bf16_workspace_bytes(const vp_gemm_desc* d);
 int vp_gemm_bf16_ws(const vp_gemm_desc* d, void* workspace, int64_t workspace_bytes, void* stream);
 

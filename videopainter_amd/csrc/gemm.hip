@@ -433,7 +433,7 @@ VP_DEV void epi_rows_out(const vp_gemm_desc& d, const MxExt& mx, const char* sme
       }
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        float o = rbf(bf2f(rv[e]) + rbf(bf2f(gv[e]) * bf2f(v[e])));
+        float o = rbf(bf2f(rv[e]) + rbf_prod(bf2f(gv[e]) * bf2f(v[e])));
         if (inj) o = rbf(o + bf2f(iv[e]));
         v[e] = f2bf(o);
       }
@@ -518,7 +518,7 @@ VP_DEV void epi_rows_gated(const vp_gemm_desc& d, const char* smem, int m0, int 
     const bool inj = (injbits >> it) & 1u;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      float o = rbf(bf2f(rv[e]) + rbf(bf2f(gv[e]) * bf2f(v[e])));
+      float o = rbf(bf2f(rv[e]) + rbf_prod(bf2f(gv[e]) * bf2f(v[e])));
       if (inj) o = rbf(o + bf2f(iv[it][e]));
       v[e] = f2bf(o);
     }
@@ -1150,7 +1150,7 @@ VP_DEV void splitk_epilogue(const vp_gemm_desc& d, int m, int n, const float (&a
     else if (d.epilogue == VP_EPI_BIAS_ADDROWS) v = bf2f(f2bf(v)) + bf2f(pv[e]);
     else if (d.epilogue == VP_EPI_GELU_BWD) v = rbf(v * gelu_grad(bf2f(pv[e])));
     else if (d.epilogue == VP_EPI_GATED) {
-      v = rbf(bf2f(pv[e]) + rbf(bf2f(gv[e]) * v));
+      v = rbf(bf2f(pv[e]) + rbf_prod(bf2f(gv[e]) * v));
       if (inj) v = rbf(v + bf2f(iv[e]));
     }
     o[e] = f2bf(v);
@@ -1278,7 +1278,9 @@ static int gemm_bf16_launch(const vp_gemm_desc* d, void* stream, int main_tiles)
   if (d->lda < d->K || d->ldc < d->N || (d->lda % 8) != 0 || (d->ldc % 8) != 0) return VP_ERR_ARG;
   if (d->rows_per_group <= 0) return VP_ERR_ARG;
   const int nsegs = d->W[2] ? 3 : (d->W[1] ? 2 : 1);
-  if (d->n_seg <= 0 || d->n_seg * nsegs != d->N) return VP_ERR_ARG;
+  // n_seg % 8: an 8-row weight block of the DMA, the 4 columns of a bias load and the 8 columns of a reduce thread
+  // each lie in one segment (two segments of n_seg % 8 == 4 would pass N % 8 == 0)
+  if (d->n_seg <= 0 || d->n_seg * nsegs != d->N || (d->n_seg % 8) != 0) return VP_ERR_ARG;
   if (d->epilogue < VP_EPI_BIAS || d->epilogue > VP_EPI_GELU_BWD || d->epilogue == VP_EPI_BIAS_GELU_MXFP8)
     return VP_ERR_ARG;
   if (check_aux(d) != VP_OK) return VP_ERR_ARG;
@@ -1419,7 +1421,7 @@ extern "C" int vp_gemm_bf16_ws(const vp_gemm_desc* d, void* workspace, int64_t w
       d->lda < d->K || d->ldc < d->N || (d->lda % 8) != 0 || (d->ldc % 8) != 0 || d->rows_per_group <= 0)
     return VP_ERR_ARG;
   const int nsegs = d->W[2] ? 3 : (d->W[1] ? 2 : 1);
-  if (d->n_seg <= 0 || d->n_seg * nsegs != d->N) return VP_ERR_ARG;
+  if (d->n_seg <= 0 || d->n_seg * nsegs != d->N || (d->n_seg % 8) != 0) return VP_ERR_ARG;
   if (d->epilogue == VP_EPI_BIAS_ADDROWS && (d->addrows == nullptr || (d->addrows_ld % 8) != 0)) return VP_ERR_ARG;
   if (check_aux(d) != VP_OK) return VP_ERR_ARG;
   static bool attr_set = false;

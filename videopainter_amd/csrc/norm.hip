@@ -93,7 +93,7 @@ VP_DEV void adaln_row(bf16x8 (&xr)[NCH], int row, int lane, int Ntok, int D, int
       for (int e = 0; e < 8; ++e) {
         const float n = rbf((bf2f(xr[i][e]) - mean) * rstd * bf2f(w[e]) + bf2f(bb[e]));
         const float s1 = rbf(1.f + bf2f(sc[e]));
-        f[e] = rbf(rbf(n * s1) + bf2f(sh[e]));
+        f[e] = rbf(rbf_prod(n * s1) + bf2f(sh[e]));
       }
       if constexpr (MX) {
         uint8_t sb;
@@ -206,7 +206,7 @@ __global__ __launch_bounds__(ROW_THREADS) void final_norm_kernel(const bf16* __r
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         const float n = rbf((r.v[i][e] - mean) * rstd * bf2f(w[e]) + bf2f(bb[e]));
-        o[e] = f2bf(rbf(n * rbf(1.f + bf2f(sc[e]))) + bf2f(sh[e]));
+        o[e] = f2bf(rbf_prod(n * rbf(1.f + bf2f(sc[e]))) + bf2f(sh[e]));
       }
       *(bf16x8*)(y + (int64_t)row * D + c * 8) = o;
     }

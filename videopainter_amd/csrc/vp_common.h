@@ -28,6 +28,16 @@ VP_DEV float bf2f(bf16 x) { return (float)x; }
 VP_DEV bf16 f2bf(float x) { return (bf16)x; }
 // round-trip through bf16 (emulates the reference's bf16 storage points)
 VP_DEV float rbf(float x) { return (float)(bf16)x; }
+// The same round trip for a product of two bf16-VALUED factors that is then added to something:
+// a + rbf_prod(b * c) with b and c each a widened bf16 (bf2f or rbf).  Written with rbf, the compiler narrows that
+// multiply to bf16 and then contracts it with the add (hipcc's default -ffp-contract=fast): one v_fma_f32, and the
+// documented rounding of the product is never performed.  Seen for the GEMM's gated residual (gate x y) and the AdaLN
+// modulation (n x (1 + scale)).  It does not happen when a factor is a genuine fp32 value (a scalar coefficient, an
+// accumulator), for rbf of a sum, or for rbf feeding a product or a store: those keep their conversion and use rbf.
+// Widening through the integer bits keeps the rounding in the instruction stream.
+VP_DEV float rbf_prod(float x) {
+  return __builtin_bit_cast(float, (uint32_t)__builtin_bit_cast(uint16_t, (bf16)x) << 16);
+}
 
 VP_DEV float gelu_tanh(float x) {
   // torch F.gelu(approximate="tanh"): 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3)))
