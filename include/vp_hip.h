@@ -33,7 +33,7 @@ extern "C" {
 #define VP_ERR_UNSUPPORTED 1001
 
 /* ABI version: bump when any struct layout or signature below changes. */
-#define VP_ABI_VERSION 29
+#define VP_ABI_VERSION 30
 int vp_abi_version(void);
 /* "<sha256 of sources + flags>:<sha256 of the compiler version>" of the build (no reference counterpart) */
 const char* vp_build_digest(void);
@@ -1045,6 +1045,47 @@ int vp_zero_shard_prodigy_update(const vp_zero_range* ranges, int32_t range_begi
 int vp_zero_unpack_gated_bf16(const vp_mt_tensor* tensors, const vp_mt_chunk* chunks, int32_t n_chunks,
                               const void* flat, int64_t flat_len, const vp_optim_scalars* scalars,
                               const vp_prodigy_scalars* dstate, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Gradient accumulation in fp32 (ABI 30; csrc/optim.hip, csrc/prodigy.hip): the reference's
+ * --gradient_accumulation_steps (train/train_cogvideox_inpainting_i2v_video.py:348, :1743, :1894).  The micro-batches'
+ * bf16 gradients are folded into one fp32 accumulator over the flat state space (tensor t at elements [state_off,
+ * state_off + numel)), and the norm and the update of the step read that accumulator instead of the bf16 gradients.
+ * Same tables and rules as the training tail: 16-byte body, scalar head / tail, no float atomics, no host read. */
+/* one fold, over the tensor / chunk tables: acc[state_off + i] = (first ? g : acc[state_off + i] + g) * scale with
+ * g = (float)grad[i] — one rounding for the add, one for the product.  scale is 1 except in the last fold of a step,
+ * where it is 1 / (number of micro-batches) (the sharded optimizers: 1 / (micro-batches x world), in place of
+ * vp_zero_pack_bf16's inv_world); it must be positive and finite.  A tensor whose grad pointer is NULL gets zeros when
+ * first and is left as it is otherwise.  zero_grads: the bf16 gradient is zeroed in the same pass.  A chunk that does
+ * not fit acc_len writes nothing; padding is never written.  2 bytes read and 4 written per element when first,
+ * 6 read and 4 written otherwise, 2 more written with zero_grads.  n_chunks = 0: no launch. */
+int vp_mt_accumulate_bf16(const vp_mt_tensor* tensors, const vp_mt_chunk* chunks, int32_t n_chunks, float* acc,
+                          int64_t acc_len, int32_t first, float scale, int32_t zero_grads, void* stream);
+/* vp_mt_grad_sqnorm_bf16 with the gradient of tensor t at acc + state_off (fp32; the fp32 bit pattern is tested for
+ * inf / NaN): 4 bytes read per element.  The grad pointers of the table are not used. */
+int vp_mt_grad_sqnorm_f32(const vp_mt_tensor* tensors, const vp_mt_chunk* chunks, int32_t n_chunks, const float* acc,
+                          float* partials, int32_t* flags, void* stream);
+/* vp_mt_adamw_bf16 / vp_mt_adam_bf16 with the gradient of tensor t at acc + state_off (fp32): the same per-element
+ * device function, param = bf16(p) written directly.  16 bytes read and 14 written per element.  The accumulator is
+ * left as it is; the bf16 gradients are not touched (the last fold zeroes them); a skipped step writes nothing. */
+int vp_mt_adamw_f32(const vp_mt_tensor* tensors, const vp_mt_chunk* chunks, int32_t chunk_begin, int32_t n_chunks,
+                    const float* acc, float* master, float* exp_avg, float* exp_avg_sq,
+                    const vp_optim_scalars* scalars, double lr, double beta1, double beta2, double eps,
+                    double weight_decay, int32_t use_clip, void* stream);
+int vp_mt_adam_f32(const vp_mt_tensor* tensors, const vp_mt_chunk* chunks, int32_t chunk_begin, int32_t n_chunks,
+                   const float* acc, float* master, float* exp_avg, float* exp_avg_sq,
+                   const vp_optim_scalars* scalars, double lr, double beta1, double beta2, double eps,
+                   double weight_decay, int32_t use_clip, void* stream);
+/* vp_mt_prodigy_moments_bf16 with the gradient of tensor t at acc + state_off (fp32): 24 bytes read and 12 written
+ * per element.  A chunk takes the scalar / vector path the bf16-gradient kernel takes for the table's grad pointer
+ * (its phase only; it is not read), so the chunk's two sums are formed in the same order.  Pass 2 reads no gradient:
+ * vp_mt_prodigy_update_bf16 as it is (zero_grads = 0 after a fold that zeroed them). */
+int vp_mt_prodigy_moments_f32(const vp_mt_tensor* tensors, const vp_mt_chunk* chunks, int32_t chunk_begin,
+                              int32_t n_chunks, const float* acc, const float* master, const float* p0,
+                              float* exp_avg, float* exp_avg_sq, float* s, float* partials,
+                              const vp_optim_scalars* scalars, const vp_prodigy_scalars* dstate, double beta1,
+                              double beta2, double beta3, double weight_decay, double d0, int32_t safeguard_warmup,
+                              int32_t use_clip, void* stream);
 
 
 #ifdef __cplusplus

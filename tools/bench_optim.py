@@ -32,6 +32,11 @@ step one by one: pass 1 (vp_zero_shard_prodigy_moments) 24 B read + 12 B written
 (vp_zero_shard_prodigy_update) 12 + 6 B, the gated unpack 2 + 2 B, the record kernel, the d update over the records and
 the 16-byte all-gather.
 
+--accumulate times the gradient-accumulation kernels at the same tensors, round by round beside vp_mt_adamw_bf16's
+update pass (the yardstick of the same round): the first fold (vp_mt_accumulate_bf16, 2 B read + 4 B written per
+parameter), a later fold (6 + 4 B; 6 + 6 B with zero_grads), the fp32-gradient norm (vp_mt_grad_sqnorm_f32, 4 B) and
+the fp32-gradient AdamW update (vp_mt_adamw_f32, 16 + 14 B).
+
 Prints ms per step per round (HIP events around N back-to-back steps), and for `fused` the effective bandwidth
 30 B x n_params / t (norm pass: 2 B read; update pass: 14 B read + 14 B written per parameter) as a fraction of
 6.3 TB/s, with the per-kernel split (norm pass / update pass).  One JSON line at the end.
@@ -70,6 +75,8 @@ def main():
     ap.add_argument("--prodigy", action="store_true", help="add FusedProdigy and time its two passes")
     ap.add_argument("--sharded-prodigy", action="store_true",
                     help="add ShardedFusedProdigy at world 1 over RCCL and time the pieces of its step")
+    ap.add_argument("--accumulate", action="store_true",
+                    help="time the gradient-accumulation kernels beside vp_mt_adamw_bf16's update pass")
     args = ap.parse_args()
     from videopainter_amd import CogvideoXBranchModel, FusedAdamW, device_scope
     from videopainter_amd import kernels as K
@@ -198,6 +205,43 @@ def main():
                   f"({gbs / yard:.2f} of vp_mt_adamw_bf16's {yard:.0f} GB/s in the same rounds)")
         print(f"prodigy step: {med['prodigy']:.3f} ms against fused {med['fused']:.3f} ms (54 B against 30 B of "
               f"traffic per parameter; d = {d_steps:.3e} after the steps); finaliser {pmed['finalize'] * 1e3:.1f} us")
+    if args.accumulate:
+        # the folds and the fp32-gradient passes at the same tensors, interleaved round by round with the yardstick;
+        # gradients of its own (the zero_grads fold writes them)
+        pa = clone()
+        for p, q in zip(pa, base):
+            p.grad = q.grad.clone()
+        z = FusedAdamW(pa, **HYP, max_grad_norm=1.0)
+        z.accumulate()
+        z.step()  # (tables, accumulator, a valid scalars block)
+        zt, acc = z._tables, z.grad_accumulator
+        hyper = dict(lr=HYP["lr"], betas=HYP["betas"], eps=HYP["eps"], weight_decay=HYP["weight_decay"],
+                     use_clip=True)
+        fold = lambda **kw: K.mt_accumulate(zt.tensors, zt.chunks, zt.n_chunks, acc, **kw)  # noqa: E731
+        pieces = dict(
+            adamw_update=(28.0, lambda: K.mt_adamw(t.tensors, t.chunks, 0, t.n_chunks, fused._master, fused._exp_avg,
+                                                   fused._exp_avg_sq, fused._scalars, **hyper, zero_grads=False)),
+            first_fold=(6.0, lambda: fold(first=True)),
+            later_fold=(10.0, lambda: fold(first=False)),
+            later_fold_zero_grads=(12.0, lambda: fold(first=False, zero_grads=True)),
+            norm_f32=(4.0, lambda: K.mt_grad_sqnorm_f32(zt.tensors, zt.chunks, zt.n_chunks, acc, zt.partials,
+                                                        zt.flags)),
+            adamw_f32=(30.0, lambda: K.mt_adamw_f32(zt.tensors, zt.chunks, 0, zt.n_chunks, acc, z._master, z._exp_avg,
+                                                    z._exp_avg_sq, z._scalars, **hyper)))
+        ams = {k: [] for k in pieces}
+        for r in range(args.rounds):
+            for k, (_, fn) in pieces.items():
+                ams[k].append(timed(fn, args.iters))
+            print("accumulate round %d: " % r + "  ".join(f"{k} {ams[k][-1]:.3f} ms" for k in pieces), flush=True)
+        amed = {k: sorted(v)[len(v) // 2] for k, v in ams.items()}
+        yard = 28.0 * n_params / (amed["adamw_update"] * 1e-3) / 1e9
+        res["accumulate"] = dict(ms=ams, median_ms=amed, yardstick_mt_adamw_gb_per_s=yard)
+        for name, (nbytes, _) in list(pieces.items())[1:]:
+            gbs = nbytes * n_params / (amed[name] * 1e-3) / 1e9
+            res["accumulate"][name] = dict(bytes_per_param=nbytes, gb_per_s=gbs, fraction_of_6p3_tb_s=gbs * 1e9 / HBM,
+                                           vs_mt_adamw=gbs / yard)
+            print(f"accumulate {name}: {amed[name]:.3f} ms = {gbs:.0f} GB/s = {gbs * 1e9 / HBM:.2f} of 6.3 TB/s "
+                  f"({gbs / yard:.2f} of vp_mt_adamw_bf16's {yard:.0f} GB/s in the same rounds)")
     if sharded is not None:
         z, zt, c = sharded, sharded._tables, sharded._comm
         mine = z._flat16[z._lo:z._hi]

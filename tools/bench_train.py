@@ -2,7 +2,7 @@
 
     python tools/bench_train.py [--steps K] [--warmup W] [--height 60 --width 90]
                                 [--optimizer none|torch|fused|adam|prodigy|sharded|sharded-adam|sharded-prodigy]
-                                [--loss]
+                                [--loss] [--accumulate K]
                                 [--fp8-gemm [ffn,qkv,out]] [--rounds R]
 
 One step = the reference's training iteration (train/train_cogvideox_inpainting_i2v_video.py:1856-1892 with the
@@ -21,7 +21,10 @@ draws its own latents, and verify_replicas runs after the last step: "replicas_i
 rank 0 prints); --optimizer sharded-adam and --optimizer sharded-prodigy run videopainter_amd.ShardedFusedAdam and
 videopainter_amd.ShardedFusedProdigy (lr 1.0) on the same two paths, with the same clip.  --loss replaces the synthetic loss gradient with inpainting_v_loss(...).backward()
 (:1879-1892).  Default: neither.  Random-init weights, synthetic latents.  Prints one JSON line; optimizer_ms = HIP
-events around optimizer.step().
+events around optimizer.step().  --accumulate K runs K micro-batches per optimizer step (opt.accumulate() after the
+first K - 1, opt.step() after the last: fp32 gradient accumulation, the script's --gradient_accumulation_steps); --steps and
+--warmup then count optimizer steps, and the line adds ms_per_micro_batch and accumulate_ms (HIP events around
+accumulate()) beside ms_per_step, optimizer_ms and the peak memory.
 
 --fp8-gemm [SUBSET] (default when given: ffn,qkv,out) is the A/B of training through the frozen transformer on the
 MX-FP8 GEMMs (forward and dgrad; the attention stays bf16): the bf16 arm and the fp8 arm run INTERLEAVED in this one
@@ -133,6 +136,9 @@ def main():
                     help="interleaved A/B: bf16 against the frozen transformer on the MX-FP8 GEMMs (subset of "
                          "ffn,qkv,out; default all three)")
     ap.add_argument("--rounds", type=int, default=5, help="--fp8-gemm: interleaved rounds (at least 5)")
+    ap.add_argument("--accumulate", type=int, default=1, metavar="K",
+                    help="K micro-batches per optimizer step: opt.accumulate() after the first K - 1, opt.step() "
+                         "after the last (--steps and --warmup count optimizer steps)")
     args = ap.parse_args()
     from videopainter_amd import CogVideoXTransformer3DModel, CogvideoXBranchModel, device_scope
     from videopainter_amd import kernels as K
@@ -207,7 +213,37 @@ def main():
         from videopainter_amd import CogVideoXDPMScheduler, inpainting_v_loss
         alphas_cumprod = CogVideoXDPMScheduler().alphas_cumprod.to(dev, torch.float32)
         target = torch.randn(1, F, 16, HL, WL, generator=g).to(dev, torch.bfloat16)
-    opt_events = []
+    K_acc = args.accumulate
+    if K_acc < 1 or (K_acc > 1 and args.optimizer in ("none", "torch")):
+        raise SystemExit("--accumulate K needs K >= 1 and one of the fused / sharded optimizers")
+    opt_events, acc_events = [], []
+
+    def timed_call(fn, events):
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        ev[0].record()
+        fn()
+        ev[1].record()
+        events.append(ev)
+
+    def micro_batch(last: bool):
+        samples = br(hidden_states=lat, encoder_hidden_states=enc, branch_cond=cond, timestep=ts,
+                     image_rotary_emb=rope, return_dict=False)[0]
+        out = tr(hidden_states=hidden, encoder_hidden_states=enc, timestep=ts, image_rotary_emb=rope,
+                 branch_block_samples=samples, branch_block_masks=mask, return_dict=False)[0]
+        if args.loss:  # (unscaled: step() takes the mean over the micro-batches)
+            inpainting_v_loss(out, lat, target, ts, alphas_cumprod, mask, 1.0).backward()
+        else:
+            out.backward(dout)
+        if last:
+            timed_call(opt.step, opt_events)
+        else:
+            timed_call(opt.accumulate, acc_events)
+        for p in params:
+            p.grad = None
+
+    def accumulated_step():
+        for j in range(K_acc):
+            micro_batch(j == K_acc - 1)
 
     def step():
         samples = br(hidden_states=lat, encoder_hidden_states=enc, branch_cond=cond, timestep=ts,
@@ -232,10 +268,13 @@ def main():
         res.update(ntok=ntok, flop_per_step=flops(ntok, nv))
         print(json.dumps(res))
         return
+    if K_acc > 1:
+        step = accumulated_step
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
     opt_events.clear()
+    acc_events.clear()
     t0 = time.perf_counter()
     for i in range(args.steps):
         step()
@@ -260,6 +299,12 @@ def main():
                loss="inpainting_v_loss" if args.loss else None,
                tflops_per_s=fl["total"] / el / 1e12, flop_per_step=fl, ntok=ntok,
                peak_mem_gib=torch.cuda.max_memory_allocated() / 2 ** 30)
+    if K_acc > 1:
+        res.update(accumulate=K_acc, ms_per_micro_batch=el * 1e3 / K_acc,
+                   accumulate_ms=sum(a.elapsed_time(b) for a, b in acc_events) / len(acc_events))
+        print(f"--accumulate {K_acc}: {el * 1e3 / K_acc:.1f} ms per micro-batch, {el * 1e3:.1f} ms per optimizer step; "
+              f"accumulate() {res['accumulate_ms']:.3f} ms, step() {res['optimizer_ms']:.3f} ms; peak "
+              f"{res['peak_mem_gib']:.2f} GiB", file=sys.stderr)
     if replicas is not None:
         res["world"] = world
         res["replicas_identical"] = replicas["identical"]

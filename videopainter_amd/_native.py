@@ -11,7 +11,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VP_HIP_LIB", os.path.join(_HERE, "_lib", "libvp_hip.so"))
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 vp = C.c_void_p
 i32 = C.c_int32
@@ -250,6 +250,14 @@ _SIGS = {
                                        C.c_double, C.c_double, i32, vp, vp, vp]),
     "vp_zero_shard_prodigy_update": (i32, [vp, i32, i32, vp, vp, vp, vp, i64, vp, vp, C.c_double, C.c_double, vp]),
     "vp_zero_unpack_gated_bf16": (i32, [vp, vp, i32, vp, i64, vp, vp, vp]),
+    "vp_mt_accumulate_bf16": (i32, [vp, vp, i32, vp, i64, i32, f32, i32, vp]),
+    "vp_mt_grad_sqnorm_f32": (i32, [vp, vp, i32, vp, vp, vp, vp]),
+    "vp_mt_adamw_f32": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double,
+                              C.c_double, i32, vp]),
+    "vp_mt_adam_f32": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double,
+                             C.c_double, i32, vp]),
+    "vp_mt_prodigy_moments_f32": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_double,
+                                        C.c_double, C.c_double, C.c_double, i32, i32, vp]),
 }
 
 EXPORTS = tuple(_SIGS)

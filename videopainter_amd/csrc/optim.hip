@@ -71,6 +71,58 @@ __global__ __launch_bounds__(OT) void mt_adamw_kernel(const vp_mt_tensor* __rest
   adam_piece<L2>(g, pm, mm, vm, w, head, r.n, a, adam_coef(a, sc));
 }
 
+// ---- e. gradient accumulation: one fold of the bf16 gradients into the fp32 flat accumulator (accumulate_piece), and
+// the norm and the update with the accumulator as the gradient: tensor t's is acc + state_off, so every fp32 stream of
+// a chunk starts at the same flat offset ----
+template <bool FIRST>
+__global__ __launch_bounds__(OT) void mt_accumulate_kernel(const vp_mt_tensor* __restrict__ tensors,
+                                                           const vp_mt_chunk* __restrict__ chunks,
+                                                           float* __restrict__ acc, int64_t acc_len, float scale,
+                                                           int zero_grads) {
+  const ChunkRange r = chunk_range(tensors, chunks, blockIdx.x);
+  const int64_t o = r.t.state_off + r.start;
+  if (r.t.state_off < 0 || o + r.n > acc_len) return;  // (a table that does not fit the buffer writes nothing)
+  float* out = acc + o;
+  bf16* g = (bf16*)r.t.grad;
+  if (g == nullptr) {  // a tensor without a gradient: zeros in the first fold, as it is afterwards
+    if (FIRST) zero_piece(out, ((uintptr_t)out & 15) ? r.n : 0, r.n);
+    return;
+  }
+  g += r.start;
+  int head = head_of(g, r.n);
+  if ((uintptr_t)(out + head) & 15) head = r.n;
+  accumulate_piece<FIRST>(g, out, head, r.n, scale, zero_grads);
+}
+
+__global__ __launch_bounds__(OT) void mt_sqnorm_f32_kernel(const vp_mt_tensor* __restrict__ tensors,
+                                                           const vp_mt_chunk* __restrict__ chunks,
+                                                           const float* __restrict__ acc,
+                                                           float* __restrict__ partials, int* __restrict__ flags) {
+  const ChunkRange r = chunk_range(tensors, chunks, blockIdx.x);
+  const float* g = acc + r.t.state_off + r.start;
+  sqnorm_piece(g, ((uintptr_t)g & 15) ? r.n : 0, r.n, partials, flags);
+}
+
+template <bool L2>
+__global__ __launch_bounds__(OT) void mt_adamw_f32_kernel(const vp_mt_tensor* __restrict__ tensors,
+                                                          const vp_mt_chunk* __restrict__ chunks, int chunk_begin,
+                                                          const float* __restrict__ acc, float* __restrict__ master,
+                                                          float* __restrict__ exp_avg, float* __restrict__ exp_avg_sq,
+                                                          const vp_optim_scalars* __restrict__ sc, const AdamArgs a) {
+  if (sc->skipped) return;  // a skipped step writes no state and no parameter (the last fold zeroed the gradients)
+  const ChunkRange r = chunk_range(tensors, chunks, chunk_begin + blockIdx.x);
+  bf16* w = (bf16*)r.t.param + r.start;
+  const int64_t so = r.t.state_off + r.start;
+  const float* g = acc + so;
+  float* pm = master + so;
+  float* mm = exp_avg + so;
+  float* vm = exp_avg_sq + so;
+  int head = head_of(w, r.n);
+  if (((uintptr_t)(g + head) | (uintptr_t)(pm + head) | (uintptr_t)(mm + head) | (uintptr_t)(vm + head)) & 15)
+    head = r.n;
+  adam_piece<L2>(g, pm, mm, vm, w, head, r.n, a, adam_coef(a, sc));
+}
+
 // ---- y = bf16(x * *s) ----
 __global__ __launch_bounds__(OT) void scale_dev_kernel(const bf16* __restrict__ x, bf16* __restrict__ y, int64_t n,
                                                        const float* __restrict__ s) {
@@ -236,6 +288,65 @@ extern "C" int vp_mt_adam_bf16(const vp_mt_tensor* tensors, const vp_mt_chunk* c
                                double weight_decay, int32_t use_clip, int32_t zero_grads, void* stream) {
   return mt_adam_launch<true>(tensors, chunks, chunk_begin, n_chunks, master, exp_avg, exp_avg_sq, scalars, lr, beta1,
                               beta2, eps, weight_decay, use_clip, zero_grads, stream);
+}
+
+extern "C" int vp_mt_accumulate_bf16(const vp_mt_tensor* tensors, const vp_mt_chunk* chunks, int32_t n_chunks,
+                                    float* acc, int64_t acc_len, int32_t first, float scale, int32_t zero_grads,
+                                    void* stream) {
+  if (n_chunks < 0 || acc_len < 0 || !(scale > 0.f && scale <= 3.402823466e38f)) return VP_ERR_ARG;
+  if (n_chunks == 0) return VP_OK;
+  if (!tensors || !chunks || !acc) return VP_ERR_ARG;
+  if (first)
+    hipLaunchKernelGGL(mt_accumulate_kernel<true>, dim3(n_chunks), dim3(OT), 0, (hipStream_t)stream, tensors, chunks,
+                       acc, acc_len, scale, zero_grads);
+  else
+    hipLaunchKernelGGL(mt_accumulate_kernel<false>, dim3(n_chunks), dim3(OT), 0, (hipStream_t)stream, tensors, chunks,
+                       acc, acc_len, scale, zero_grads);
+  VP_CHECK_LAUNCH();
+  return VP_OK;
+}
+
+extern "C" int vp_mt_grad_sqnorm_f32(const vp_mt_tensor* tensors, const vp_mt_chunk* chunks, int32_t n_chunks,
+                                     const float* acc, float* partials, int32_t* flags, void* stream) {
+  if (n_chunks < 0) return VP_ERR_ARG;
+  if (n_chunks == 0) return VP_OK;
+  if (!tensors || !chunks || !acc || !partials || !flags) return VP_ERR_ARG;
+  hipLaunchKernelGGL(mt_sqnorm_f32_kernel, dim3(n_chunks), dim3(OT), 0, (hipStream_t)stream, tensors, chunks, acc,
+                     partials, flags);
+  VP_CHECK_LAUNCH();
+  return VP_OK;
+}
+
+template <bool L2>
+static int mt_adam_f32_launch(const vp_mt_tensor* tensors, const vp_mt_chunk* chunks, int32_t chunk_begin,
+                              int32_t n_chunks, const float* acc, float* master, float* exp_avg, float* exp_avg_sq,
+                              const vp_optim_scalars* scalars, double lr, double beta1, double beta2, double eps,
+                              double weight_decay, int32_t use_clip, void* stream) {
+  if (n_chunks < 0 || chunk_begin < 0 || !scalars || !acc || !master || !exp_avg || !exp_avg_sq) return VP_ERR_ARG;
+  if (!adam_hyper_ok(lr, beta1, beta2, eps, weight_decay)) return VP_ERR_ARG;
+  if (n_chunks == 0) return VP_OK;
+  if (!tensors || !chunks) return VP_ERR_ARG;
+  const AdamArgs a = adam_args(lr, beta1, beta2, eps, weight_decay, use_clip, 0);
+  hipLaunchKernelGGL(mt_adamw_f32_kernel<L2>, dim3(n_chunks), dim3(OT), 0, (hipStream_t)stream, tensors, chunks,
+                     chunk_begin, acc, master, exp_avg, exp_avg_sq, scalars, a);
+  VP_CHECK_LAUNCH();
+  return VP_OK;
+}
+
+extern "C" int vp_mt_adamw_f32(const vp_mt_tensor* tensors, const vp_mt_chunk* chunks, int32_t chunk_begin,
+                               int32_t n_chunks, const float* acc, float* master, float* exp_avg, float* exp_avg_sq,
+                               const vp_optim_scalars* scalars, double lr, double beta1, double beta2, double eps,
+                               double weight_decay, int32_t use_clip, void* stream) {
+  return mt_adam_f32_launch<false>(tensors, chunks, chunk_begin, n_chunks, acc, master, exp_avg, exp_avg_sq, scalars,
+                                   lr, beta1, beta2, eps, weight_decay, use_clip, stream);
+}
+
+extern "C" int vp_mt_adam_f32(const vp_mt_tensor* tensors, const vp_mt_chunk* chunks, int32_t chunk_begin,
+                              int32_t n_chunks, const float* acc, float* master, float* exp_avg, float* exp_avg_sq,
+                              const vp_optim_scalars* scalars, double lr, double beta1, double beta2, double eps,
+                              double weight_decay, int32_t use_clip, void* stream) {
+  return mt_adam_f32_launch<true>(tensors, chunks, chunk_begin, n_chunks, acc, master, exp_avg, exp_avg_sq, scalars,
+                                  lr, beta1, beta2, eps, weight_decay, use_clip, stream);
 }
 
 extern "C" int vp_scale_dev_bf16(const void* x, void* y, int64_t n, const float* s, void* stream) {

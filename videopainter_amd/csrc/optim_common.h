@@ -1,7 +1,8 @@
 // What the optimizer kernels of csrc/optim.hip (one GPU) and csrc/zero.hip (data-parallel, sharded state) share —
 // everything but the decoding of their tables and the choice of each piece's scalar head: the workgroup shape and its
 // fixed-order sum, stream_piece (scalar head / 16-byte body / scalar tail of one piece), the zero fill, the gradient
-// norm's first stage (sqnorm_piece) and finaliser, the AdamW update of one piece (adam_piece), the two passes of
+// norm's first stage (sqnorm_piece) and finaliser, one fold of a gradient accumulation (accumulate_piece), the AdamW
+// update of one piece (adam_piece), the two passes of
 // Prodigy over one piece (prodigy_moments_piece, prodigy_update_piece), Prodigy's one-workgroup finaliser (the strided
 // double sum, dlr, the d update: over the chunks' pairs in csrc/prodigy.hip, over the ranks' records in csrc/zero.hip)
 // and the host-side argument checks.  Both AdamW kernels are adam_piece around the SAME adam_element(), and every
@@ -133,6 +134,37 @@ VP_DEV void sqnorm_piece(const T* __restrict__ g, int head, int n, float* __rest
     partials[blockIdx.x] = s;
     flags[blockIdx.x] = bad_any;
   }
+}
+
+// ---- one fold of a gradient accumulation over one piece: acc[i] = (FIRST ? g : acc[i] + g) * scale with
+// g = float(grad[i]) — one rounding for the add, one for the product; the bf16 gradient zeroed in the same pass when
+// asked to (acc + head and g + head on a 16-byte boundary, or head == n) ----
+template <bool FIRST>
+VP_DEV void accumulate_piece(bf16* __restrict__ g, float* __restrict__ acc, int head, int n, float scale,
+                             int zero_grads) {
+#pragma clang fp contract(off)
+  const bf16 zero = f2bf(0.f);
+  stream_piece<8>(
+      head, n,
+      [&](int i) {
+        const float x = bf2f(g[i]);
+        acc[i] = (FIRST ? x : acc[i] + x) * scale;
+        if (zero_grads) g[i] = zero;
+      },
+      [&](int o) {
+        float x[8];
+        load8(g + o, x);
+        if constexpr (!FIRST) {
+          float a[8];
+          load8(acc + o, a);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) x[e] = a[e] + x[e];
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) x[e] *= scale;
+        store8(acc + o, x);
+        if (zero_grads) *(bf16x8*)(g + o) = bf16x8{};
+      });
 }
 
 // ---- AdamW with fp32 master weights: the per-element update ----

@@ -55,6 +55,33 @@ __global__ __launch_bounds__(OT) void mt_prodigy_moments_kernel(
                         prodigy_moment_coef(a, sc, ds));
 }
 
+// ---- pass 1 on an accumulated gradient: the fp32 accumulator is the gradient, tensor t's at acc + state_off ----
+__global__ __launch_bounds__(OT) void mt_prodigy_moments_f32_kernel(
+    const vp_mt_tensor* __restrict__ tensors, const vp_mt_chunk* __restrict__ chunks, int chunk_begin,
+    const float* __restrict__ acc, const float* __restrict__ master, const float* __restrict__ p0,
+    float* __restrict__ exp_avg, float* __restrict__ exp_avg_sq, float* __restrict__ s, float* __restrict__ partials,
+    const vp_optim_scalars* __restrict__ sc, const vp_prodigy_scalars* __restrict__ ds, const ProdigyMomentArgs a) {
+  if (sc->skipped) return;
+  const int c = chunk_begin + blockIdx.x;
+  const ChunkRange r = chunk_range(tensors, chunks, c);
+  const int64_t so = r.t.state_off + r.start;
+  const float* g = acc + so;
+  const float* pm = master + so;
+  const float* p0m = p0 + so;
+  float* mm = exp_avg + so;
+  float* vm = exp_avg_sq + so;
+  float* sm = s + so;
+  // the head is the one the bf16-gradient kernel picks from the phase of the last folded gradient (the pointer is not
+  // dereferenced): an element's path decides the order of the chunk's two sums, so a step on an accumulated gradient
+  // sums as a step on that gradient itself would
+  int head = head_of((const bf16*)r.t.grad + r.start, r.n);
+  if (((uintptr_t)(g + head) | (uintptr_t)(pm + head) | (uintptr_t)(p0m + head) | (uintptr_t)(mm + head) |
+       (uintptr_t)(vm + head) | (uintptr_t)(sm + head)) & 15)
+    head = r.n;
+  prodigy_moments_piece(g, pm, p0m, mm, vm, sm, head, r.n, partials + 2 * (int64_t)c, a,
+                        prodigy_moment_coef(a, sc, ds));
+}
+
 // ---- pass 2 ----
 __global__ __launch_bounds__(OT) void mt_prodigy_update_kernel(
     const vp_mt_tensor* __restrict__ tensors, const vp_mt_chunk* __restrict__ chunks, int chunk_begin,
@@ -109,6 +136,26 @@ extern "C" int vp_mt_prodigy_moments_bf16(const vp_mt_tensor* tensors, const vp_
   const ProdigyMomentArgs a = prodigy_moment_args(beta1, beta2, beta3, weight_decay, d0, safeguard_warmup, use_clip);
   hipLaunchKernelGGL(mt_prodigy_moments_kernel, dim3(n_chunks), dim3(OT), 0, (hipStream_t)stream, tensors, chunks,
                      chunk_begin, master, p0, exp_avg, exp_avg_sq, s, partials, scalars, dstate, a);
+  VP_CHECK_LAUNCH();
+  return VP_OK;
+}
+
+extern "C" int vp_mt_prodigy_moments_f32(const vp_mt_tensor* tensors, const vp_mt_chunk* chunks, int32_t chunk_begin,
+                                         int32_t n_chunks, const float* acc, const float* master, const float* p0,
+                                         float* exp_avg, float* exp_avg_sq, float* s, float* partials,
+                                         const vp_optim_scalars* scalars, const vp_prodigy_scalars* dstate,
+                                         double beta1, double beta2, double beta3, double weight_decay, double d0,
+                                         int32_t safeguard_warmup, int32_t use_clip, void* stream) {
+  if (n_chunks < 0 || chunk_begin < 0 || !scalars || !dstate || !acc || !master || !p0 || !exp_avg || !exp_avg_sq ||
+      !s)
+    return VP_ERR_ARG;
+  if (!prodigy_hyper_ok(beta1, beta2, beta3, d0) || !finite_nonneg(d0) || !finite_nonneg(weight_decay))
+    return VP_ERR_ARG;
+  if (n_chunks == 0) return VP_OK;
+  if (!tensors || !chunks || !partials) return VP_ERR_ARG;
+  const ProdigyMomentArgs a = prodigy_moment_args(beta1, beta2, beta3, weight_decay, d0, safeguard_warmup, use_clip);
+  hipLaunchKernelGGL(mt_prodigy_moments_f32_kernel, dim3(n_chunks), dim3(OT), 0, (hipStream_t)stream, tensors, chunks,
+                     chunk_begin, acc, master, p0, exp_avg, exp_avg_sq, s, partials, scalars, dstate, a);
   VP_CHECK_LAUNCH();
   return VP_OK;
 }

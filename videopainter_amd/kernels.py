@@ -1786,6 +1786,87 @@ def mt_prodigy_update(tensors: torch.Tensor, chunks: torch.Tensor, chunk_begin: 
                                               int(zero_grads), _stream()), "vp_mt_prodigy_update_bf16")
 
 
+# gradient accumulation: the fold into the fp32 flat accumulator and the norm / update passes that read it
+
+def _chk_flat_f32(who: str, acc: torch.Tensor, **state: torch.Tensor) -> None:
+    """The accumulator and the flat state buffers that go with it: dtype, shape and length of every one before the
+    device of any, so that each failure can be told apart (and tested without a GPU)."""
+    for name, t in dict(acc=acc, **state).items():
+        if t.dtype != torch.float32:
+            raise TypeError(f"{who}: {name} must be torch.float32, got {t.dtype}")
+        if t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous 1-D tensor")
+        if t.numel() != acc.numel():
+            raise ValueError(f"{who}: {name} must have the accumulator's length {acc.numel()}, got {t.numel()}")
+    for name, t in dict(acc=acc, **state).items():
+        _chk(t, name, torch.float32)
+
+
+def mt_accumulate(tensors: torch.Tensor, chunks: torch.Tensor, n_chunks: int, acc: torch.Tensor, *, first: bool,
+                  scale: float = 1.0, zero_grads: bool = False) -> None:
+    """acc[state_off + i] = (first ? g : acc[state_off + i] + g) * scale with g = float(grad[i]) over the tables (a
+    NULL gradient pointer: zeros when `first`, untouched otherwise)."""
+    scale = float(scale)
+    if not 0.0 < scale < float("inf"):
+        raise ValueError("mt_accumulate: scale must be positive and finite")
+    _chk_flat_f32("mt_accumulate", acc)
+    N.check(N.lib().vp_mt_accumulate_bf16(_p(tensors), _p(chunks), n_chunks, _p(acc), acc.numel(), int(first), scale,
+                                          int(zero_grads), _stream()), "vp_mt_accumulate_bf16")
+
+
+def mt_grad_sqnorm_f32(tensors: torch.Tensor, chunks: torch.Tensor, n_chunks: int, acc: torch.Tensor,
+                       partials: torch.Tensor, flags: torch.Tensor) -> None:
+    """mt_grad_sqnorm over the accumulated gradient: tensor t's is acc[state_off : state_off + numel]."""
+    _chk_flat_f32("mt_grad_sqnorm_f32", acc)
+    _chk_slots(partials, flags, n_chunks, "mt_grad_sqnorm_f32", "n_chunks")
+    N.check(N.lib().vp_mt_grad_sqnorm_f32(_p(tensors), _p(chunks), n_chunks, _p(acc), _p(partials), _p(flags),
+                                          _stream()), "vp_mt_grad_sqnorm_f32")
+
+
+def _mt_adam_f32(entry: str, who: str, tensors, chunks, chunk_begin, n_chunks, acc, master, exp_avg, exp_avg_sq,
+                 scalars, lr, betas, eps, weight_decay, use_clip) -> None:
+    _chk_flat_f32(who, acc, master=master, exp_avg=exp_avg, exp_avg_sq=exp_avg_sq)
+    _chk_scalars(scalars, who)
+    N.check(getattr(N.lib(), entry)(_p(tensors), _p(chunks), chunk_begin, n_chunks, _p(acc), _p(master), _p(exp_avg),
+                                    _p(exp_avg_sq), _p(scalars), lr, betas[0], betas[1], eps, weight_decay,
+                                    int(use_clip), _stream()), entry)
+
+
+def mt_adamw_f32(tensors: torch.Tensor, chunks: torch.Tensor, chunk_begin: int, n_chunks: int, acc: torch.Tensor,
+                 master: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, scalars: torch.Tensor, *,
+                 lr: float, betas, eps: float, weight_decay: float, use_clip: bool) -> None:
+    """mt_adamw on the accumulated gradient (the bf16 gradients are not touched: the last fold zeroes them)."""
+    _mt_adam_f32("vp_mt_adamw_f32", "mt_adamw_f32", tensors, chunks, chunk_begin, n_chunks, acc, master, exp_avg,
+                 exp_avg_sq, scalars, lr, betas, eps, weight_decay, use_clip)
+
+
+def mt_adam_f32(tensors: torch.Tensor, chunks: torch.Tensor, chunk_begin: int, n_chunks: int, acc: torch.Tensor,
+                master: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, scalars: torch.Tensor, *,
+                lr: float, betas, eps: float, weight_decay: float, use_clip: bool) -> None:
+    """mt_adam on the accumulated gradient."""
+    _mt_adam_f32("vp_mt_adam_f32", "mt_adam_f32", tensors, chunks, chunk_begin, n_chunks, acc, master, exp_avg,
+                 exp_avg_sq, scalars, lr, betas, eps, weight_decay, use_clip)
+
+
+def mt_prodigy_moments_f32(tensors: torch.Tensor, chunks: torch.Tensor, chunk_begin: int, n_chunks: int,
+                           acc: torch.Tensor, master: torch.Tensor, p0: torch.Tensor, exp_avg: torch.Tensor,
+                           exp_avg_sq: torch.Tensor, s: torch.Tensor, partials: torch.Tensor, scalars: torch.Tensor,
+                           dstate: torch.Tensor, *, betas, beta3: float, weight_decay: float, d0: float,
+                           safeguard_warmup: bool, use_clip: bool) -> None:
+    """mt_prodigy_moments on the accumulated gradient."""
+    _chk_flat_f32("mt_prodigy_moments_f32", acc, master=master, p0=p0, exp_avg=exp_avg, exp_avg_sq=exp_avg_sq, s=s)
+    _chk_scalars(scalars, "mt_prodigy_moments_f32")
+    _chk_dstate(dstate, "mt_prodigy_moments_f32")
+    if chunk_begin < 0:
+        raise ValueError("mt_prodigy_moments_f32: negative chunk_begin")
+    _chk_pairs(partials, chunk_begin + n_chunks, "mt_prodigy_moments_f32")
+    N.check(N.lib().vp_mt_prodigy_moments_f32(_p(tensors), _p(chunks), chunk_begin, n_chunks, _p(acc), _p(master),
+                                              _p(p0), _p(exp_avg), _p(exp_avg_sq), _p(s), _p(partials), _p(scalars),
+                                              _p(dstate), betas[0], betas[1], beta3, weight_decay, d0,
+                                              int(safeguard_warmup), int(use_clip), _stream()),
+            "vp_mt_prodigy_moments_f32")
+
+
 # sharded training tail (csrc/zero.hip; videopainter_amd/zero.py builds the tables and runs the collectives between)
 
 def _flat1(t: torch.Tensor, name: str, dtype) -> None:

@@ -15,13 +15,20 @@ back every step.
     clip_grad_norm_(parameters, max_norm)        norm + in-place scale (accelerator.clip_grad_norm_'s job, :1897)
     get_gradient_norm(parameters)                norm only (the script's helper, :80-90, without its host loop)
 
+Gradient accumulation (the script's --gradient_accumulation_steps, :348 / :1743 / :1894): every optimizer here and in
+zero.py has `accumulate()`, which folds the current bf16 gradients into an fp32 flat accumulator, and a `step()` that,
+with folds pending, folds the last micro-batch scaled to the mean and runs norm, clip and update on the accumulator
+(vp_mt_accumulate_bf16 and the fp32-gradient forms of the norm and update kernels).  The mean is what accelerate's
+loss / k gives, so micro-batch losses are passed unscaled.  Adding micro-batches into the bf16 `.grad` instead would
+lose exactly what the fp32 masters keep.
+
 Nothing here copies device memory to the host or synchronises: the norm, the clip coefficient, the non-finite flag,
 the step counter and the bias corrections live in a small device block the kernels read, and so does Prodigy's d.
 
 The data-parallel optimizers (zero.ShardedFusedAdamW, ShardedFusedAdam, ShardedFusedProdigy) are built on the same
 parts: `_FlatAdamW` (validation, the flat layout of `flat_offsets`, the scalars block, the state-dict checks, the step
-prologue), `_ProdigyCore` (Prodigy's options, its d block and state-dict entry) and `DeviceTables` (the table uploader
-over `pack_tables`).
+prologue, the gradient accumulation), `_ProdigyCore` (Prodigy's options, its d block and state-dict entry) and
+`DeviceTables` (the table uploader over `pack_tables`).
 """
 from __future__ import annotations
 
@@ -229,8 +236,10 @@ _STATE_KEYS = ("master", "exp_avg", "exp_avg_sq")
 class _FlatAdamW(torch.optim.Optimizer):
     """What `FusedAdamW` and `zero.ShardedFusedAdamW` share: the validation of hyper-parameters and parameters, the
     trainable parameters laid out in one flat element space (`flat_offsets`), the int32[8] device scalars block
-    (N.OptimScalars) with its read-only views, the checks of a loaded state dict and the prologue of `step()`.  A
-    subclass owns the state buffers, the step itself and its checkpoint formats."""
+    (N.OptimScalars) with its read-only views, the checks of a loaded state dict, the prologue of `step()` and the
+    gradient accumulation (`accumulate()`, `pending`, `reset_accumulation()`; a subclass names the tables and the
+    accumulator in `_fold_target` and calls `_last_fold` from a step with folds pending).  A subclass owns the state
+    buffers, the step itself and its checkpoint formats."""
 
     def __init__(self, params, lr, betas, eps, weight_decay, max_grad_norm, skip_nonfinite, zero_grads):
         """Validates everything and lays out the flat space; allocates nothing (`_alloc_scalars` is the subclass's
@@ -272,6 +281,9 @@ class _FlatAdamW(torch.optim.Optimizer):
         self._device = self._params[0].device
         offs, self.total = flat_offsets([p.numel() for p in self._params])
         self._offs = dict(zip(self._params, offs))
+        self._pending = 0         # micro-batches folded into the accumulator since the last step
+        self._acc_active = None   # which trainable parameters had a gradient in the first fold of this step
+        self._acc = None          # fp32 [total]: the single-GPU accumulator, allocated by the first accumulate()
 
     def _alloc_scalars(self) -> None:
         self._scalars = torch.zeros(8, device=self._device, dtype=torch.int32)  # N.OptimScalars
@@ -309,6 +321,74 @@ class _FlatAdamW(torch.optim.Optimizer):
         if p not in self._offs:
             raise KeyError("not a trainable parameter of this optimizer")
         return self._offs[p]
+
+    # ---- gradient accumulation ----
+    @property
+    def pending(self) -> int:
+        """The number of micro-batches `accumulate()` has folded since the last step (a host int)."""
+        return self._pending
+
+    @property
+    def grad_accumulator(self) -> Optional[torch.Tensor]:
+        """The fp32 flat accumulator (the element space of `flat_offset`; read-only for callers).  None until the
+        first `accumulate()`: an optimizer that never accumulates allocates nothing."""
+        return self._acc
+
+    def reset_accumulation(self) -> None:
+        """Drops the pending folds: the next `accumulate()` or `step()` starts from the gradients alone."""
+        self._pending, self._acc_active = 0, None
+
+    @torch.no_grad()
+    def accumulate(self) -> None:
+        """Folds the current bf16 `.grad` of every parameter that has one into the fp32 accumulator as one more
+        micro-batch — the first fold after a step overwrites, later ones add — and zeroes the gradients in the same
+        pass under `zero_grads` (gradients set to None between micro-batches work as well).  One launch: no host
+        read, no synchronisation, no collective.  The loop of k micro-batches is
+
+            for i in range(k): backward(); opt.accumulate() if i < k - 1 else opt.step()
+
+        and `step()` applies the 1 / k: it runs on the fp32 MEAN of the micro-batch gradients, which is what
+        accelerate's loss / k gives, so the micro-batch losses are passed UNSCALED.  The set of parameters with a
+        gradient must be the same in every micro-batch of one step (ValueError otherwise)."""
+        from . import kernels as K
+        self._begin_step(None)
+        with torch.cuda.device(self._device):
+            self._fold(K, 1.0)
+
+    def _fold(self, K, scale: float):
+        """One fold of the current gradients with `scale` (1, or the step's 1 / count in the last one); returns the
+        tables it ran over."""
+        active = tuple(p.grad is not None for p in self._params)
+        if self._pending and active != self._acc_active:
+            raise ValueError(f"{type(self).__name__}: the set of parameters with a gradient changed between the "
+                             f"micro-batches of one step")
+        t, acc = self._fold_target()
+        K.mt_accumulate(t.tensors, t.chunks, t.n_chunks, acc, first=self._pending == 0, scale=scale,
+                        zero_grads=self.zero_grads)
+        self._acc_active = active
+        self._pending += 1
+        return t
+
+    def _fold_target(self):
+        """(the tables of the current gradients, the accumulator) — the single-GPU form: the active tensors' tables
+        and an fp32 [total] buffer of this optimizer's own."""
+        params = [p for g in self.param_groups for p in g["params"] if p.grad is not None]
+        self._tables.update([p.grad for p in params], params, [self._offs[p] for p in params])
+        if self._acc is None:
+            self._acc = torch.zeros(max(self.total, 1), device=self._device, dtype=torch.float32)
+        return self._tables, self._acc
+
+    def _last_fold(self, K, ranks: int = 1):
+        """step() with pending folds: the current gradients as the last micro-batch, scaled to the mean (over the
+        micro-batches and, for a sharded step, the `ranks` whose folds the reduce-scatter then sums)."""
+        t = self._fold(K, 1.0 / ((self._pending + 1) * ranks))
+        self.reset_accumulation()
+        return t
+
+    def _no_pending(self, what: str) -> None:
+        if self._pending:
+            raise RuntimeError(f"{type(self).__name__}.{what}() with {self._pending} accumulated micro-batch(es) "
+                               f"pending: step() or reset_accumulation() first")
 
     def _begin_step(self, closure):
         """The prologue of step(): (the closure's loss, the betas every group shares), after checking every gradient
@@ -394,6 +474,10 @@ class FusedAdamW(_FlatAdamW):
                       step counter, and `last_step_skipped` is 1.
       zero_grads      zero the gradients (in place, same storage) in the update pass — also in a skipped step.
 
+    `accumulate()` / `pending` / `reset_accumulation()` / `grad_accumulator` (`_FlatAdamW`): fp32 gradient
+    accumulation over micro-batches — `for i in range(k): backward(); opt.accumulate() if i < k - 1 else opt.step()`
+    with UNSCALED micro-batch losses; the step runs on the fp32 mean.  State dicts are refused while folds are pending.
+
     Differences from torch's: one step counter for the whole optimizer (a parameter whose grad was None in some
     step shares the others' bias correction); betas must be the same in every parameter group (lr, weight_decay and
     eps may differ); parameters must be bf16, contiguous, on one device; amsgrad / maximize / foreach / capturable do
@@ -425,30 +509,41 @@ class FusedAdamW(_FlatAdamW):
         params = [p for g in self.param_groups for p in g["params"] if p.grad is not None]
         t = self._tables
         with torch.cuda.device(self._device):
-            t.update([p.grad for p in params], params, [self._offs[p] for p in params])
-            K.mt_grad_sqnorm(t.tensors, t.chunks, t.n_chunks, t.partials, t.flags)
+            accumulated = self._pending > 0
+            if accumulated:  # the gradient of the step is the accumulator: the fp32 mean of the micro-batches
+                self._last_fold(K)
+                K.mt_grad_sqnorm_f32(t.tensors, t.chunks, t.n_chunks, self._acc, t.partials, t.flags)
+            else:
+                t.update([p.grad for p in params], params, [self._offs[p] for p in params])
+                K.mt_grad_sqnorm(t.tensors, t.chunks, t.n_chunks, t.partials, t.flags)
             K.optim_finalize(t.partials, t.flags, t.n_chunks, self._scalars, max_norm=self.max_grad_norm or 0.0,
                              betas=betas, skip_nonfinite=self.skip_nonfinite, advance_step=True)
-            first, update = 0, getattr(K, self._UPDATE)
+            first, update = 0, getattr(K, self._UPDATE + "_f32" if accumulated else self._UPDATE)
             for group in self.param_groups:  # the active tensors of a group are one run of the list
                 n = sum(p.grad is not None for p in group["params"])
                 c0, nc = t.chunks_of(first, n)
                 first += n
-                update(t.tensors, t.chunks, c0, nc, self._master, self._exp_avg, self._exp_avg_sq, self._scalars,
-                       lr=float(group["lr"]), betas=betas, eps=float(group["eps"]),
-                       weight_decay=float(group["weight_decay"]), use_clip=self.max_grad_norm is not None,
-                       zero_grads=self.zero_grads)
+                hyper = dict(lr=float(group["lr"]), betas=betas, eps=float(group["eps"]),
+                             weight_decay=float(group["weight_decay"]), use_clip=self.max_grad_norm is not None)
+                if accumulated:  # (the last fold zeroed the gradients)
+                    update(t.tensors, t.chunks, c0, nc, self._acc, self._master, self._exp_avg, self._exp_avg_sq,
+                           self._scalars, **hyper)
+                else:
+                    update(t.tensors, t.chunks, c0, nc, self._master, self._exp_avg, self._exp_avg_sq, self._scalars,
+                           **hyper, zero_grads=self.zero_grads)
         return loss
 
     def state_dict(self):
         """{"state": {index: {master, exp_avg, exp_avg_sq}}, "param_groups": [...], "step": int} — clones; reading
         the step counter is the one device-to-host copy of this class (not on the step path)."""
+        self._no_pending("state_dict")
         state = {i: {k: self.state[p][k].detach().clone() for k in _STATE_KEYS}
                  for i, p in self._indexed() if p in self._offs}
         return {"state": state, "param_groups": self._groups_dict(), "step": int(self._scalars[3].item())}
 
     @torch.no_grad()
     def load_state_dict(self, state_dict):
+        self._no_pending("load_state_dict")
         self._check_groups(state_dict)
         for p, s in self._full_state(state_dict):
             for k in _STATE_KEYS:
@@ -643,10 +738,17 @@ class FusedProdigy(_ProdigyCore, _FlatAdamW):
         use_clip = self.max_grad_norm is not None
         fin = self._finalize_args(lr, betas, beta3)
         with torch.cuda.device(self._device):
-            t.update([p.grad for p in params], params, [self._offs[p] for p in params])
+            accumulated = self._pending > 0
+            if accumulated:  # the gradient of the step is the accumulator: the fp32 mean of the micro-batches
+                self._last_fold(K)
+            else:
+                t.update([p.grad for p in params], params, [self._offs[p] for p in params])
             if self._pairs is None or self._pairs.numel() < 2 * t.n_chunks:
                 self._pairs = torch.empty(max(2 * t.n_chunks, 2048), device=self._device, dtype=torch.float32)
-            K.mt_grad_sqnorm(t.tensors, t.chunks, t.n_chunks, t.partials, t.flags)
+            if accumulated:
+                K.mt_grad_sqnorm_f32(t.tensors, t.chunks, t.n_chunks, self._acc, t.partials, t.flags)
+            else:
+                K.mt_grad_sqnorm(t.tensors, t.chunks, t.n_chunks, t.partials, t.flags)
             K.optim_finalize(t.partials, t.flags, t.n_chunks, self._scalars, max_norm=self.max_grad_norm or 0.0,
                              betas=betas, skip_nonfinite=self.skip_nonfinite, advance_step=True)
             K.prodigy_finalize(0, None, 0, self._scalars, self._d_block, **fin)
@@ -656,23 +758,28 @@ class FusedProdigy(_ProdigyCore, _FlatAdamW):
                 runs.append((group, *t.chunks_of(first, n)))
                 first += n
             for group, c0, nc in runs:
-                K.mt_prodigy_moments(t.tensors, t.chunks, c0, nc, self._master, self._p0, self._exp_avg,
-                                     self._exp_avg_sq, self._s, self._pairs, self._scalars, self._d_block,
-                                     betas=betas, beta3=beta3,
-                                     weight_decay=0.0 if self.decouple else float(group["weight_decay"]), d0=self.d0,
-                                     safeguard_warmup=self.safeguard_warmup, use_clip=use_clip)
+                moments = dict(betas=betas, beta3=beta3,
+                               weight_decay=0.0 if self.decouple else float(group["weight_decay"]), d0=self.d0,
+                               safeguard_warmup=self.safeguard_warmup, use_clip=use_clip)
+                state = (self._master, self._p0, self._exp_avg, self._exp_avg_sq, self._s, self._pairs,
+                         self._scalars, self._d_block)
+                if accumulated:
+                    K.mt_prodigy_moments_f32(t.tensors, t.chunks, c0, nc, self._acc, *state, **moments)
+                else:
+                    K.mt_prodigy_moments(t.tensors, t.chunks, c0, nc, *state, **moments)
             K.prodigy_finalize(1, self._pairs, t.n_chunks, self._scalars, self._d_block, **fin)
             for group, c0, nc in runs:
                 K.mt_prodigy_update(t.tensors, t.chunks, c0, nc, self._master, self._exp_avg, self._exp_avg_sq,
                                     self._scalars, self._d_block, eps=float(group["eps"]),
                                     weight_decay=float(group["weight_decay"]) if self.decouple else 0.0,
-                                    zero_grads=self.zero_grads)
+                                    zero_grads=self.zero_grads and not accumulated)  # (the last fold zeroed them)
         return loss
 
     def state_dict(self):
         """{"state": {index: {master, exp_avg, exp_avg_sq, s, p0}}, "param_groups": [...], "step": int, "prodigy":
         {the d block's values and the optimizer-wide options}} — clones; reading the step counter and the d block are
         the device-to-host copies of this class (not on the step path)."""
+        self._no_pending("state_dict")
         state = {i: {k: self.state[p][k].detach().clone() for k in _PRODIGY_KEYS}
                  for i, p in self._indexed() if p in self._offs}
         return {"state": state, "param_groups": self._groups_dict(), "step": int(self._scalars[3].item()),
@@ -680,6 +787,7 @@ class FusedProdigy(_ProdigyCore, _FlatAdamW):
 
     @torch.no_grad()
     def load_state_dict(self, state_dict):
+        self._no_pending("load_state_dict")
         self._check_groups(state_dict)
         pr = self._prodigy_entry(state_dict)
         for p, s in self._full_state(state_dict, _PRODIGY_KEYS):

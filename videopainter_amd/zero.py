@@ -39,6 +39,11 @@ a fourth collective, of 16 bytes per rank.
     d-phase 1       FusedProdigy's d update over the records in rank order     -> the same d block on every rank
     pass 2          per group: the update with the new d, bf16(p)              12 B read, 6 B written per parameter / world
 
+Gradient accumulation (`accumulate()`, optim._FlatAdamW): a micro-batch that does not step is one launch,
+vp_mt_accumulate_bf16 into the gradient staging buffer, and NO collective (DDP's no_sync); the stepping call folds the
+last micro-batch with the scale 1 / (micro-batches x world) in the pack's place, and everything from the
+reduce-scatter on is the step above.  No memory is added.
+
 A skipped step (a non-finite averaged gradient under skip_nonfinite) and Prodigy's no-progress step (sum |s| == 0 over
 all ranks) leave every bf16 parameter byte as it was on every rank: the unpack is gated on both, on the device.
 """
@@ -143,8 +148,9 @@ class _Sharded(_FlatAdamW):
     """What the three sharded optimizers share on top of `_FlatAdamW`: the communicator and this rank's place in it,
     the fp32 [per] state shards named by `_KEYS` (attributes `_master`, `_exp_avg`, ...; masters start as the fp32
     value of the bf16 parameters), the staging buffers, the norm records and the tables; the prologue of a step (tables,
-    pack, reduce-scatter, shard norm, record all-gather, finalise) and its epilogue (bf16 all-gather, unpack); and the
-    two checkpoint formats over `_KEYS`.  A subclass owns what runs between prologue and epilogue."""
+    pack — or, with folds pending, the last fold — reduce-scatter, shard norm, record all-gather, finalise) and its
+    epilogue (bf16 all-gather, unpack); and the two checkpoint formats over `_KEYS`.  A subclass owns what runs
+    between prologue and epilogue."""
 
     _KEYS = _STATE_KEYS
 
@@ -224,6 +230,17 @@ class _Sharded(_FlatAdamW):
         return self._flat32
 
     @property
+    def grad_accumulator(self) -> torch.Tensor:
+        """The fp32 accumulator of `accumulate()`: the gradient staging buffer itself (no memory of its own)."""
+        return self._flat32
+
+    def _fold_target(self):
+        """(the tables of ALL trainable tensors, the accumulator): a fold runs where the pack runs."""
+        gp = [0 if p.grad is None else p.grad.data_ptr() for p in self._params]
+        self._tables.update(gp, [p.data_ptr() for p in self._params])
+        return self._tables, self._flat32
+
+    @property
     def param_staging(self) -> torch.Tensor:
         """bf16 [world * per]: the all-gathered bf16(master) of the tensors updated in the last step."""
         return self._flat16
@@ -231,11 +248,13 @@ class _Sharded(_FlatAdamW):
     def _prologue(self, K, betas) -> _ShardTables:
         """Tables, pack, reduce-scatter, shard norm, record all-gather, finalise: after it `_grad_shard` holds the
         averaged gradient of this shard and the scalars block is the step's, the same on every rank."""
-        gp = [0 if p.grad is None else p.grad.data_ptr() for p in self._params]
-        t, c, r = self._tables, self._comm, self.rank
-        t.update(gp, [p.data_ptr() for p in self._params])
-        K.zero_pack(t.tensors, t.chunks, t.n_chunks, self._flat32, inv_world=1.0 / self.world,
-                    zero_grads=self.zero_grads)
+        c, r = self._comm, self.rank
+        if self._pending:  # the last fold takes the pack's place: the mean over micro-batches and ranks in one scale
+            t = self._last_fold(K, self.world)
+        else:
+            t, _ = self._fold_target()
+            K.zero_pack(t.tensors, t.chunks, t.n_chunks, self._flat32, inv_world=1.0 / self.world,
+                        zero_grads=self.zero_grads)
         c.reduce_scatter_sum(r, self._grad_shard, self._flat32)
         K.zero_shard_sqnorm(t.ranges, t.n_ranges, self._grad_shard, t.partials, t.flags, self._record)
         c.all_gather(r, self._records, self._record)
@@ -261,6 +280,7 @@ class _Sharded(_FlatAdamW):
         "exp_avg", "exp_avg_sq", ...), "param_groups"}.  Reloads into the same world size and rank only;
         `full_state_dict()` is the portable form.  Reading the step counter is a device-to-host copy (not on the step
         path)."""
+        self._no_pending("state_dict")
         sd = {"world": self.world, "rank": self.rank, "per": self.per, "step": int(self._scalars[3].item())}
         sd.update({k: v.detach().clone() for k, v in self._shards().items()})
         sd["param_groups"] = self._groups_dict()
@@ -272,6 +292,7 @@ class _Sharded(_FlatAdamW):
         state_dict() format — {"state": {index: {master, exp_avg, exp_avg_sq, ...}}, "param_groups", "step"},
         per-parameter fp32 clones.  One fp32 all-gather per state buffer through the gradient staging buffer (no extra
         flat buffer)."""
+        self._no_pending("full_state_dict")
         state = {i: {} for i, p in self._indexed() if p in self._offs}
         with torch.cuda.device(self._master.device):
             for k, shard in self._shards().items():
@@ -289,6 +310,7 @@ class _Sharded(_FlatAdamW):
         optimizer's, or full_state_dict() of any world size): this rank's slice of every tensor.  Restores the state
         shards, the parameter groups' options and the step counter; the bf16 parameters are left as they are (a
         checkpoint's model weights are bf16(master) already)."""
+        self._no_pending("load_state_dict")
         self._check_groups(state_dict)
         keys, mine = self._KEYS, self._shards()
         if "state" not in state_dict:
@@ -332,7 +354,11 @@ class ShardedFusedAdamW(_Sharded):
         first.  Masters start as the fp32 value of the bf16 parameters.
       * the set of parameters whose `.grad` is None is the same on every rank in every step.  Such a parameter is
         left untouched (no decay, no moment update), as in FusedAdamW; its flat gradient region is written as zeros.
-    `step()` consumes whatever is in `.grad` (gradient accumulation is the caller's business).  `grad_norm` (of the
+    `step()` consumes whatever is in `.grad`, plus the micro-batches `accumulate()` has folded since the last step:
+    `for i in range(k): backward(); opt.accumulate() if i < k - 1 else opt.step()` with UNSCALED micro-batch losses
+    averages over micro-batches and ranks in fp32; `accumulate()` issues no collective, and the set of parameters
+    with a gradient must be the same in every micro-batch.  The checkpoint methods are refused while folds are pending
+    (`full_state_dict()` gathers through the staging buffer that holds them).  `grad_norm` (of the
     averaged gradient, before the clip), `clip_coef`, `nonfinite`, `step_count` and `last_step_skipped` are device
     tensors, bit-identical on every rank.  Other differences from torch.optim.AdamW are FusedAdamW's: one step
     counter, the same betas in every group, bf16 contiguous parameters on one device.
@@ -486,6 +512,7 @@ class ShardedFusedProdigy(_ProdigyCore, _Sharded):
     @torch.no_grad()
     def load_state_dict(self, state_dict):
         """Either format (a dict without the d block is refused before anything is copied)."""
+        self._no_pending("load_state_dict")
         pr = self._prodigy_entry(state_dict)
         super().load_state_dict(state_dict)
         self._load_prodigy_dict(pr)
