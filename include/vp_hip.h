@@ -33,7 +33,7 @@ extern "C" {
 #define VP_ERR_UNSUPPORTED 1001
 
 /* ABI version: bump when any struct layout or signature below changes. */
-#define VP_ABI_VERSION 30
+#define VP_ABI_VERSION 31
 int vp_abi_version(void);
 /* "<sha256 of sources + flags>:<sha256 of the compiler version>" of the build (no reference counterpart) */
 const char* vp_build_digest(void);
@@ -1087,6 +1087,84 @@ int vp_mt_prodigy_moments_f32(const vp_mt_tensor* tensors, const vp_mt_chunk* ch
                               double beta2, double beta3, double weight_decay, double d0, int32_t safeguard_warmup,
                               int32_t use_clip, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * The front of the training iteration (ABI 31; csrc/train_inputs.hip): everything between the three VAE encodes and
+ * the models, train/train_cogvideox_inpainting_i2v_video.py:1774-1853 — the pixel-space first-frame noise, the three
+ * posterior samples with the scaling factor and the [B, C, F, H, W] -> [B, F, C, H, W] permute, the zero-padded image
+ * latents and their dropout, the mask's nearest resize as the 17th conditioning channel, scheduler.add_noise and the
+ * 32-channel concatenation.  One launch, vector loads / stores, plain stores only, no host read of the device.
+ *
+ * Noise: a Philox4x32-10 counter generator.  Normal number e (a 64-bit element index) of (seed, stream) comes from
+ * block e >> 2, lane e & 3: counter (lo32(block), hi32(block), lo32(stream), hi32(stream)), key (lo32(seed),
+ * hi32(seed)), ten rounds with multipliers M0 = 0xD2511F53 (on c0) and M1 = 0xCD9E8D57 (on c2) and key increments
+ * 0x9E3779B9 / 0xBB67AE85 between rounds; round output (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1,
+ * lo(M0 c0)).  Output words (x0, x1) give lanes 0 and 1, (x2, x3) lanes 2 and 3, by Box-Muller in fp32:
+ * u1 = ((xa >> 8) + 1) 2^-24 in (0, 1], u2 = (xb >> 8) 2^-24, r = sqrt(-2 ln u1), even lane r cos(2 pi u2), odd lane
+ * r sin(2 pi u2) (logf, sincospif(2 u2): the accurate forms).  The fp32 value is the fp32 output; the bf16 output is
+ * its one rounding.  The stream is a function of (seed, stream, e) alone: independent of launch shape and rank count,
+ * and continued by continuing the offset. */
+/* out[i] = normal number (offset + i) of (seed, stream), i < n; out fp32 (out_is_f32) or bf16.  Any offset and n:
+ * whole blocks of four are one vector store where the address allows it, the head and tail scalar stores. */
+int vp_philox_normal(void* out, int32_t out_is_f32, int64_t n, uint64_t seed, uint64_t stream, uint64_t offset,
+                     void* hip_stream);
+/* :1774-1779 on the first frame as the caller laid it out: x [B, n_per] fp32 (x_is_f32) or bf16, sigma [B] bf16 on
+ * the device, noise in x's dtype or NULL (then normal number b n_per + i of (seed, stream), drawn in x's dtype as
+ * vp_philox_normal draws it).  out bf16 [B, n_per], in torch's promoted arithmetic:
+ *   fp32 x:  out = bf16(x + n * float(sigma_b))     the product and the sum each rounded in fp32
+ *   bf16 x:  out = bf16(x + bf16(n * sigma_b)) */
+int vp_noise_frame(const void* x, int32_t x_is_f32, const void* sigma, const void* noise, void* out, int32_t B,
+                   int64_t n_per, uint64_t seed, uint64_t stream, void* hip_stream);
+/* :1780-1853 in one launch.  rbf = round to bf16; every product below that is added to something has its own
+ * rounding (it is not contracted into an fma).
+ *   posterior parameters p_*: the VAE encoder's channels-last rows [B, T, h, w, ldp], mean = channels [0, L),
+ *     logvar = [L, 2L); p_image has T = 1 (the noised first frame)
+ *   sample(p, n):  lv = clamp(logvar, -30, 20);  std = rbf(expf(rbf(0.5 lv)));  x = rbf(mean + rbf(std n));
+ *                  z = rbf(x * scaling_factor)                       (scaling_factor an fp32 value)
+ *   noise_video / noise_cond / noise_image: the posterior noises [B, L, T, h, w] bf16 (T = 1 for the image);
+ *     noise_diff: the diffusion noise eps [B, T, L, h, w] bf16.  NULL: normal number = the element's linear index in
+ *     that layout of (seed, stream_*), rounded to bf16 — what vp_philox_normal(bf16, offset 0) writes into such a
+ *     tensor.
+ *   target               [B, T, L, h, w]      = z_video
+ *   noisy                [B, T, L, h, w]      = rbf(rbf(sa_t z_video) + rbf(sb_t eps)),  (sa_t, sb_t) = sa_sb[t_b],
+ *                                               t_b = timesteps[b] clamped to [0, n_alphas) as vp_v_loss_bf16 clamps
+ *   noisy_model_input    [B, T, 2L, h, w]     channels [0, L) = noisy;  [L, 2L) = z_image in frame 0, zero in frames
+ *                                               >= 1, zero everywhere when image_dropout
+ *   masks_latent         [B, T, 1, h, w]      = bf16(mask[b, ft, 0, fy, fx]), F.interpolate(mode="nearest") per axis:
+ *                                               src = min((int)floorf((float)dst * ((float)in / (float)out)), in - 1)
+ *   conditioning_latents [B, T, L + 1, h, w]  channels [0, L) = z_cond, channel L = masks_latent
+ * Every output element is written exactly once and nothing else is written.  16-byte loads and stores when h w is a
+ * multiple of 8 and the noise / output pointers are 16-byte aligned, element-wise otherwise (same values).
+ * VP_ERR_ARG (before any launch): a NULL required pointer, struct_bytes != sizeof, L != 16, ldp < 2L, B, T, h, w,
+ * Fp, Hp, Wp or n_alphas <= 0, mask_dtype not 0..2.  (The image posterior has T = 1 by construction: image_T must
+ * be 1.) */
+typedef struct {
+  int32_t struct_bytes; /* sizeof(vp_train_inputs_desc): the layout check of this descriptor */
+  int32_t B, T, h, w, L, ldp;
+  int32_t image_T;      /* frames of p_image: must be 1 */
+  int32_t Fp, Hp, Wp;   /* the pixel mask [B, Fp, 1, Hp, Wp] */
+  int32_t mask_dtype;   /* 0 fp32, 1 bf16, 2 uint8 */
+  int32_t image_dropout;
+  int32_t n_alphas;
+  float scaling_factor;
+  int32_t pad0;
+  const void* p_video;
+  const void* p_cond;
+  const void* p_image;
+  const void* noise_video;
+  const void* noise_cond;
+  const void* noise_image;
+  const void* noise_diff;
+  uint64_t seed, stream_video, stream_cond, stream_image, stream_diff;
+  const int64_t* timesteps; /* [B] */
+  const float* sa_sb;       /* [n_alphas, 2] */
+  const void* mask;
+  void* target;
+  void* noisy;
+  void* noisy_model_input;
+  void* masks_latent;
+  void* conditioning_latents;
+} vp_train_inputs_desc;
+int vp_train_inputs_bf16(const vp_train_inputs_desc* d, void* stream);
 
 #ifdef __cplusplus
 }

@@ -2,8 +2,9 @@
 
     python tools/bench_train.py [--steps K] [--warmup W] [--height 60 --width 90]
                                 [--optimizer none|torch|fused|adam|prodigy|sharded|sharded-adam|sharded-prodigy]
-                                [--loss] [--accumulate K]
+                                [--loss] [--accumulate K] [--inputs]
                                 [--fp8-gemm [ffn,qkv,out]] [--rounds R]
+    python tools/bench_train.py --inputs-ab [--steps K] [--warmup W] [--rounds R]
 
 One step = the reference's training iteration (train/train_cogvideox_inpainting_i2v_video.py:1856-1892 with the
 launch script train/VideoPainter.sh: 49 frames 480x720 -> latent 13x60x90, batch 1, bf16, branch_layer_num 2,
@@ -33,6 +34,16 @@ per arm the step time (median, min, max over all timed steps), the per-class HIP
 gemm_mx, attention, attention_bwd) and the peak memory of the arm's timed steps, plus whether the two arms' ranges
 overlap.  Both arms' cached transposed dgrad weights (bf16 and MX) stay resident throughout, so the peaks compare
 the arms' activations, not their weight caches.
+
+--inputs (with --loss) starts the step from pixels, the script's lines 1774-1853 included: a synthetic 49-frame
+480x720 fp32 video, its masked copy and a box mask go through videopainter_amd.prepare_training_inputs (the
+first-frame noise, the three VAE encodes with enable_tiling + enable_slicing as train/VideoPainter.sh runs them, on a
+5b VAE with synthetic weights, and the one fused launch), and the models and the loss run on what it returns.  The
+JSON line adds, by HIP events per step, vae_encode_ms (the three encodes together), prepare_ms (vp_noise_frame +
+vp_train_inputs_bf16) and step_ms_events (the whole step), and vae_encode_share.
+
+--inputs-ab times that front without the encodes against its restatement from torch ops (torch_front below), both
+on the same three encodes, alternating in one process, --rounds rounds (at least 5) of --steps calls per arm.
 """
 from __future__ import annotations
 
@@ -122,8 +133,149 @@ def fp8_gemm_ab(args, tr, step, K) -> dict:
     return res
 
 
+PIX_F, PIX_H, PIX_W = 49, 480, 720  # the launch script's clip
+
+
+def synthetic_pixels(dev, rank: int = 0):
+    """A 49-frame 480x720 fp32 video in [-1, 1], its masked copy (the conditioning video) and the box mask
+    [1, 49, 1, 480, 720] (frame 0 clear), made on the device."""
+    g = torch.Generator(device=dev).manual_seed(11 + rank)
+    px = torch.rand(1, PIX_F, 3, PIX_H, PIX_W, generator=g, device=dev) * 2 - 1
+    mk = torch.zeros(1, PIX_F, 1, PIX_H, PIX_W, device=dev)
+    mk[:, 1:, :, PIX_H // 4:PIX_H // 4 + PIX_H // 2, PIX_W // 4:PIX_W // 4 + PIX_W // 2] = 1.0
+    return px, px * (1 - mk), mk
+
+
+def training_vae(dev):
+    """The 5b VAE with synthetic weights, tiled and sliced as train/VideoPainter.sh runs it."""
+    from videopainter_amd.vae import AutoencoderKLCogVideoX
+    vae = AutoencoderKLCogVideoX.from_config({}, device=dev)
+    vae.init_synthetic_weights_(1236)
+    vae.enable_tiling()
+    vae.enable_slicing()
+    return vae
+
+
+def timed_encodes(vae, events):
+    """Wrap vae.encode so that every call leaves a pair of HIP events in `events`."""
+    encode = vae.encode
+
+    def timed(x, *a, **kw):
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        ev[0].record()
+        out = encode(x, *a, **kw)
+        ev[1].record()
+        events.append(ev)
+        return out
+
+    vae.encode = timed
+
+
+def torch_front(sched, p_image_of, px, p_video, p_cond, mk, scaling_factor, L=16):
+    """train/train_cogvideox_inpainting_i2v_video.py:1774-1853 from torch ops on the device, on the encoder's
+    posterior parameters (channels-last [B, T, h, w, 2L]; the permuted views cost nothing).  p_image_of(noisy_images)
+    returns the image posterior (the A/B hands both arms the same three encodes)."""
+    import torch.nn.functional as Fn
+    bf = torch.bfloat16
+
+    def sample(p):
+        mean = p[..., :L].permute(0, 4, 1, 2, 3)
+        std = torch.exp(0.5 * torch.clamp(p[..., L:2 * L].permute(0, 4, 1, 2, 3), -30.0, 20.0))
+        x = mean + std * torch.randn(mean.shape, device=p.device, dtype=bf)
+        return (x.permute(0, 2, 1, 3, 4) * scaling_factor).to(memory_format=torch.contiguous_format, dtype=bf)
+
+    images = px[:, :1].permute(0, 2, 1, 3, 4)
+    sigma = torch.exp(torch.normal(mean=-3.0, std=0.5, size=(images.size(0),), device=px.device, dtype=bf))
+    noisy_images = images + torch.randn_like(images) * sigma[:, None, None, None, None]
+    image_latents = sample(p_image_of(noisy_images.to(bf)))
+    model_input = sample(p_video)
+    cond = sample(p_cond)
+    padding = image_latents.new_zeros((cond.shape[0], cond.shape[1] - 1, *cond.shape[2:]))
+    image_latents = torch.cat([image_latents, padding], dim=1)
+    m = mk.permute(0, 2, 1, 3, 4)
+    m = Fn.interpolate(m, size=(cond.shape[1], cond.shape[3], cond.shape[4])).permute(0, 2, 1, 3, 4).to(bf)
+    cond = torch.concat([cond, m], -3).to(bf)
+    noise = torch.randn_like(model_input).to(bf)
+    ts = torch.randint(0, sched.config.num_train_timesteps, (model_input.shape[0],), device=px.device).long()
+    noisy = sched.add_noise(model_input, noise, ts)
+    return model_input, noisy, torch.cat([noisy, image_latents], dim=2), cond, m, ts
+
+
+def inputs_ab(args) -> dict:
+    """--inputs-ab: the torch-op front against vp_noise_frame + vp_train_inputs_bf16, on the same three encodes
+    (made once), the arms alternating in this process: --rounds rounds (at least 5) of --steps calls per arm.  Per
+    call: HIP events around the arm, and the host clock around the arm plus a synchronise."""
+    import statistics
+    from videopainter_amd import CogVideoXDPMScheduler, TrainingNoise
+    from videopainter_amd import kernels as K
+    from videopainter_amd import training as TR
+    dev = "cuda"
+    vae, sched = training_vae(dev), CogVideoXDPMScheduler()
+    px, cpx, mk = synthetic_pixels(dev)
+    noise = TrainingNoise(1)
+    sf = float(vae.config.scaling_factor)
+    with torch.no_grad():
+        p_image = vae.encode(px[:, :1].permute(0, 2, 1, 3, 4).to(torch.bfloat16)).latent_dist._p.contiguous()
+        p_video = vae.encode(px.permute(0, 2, 1, 3, 4)).latent_dist._p.contiguous()
+        p_cond = vae.encode(cpx.permute(0, 2, 1, 3, 4)).latent_dist._p.contiguous()
+    table = sched.add_noise_table(torch.bfloat16, dev)
+    ids = (TR.NOISE_POSTERIOR_VIDEO, TR.NOISE_POSTERIOR_COND, TR.NOISE_POSTERIOR_IMAGE, TR.NOISE_DIFFUSION)
+
+    def native():
+        ts_h, sigma_h, _ = noise.host_draws(1, 1000)
+        ts, sigma = TrainingNoise.upload(ts_h, sigma_h, dev)
+        K.noise_frame(px[:, 0], sigma, None, seed=noise.seed, stream=noise.stream(TR.NOISE_IMAGE_PIXELS))
+        out = K.train_inputs(p_video, p_cond, p_image, mk, ts, table, sf, seed=noise.seed,
+                             streams=tuple(noise.stream(i) for i in ids))
+        noise.next_step()
+        return out
+
+    def torch_ops():
+        with torch.no_grad():
+            return torch_front(sched, lambda noisy_images: p_image, px, p_video, p_cond, mk, sf)
+
+    arms = (("torch", torch_ops), ("native", native))
+    rounds = max(5, args.rounds)
+    for _, fn in arms:
+        for _ in range(max(2, args.warmup)):
+            fn()
+    torch.cuda.synchronize()
+    dev_ms = {n: [] for n, _ in arms}
+    wall_ms = {n: [] for n, _ in arms}
+    for r in range(rounds):
+        for name, fn in arms:
+            for _ in range(args.steps):
+                ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                ev[0].record()
+                fn()
+                ev[1].record()
+                torch.cuda.synchronize()
+                wall_ms[name].append((time.perf_counter() - t0) * 1e3)
+                dev_ms[name].append(ev[0].elapsed_time(ev[1]))
+            print(f"round {r} {name}: events {[round(v, 3) for v in dev_ms[name][-args.steps:]]} ms, host "
+                  f"{[round(v, 3) for v in wall_ms[name][-args.steps:]]} ms", file=sys.stderr, flush=True)
+    res = dict(metric="front of the training step without the encodes (:1774-1853; 49f 480x720, B=1): torch ops "
+                      "against vp_noise_frame + vp_train_inputs_bf16", rounds=rounds, steps_per_round=args.steps,
+               unit="ms/call", arms={})
+    for name, _ in arms:
+        res["arms"][name] = {k: dict(median=statistics.median(v), min=min(v), max=max(v))
+                             for k, v in (("events_ms", dev_ms[name]), ("host_ms", wall_ms[name]))}
+    t, n = res["arms"]["torch"], res["arms"]["native"]
+    for k in ("events_ms", "host_ms"):
+        res[f"native_minus_torch_median_{k}"] = n[k]["median"] - t[k]["median"]
+        res[f"ranges_overlap_{k}"] = not (n[k]["max"] < t[k]["min"] or t[k]["max"] < n[k]["min"])
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--inputs", action="store_true",
+                    help="start the step from synthetic pixels: prepare_training_inputs (frame noise, three tiled and "
+                         "sliced VAE encodes, the fused front) feeds the models and the loss")
+    ap.add_argument("--inputs-ab", action="store_true",
+                    help="interleaved A/B of the front without the encodes: torch ops against the HIP front")
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--height", type=int, default=60)
@@ -140,6 +292,9 @@ def main():
                     help="K micro-batches per optimizer step: opt.accumulate() after the first K - 1, opt.step() "
                          "after the last (--steps and --warmup count optimizer steps)")
     args = ap.parse_args()
+    if args.inputs_ab:
+        print(json.dumps(inputs_ab(args)))
+        return
     from videopainter_amd import CogVideoXTransformer3DModel, CogvideoXBranchModel, device_scope
     from videopainter_amd import kernels as K
     from videopainter_amd.config import COGVIDEOX_5B_I2V
@@ -213,6 +368,16 @@ def main():
         from videopainter_amd import CogVideoXDPMScheduler, inpainting_v_loss
         alphas_cumprod = CogVideoXDPMScheduler().alphas_cumprod.to(dev, torch.float32)
         target = torch.randn(1, F, 16, HL, WL, generator=g).to(dev, torch.bfloat16)
+    enc_events, prep = [], None
+    if args.inputs:
+        if (HL, WL) != (PIX_H // 8, PIX_W // 8) or not args.loss or args.accumulate > 1 or args.fp8_gemm is not None:
+            raise SystemExit("--inputs runs the default 480x720 clip with --loss (no --accumulate, no --fp8-gemm)")
+        from videopainter_amd import TrainingNoise, prepare_training_inputs
+        vae, sched = training_vae(dev), CogVideoXDPMScheduler()
+        px, cpx, pmask = synthetic_pixels(dev, rank)
+        tnoise = TrainingNoise(2024, rank=rank)
+        timed_encodes(vae, enc_events)
+        prep = K.timed_launches("noise_frame", "train_inputs")
     K_acc = args.accumulate
     if K_acc < 1 or (K_acc > 1 and args.optimizer in ("none", "torch")):
         raise SystemExit("--accumulate K needs K >= 1 and one of the fused / sharded optimizers")
@@ -246,6 +411,19 @@ def main():
             micro_batch(j == K_acc - 1)
 
     def step():
+        if args.inputs:  # pixels in: the step's front, then the models on what it made
+            r = prepare_training_inputs(vae, sched, px, cpx, pmask, noise=tnoise)
+            tnoise.next_step()
+            samples = br(hidden_states=r.noisy_video_latents, encoder_hidden_states=enc,
+                         branch_cond=r.conditioning_latents, timestep=r.timesteps, image_rotary_emb=rope,
+                         return_dict=False)[0]
+            out = tr(hidden_states=r.noisy_model_input, encoder_hidden_states=enc, timestep=r.timesteps,
+                     image_rotary_emb=rope, branch_block_samples=samples, branch_block_masks=r.masks,
+                     return_dict=False)[0]
+            inpainting_v_loss(out, r.noisy_video_latents, r.model_input, r.timesteps, alphas_cumprod, r.masks,
+                              1.0).backward()
+            finish_step()
+            return
         samples = br(hidden_states=lat, encoder_hidden_states=enc, branch_cond=cond, timestep=ts,
                      image_rotary_emb=rope, return_dict=False)[0]
         out = tr(hidden_states=hidden, encoder_hidden_states=enc, timestep=ts, image_rotary_emb=rope,
@@ -254,6 +432,9 @@ def main():
             inpainting_v_loss(out, lat, target, ts, alphas_cumprod, mask, 1.0).backward()
         else:
             out.backward(dout)
+        finish_step()
+
+    def finish_step():
         if opt is not None:
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             ev[0].record()
@@ -275,12 +456,18 @@ def main():
     torch.cuda.synchronize()
     opt_events.clear()
     acc_events.clear()
+    enc_events.clear()
+    step_events = []
+    if prep is not None:
+        prep.__enter__()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step()
+        timed_call(step, step_events)
         torch.cuda.synchronize()
         print(f"step {i}: {time.perf_counter() - t0:.2f}s", file=sys.stderr, flush=True)
     el = (time.perf_counter() - t0) / args.steps
+    if prep is not None:
+        prep.__exit__(None, None, None)
     replicas = None
     if args.optimizer in SHARDED:
         el = VD.max_over_ranks(el, dev)
@@ -299,6 +486,13 @@ def main():
                loss="inpainting_v_loss" if args.loss else None,
                tflops_per_s=fl["total"] / el / 1e12, flop_per_step=fl, ntok=ntok,
                peak_mem_gib=torch.cuda.max_memory_allocated() / 2 ** 30)
+    if args.inputs:  # HIP events: the three encodes of a step together, the frame noise + the fused launch, the step
+        ev_ms = lambda evs: sum(a.elapsed_time(b) for a, b in evs) / args.steps  # noqa: E731
+        res.update(inputs="prepare_training_inputs (49f 480x720 fp32 pixels, tiled + sliced VAE)",
+                   vae_encode_ms=ev_ms(enc_events),
+                   prepare_ms=ev_ms(prep.events["noise_frame"]) + ev_ms(prep.events["train_inputs"]),
+                   step_ms_events=ev_ms(step_events))
+        res["vae_encode_share"] = res["vae_encode_ms"] / res["step_ms_events"]
     if K_acc > 1:
         res.update(accumulate=K_acc, ms_per_micro_batch=el * 1e3 / K_acc,
                    accumulate_ms=sum(a.elapsed_time(b) for a, b in acc_events) / len(acc_events))

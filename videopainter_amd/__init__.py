@@ -37,7 +37,7 @@ def __getattr__(name):
     if name in ("ShardedFusedAdamW", "ShardedFusedAdam", "ShardedFusedProdigy"):
         from . import zero
         return getattr(zero, name)
-    if name in ("inpainting_v_loss",):
+    if name in ("inpainting_v_loss", "TrainingNoise", "prepare_training_inputs", "TrainingInputs"):
         from . import training
         return getattr(training, name)
     raise AttributeError(name)

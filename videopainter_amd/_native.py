@@ -11,7 +11,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VP_HIP_LIB", os.path.join(_HERE, "_lib", "libvp_hip.so"))
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 vp = C.c_void_p
 i32 = C.c_int32
@@ -126,6 +126,20 @@ class ZeroRange(C.Structure):
 
 class ZeroRecord(C.Structure):
     _fields_ = [("sqsum", f32), ("nonfinite", i32)]
+
+
+class TrainInputsDesc(C.Structure):
+    """vp_train_inputs_desc (ABI 31).  struct_bytes carries sizeof: the library checks the layout per call."""
+    _fields_ = [("struct_bytes", i32), ("B", i32), ("T", i32), ("h", i32), ("w", i32), ("L", i32), ("ldp", i32),
+                ("image_T", i32), ("Fp", i32), ("Hp", i32), ("Wp", i32), ("mask_dtype", i32), ("image_dropout", i32),
+                ("n_alphas", i32), ("scaling_factor", f32), ("pad0", i32),
+                ("p_video", vp), ("p_cond", vp), ("p_image", vp),
+                ("noise_video", vp), ("noise_cond", vp), ("noise_image", vp), ("noise_diff", vp),
+                ("seed", C.c_uint64), ("stream_video", C.c_uint64), ("stream_cond", C.c_uint64),
+                ("stream_image", C.c_uint64), ("stream_diff", C.c_uint64),
+                ("timesteps", vp), ("sa_sb", vp), ("mask", vp),
+                ("target", vp), ("noisy", vp), ("noisy_model_input", vp), ("masks_latent", vp),
+                ("conditioning_latents", vp)]
 
 
 (EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_SCALE, EPI_GATED, EPI_BIAS_ADDROWS, EPI_BIAS_GELU_MXFP8, EPI_BIAS_QKNORM_ROPE,
@@ -258,6 +272,9 @@ _SIGS = {
                              C.c_double, i32, vp]),
     "vp_mt_prodigy_moments_f32": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_double,
                                         C.c_double, C.c_double, C.c_double, i32, i32, vp]),
+    "vp_philox_normal": (i32, [vp, i32, i64, C.c_uint64, C.c_uint64, C.c_uint64, vp]),
+    "vp_noise_frame": (i32, [vp, i32, vp, vp, vp, i32, i64, C.c_uint64, C.c_uint64, vp]),
+    "vp_train_inputs_bf16": (i32, [C.POINTER(TrainInputsDesc), vp]),
 }
 
 EXPORTS = tuple(_SIGS)

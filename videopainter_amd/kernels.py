@@ -2090,3 +2090,121 @@ def v_loss(model_output: torch.Tensor, noisy: torch.Tensor, target: torch.Tensor
                                    _p(alphas_cumprod), alphas_cumprod.numel(), B, F, Cc, H * W, float(lam),
                                    _p(partials), _p(loss), _p(dout), _stream()), "vp_v_loss_bf16")
     return loss, dout
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the front of the training iteration (csrc/train_inputs.hip)
+# ------------------------------------------------------------------------------------------------------------------
+
+_U64 = 0xFFFFFFFFFFFFFFFF
+
+
+def philox_normal_(out: torch.Tensor, seed: int, stream: int, offset: int = 0) -> torch.Tensor:
+    """Fill `out` (fp32 / bf16, contiguous) with the normal numbers offset .. offset + numel of (seed, stream)."""
+    if not out.is_cuda or out.dtype not in (torch.float32, BF16):
+        raise TypeError("philox_normal_: out must be a float32 / bfloat16 device tensor")
+    if not out.is_contiguous():
+        raise ValueError("philox_normal_: out must be contiguous")
+    if out.numel():
+        N.check(N.lib().vp_philox_normal(_p(out), int(out.dtype == torch.float32), out.numel(), seed & _U64,
+                                         stream & _U64, offset & _U64, _stream()), "vp_philox_normal")
+    return out
+
+
+def noise_frame(x: torch.Tensor, sigma: torch.Tensor, noise: Optional[torch.Tensor] = None, *, seed: int = 0,
+                stream: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """bf16(x + n * sigma[b]) in torch's promoted arithmetic: x [B, ...] fp32 / bf16, sigma bf16 [B], noise like x or
+    None (then the normal numbers of (seed, stream) by linear index, drawn in x's dtype).  out: a contiguous bf16
+    tensor of x's shape to write into."""
+    if not x.is_cuda or x.dtype not in (torch.float32, BF16):
+        raise TypeError("noise_frame: x must be a float32 / bfloat16 device tensor")
+    _chk(sigma, "sigma")
+    x = x.contiguous()
+    B = x.shape[0]
+    if sigma.shape != (B,) or not sigma.is_contiguous():
+        raise ValueError("noise_frame: sigma must be a contiguous [B] tensor")
+    if noise is not None:
+        _chk(noise, "noise", x.dtype)
+        if noise.shape != x.shape:
+            raise ValueError("noise_frame: noise must have x's shape")
+        noise = noise.contiguous()
+    if out is None:
+        out = torch.empty(x.shape, device=x.device, dtype=BF16)
+    else:
+        _chk(out, "out")
+        if out.shape != x.shape or not out.is_contiguous():
+            raise ValueError("noise_frame: out must be contiguous with x's shape")
+    ev = _t0("noise_frame")
+    N.check(N.lib().vp_noise_frame(_p(x), int(x.dtype == torch.float32), _p(sigma), _p(noise), _p(out), B,
+                                   x.numel() // B, seed & _U64, stream & _U64, _stream()), "vp_noise_frame")
+    _t1("noise_frame", ev)
+    return out
+
+
+_MASK_DTYPES = {torch.float32: 0, BF16: 1, torch.uint8: 2}
+
+
+def train_inputs(p_video: torch.Tensor, p_cond: torch.Tensor, p_image: torch.Tensor, mask: torch.Tensor,
+                 timesteps: torch.Tensor, sa_sb: torch.Tensor, scaling_factor: float, *, latent_channels: int = 16,
+                 image_dropout: bool = False, noises: Sequence[Optional[torch.Tensor]] = (None, None, None, None),
+                 seed: int = 0, streams: Sequence[int] = (0, 0, 0, 0), out: Optional[Sequence[torch.Tensor]] = None):
+    """vp_train_inputs_bf16: (target, noisy, noisy_model_input, masks_latent, conditioning_latents) — new tensors, or
+    the five contiguous bf16 tensors of `out`, in that order.
+
+    p_*: the encoder's channels-last posterior parameters [B, T, h, w, ld] (p_image: T = 1); mask [B, Fp, 1, Hp, Wp]
+    fp32 / bf16 / uint8; timesteps int64 [B]; sa_sb fp32 [n, 2]; noises / streams in the order video posterior,
+    conditioning posterior, image posterior, diffusion (a None noise is drawn in the kernel from (seed, stream))."""
+    L = latent_channels
+    for t, n in ((p_video, "p_video"), (p_cond, "p_cond"), (p_image, "p_image")):
+        _chk(t, n)
+        if t.dim() != 5 or not t.is_contiguous():
+            raise ValueError(f"{n} must be contiguous [B, T, h, w, ld]")
+    B, T, h, w, ld = p_video.shape
+    if p_cond.shape != p_video.shape or p_image.shape != (B, 1, h, w, ld):
+        raise ValueError("train_inputs: p_cond must match p_video and p_image must be its one-frame shape")
+    if not mask.is_cuda or mask.dtype not in _MASK_DTYPES:
+        raise TypeError("mask must be a float32 / bfloat16 / uint8 device tensor")
+    if mask.dim() != 5 or mask.shape[0] != B or mask.shape[2] != 1 or not mask.is_contiguous():
+        raise ValueError("mask must be contiguous [B, Fp, 1, Hp, Wp]")
+    _chk(timesteps, "timesteps", torch.int64)
+    _chk(sa_sb, "sa_sb", torch.float32)
+    if timesteps.shape != (B,) or not timesteps.is_contiguous():
+        raise ValueError("timesteps must be a contiguous [B] tensor")
+    if sa_sb.dim() != 2 or sa_sb.shape[1] != 2 or not sa_sb.is_contiguous():
+        raise ValueError("sa_sb must be a contiguous [n, 2] table")
+    shapes = ((B, L, T, h, w), (B, L, T, h, w), (B, L, 1, h, w), (B, T, L, h, w))
+    noises = list(noises)
+    for i, (nz, shp) in enumerate(zip(noises, shapes)):
+        if nz is not None:
+            _chk(nz, f"noises[{i}]")
+            if tuple(nz.shape) != shp:
+                raise ValueError(f"noises[{i}] must be {shp}, got {tuple(nz.shape)}")
+            noises[i] = nz.contiguous()
+    dev = p_video.device
+    new = lambda c: torch.empty(B, T, c, h, w, device=dev, dtype=BF16)  # noqa: E731
+    if out is None:
+        out = (new(L), new(L), new(2 * L), new(1), new(L + 1))
+    elif len(out) != 5:
+        raise ValueError("train_inputs: out must hold five tensors")
+    for t, c in zip(out, (L, L, 2 * L, 1, L + 1)):
+        _chk(t, "out")
+        if t.shape != (B, T, c, h, w) or not t.is_contiguous():
+            raise ValueError(f"train_inputs: an output must be contiguous {(B, T, c, h, w)}, got {tuple(t.shape)}")
+    target, noisy, nmi, mlat, cond = out
+    d = N.TrainInputsDesc()
+    d.struct_bytes = C.sizeof(N.TrainInputsDesc)
+    d.B, d.T, d.h, d.w, d.L, d.ldp, d.image_T = B, T, h, w, L, ld, p_image.shape[1]
+    d.Fp, d.Hp, d.Wp = mask.shape[1], mask.shape[3], mask.shape[4]
+    d.mask_dtype, d.image_dropout, d.n_alphas = _MASK_DTYPES[mask.dtype], int(bool(image_dropout)), sa_sb.shape[0]
+    d.scaling_factor = float(scaling_factor)
+    d.p_video, d.p_cond, d.p_image = _p(p_video), _p(p_cond), _p(p_image)
+    d.noise_video, d.noise_cond, d.noise_image, d.noise_diff = (_p(n) for n in noises)
+    d.seed = seed & _U64
+    d.stream_video, d.stream_cond, d.stream_image, d.stream_diff = (s & _U64 for s in streams)
+    d.timesteps, d.sa_sb, d.mask = _p(timesteps), _p(sa_sb), _p(mask)
+    d.target, d.noisy, d.noisy_model_input = _p(target), _p(noisy), _p(nmi)
+    d.masks_latent, d.conditioning_latents = _p(mlat), _p(cond)
+    ev = _t0("train_inputs")
+    N.check(N.lib().vp_train_inputs_bf16(C.byref(d), _stream()), "vp_train_inputs_bf16")
+    _t1("train_inputs", ev)
+    return target, noisy, nmi, mlat, cond

@@ -189,6 +189,18 @@ class CogVideoXDPMScheduler:
         t = torch.tensor([int(timestep)])
         return float((ac[t] ** 0.5).float()), float(((1 - ac[t]) ** 0.5).float())
 
+    def add_noise_table(self, dtype=BF16, device=None) -> torch.Tensor:
+        """fp32 [num_train_timesteps, 2]: row t = add_noise_scalars(t, dtype), the (sqrt(a_t), sqrt(1 - a_t)) that
+        `add_noise` multiplies with — computed in the sample dtype as :442-466 does, stored as fp32 (the operand of
+        vp_train_inputs_bf16).  Built once per (dtype, device) and kept."""
+        key = (dtype, None if device is None else torch.device(device))
+        cache = self.__dict__.setdefault("_add_noise_tables", {})
+        if key not in cache:
+            ac = self.alphas_cumprod.to(dtype=dtype)
+            tab = torch.stack([(ac ** 0.5).float(), ((1 - ac) ** 0.5).float()], dim=1).contiguous()
+            cache[key] = tab if device is None else tab.to(device)
+        return cache[key]
+
     def add_noise(self, original_samples: torch.Tensor, noise: torch.Tensor, timesteps: torch.IntTensor):
         """:442-466 (host formula; the pipeline fuses it into the step kernel)."""
         ac = self.alphas_cumprod.to(device=original_samples.device, dtype=original_samples.dtype)
