@@ -33,7 +33,7 @@ extern "C" {
 #define VP_ERR_UNSUPPORTED 1001
 
 /* ABI version: bump when any struct layout or signature below changes. */
-#define VP_ABI_VERSION 31
+#define VP_ABI_VERSION 32
 int vp_abi_version(void);
 /* "<sha256 of sources + flags>:<sha256 of the compiler version>" of the build (no reference counterpart) */
 const char* vp_build_digest(void);
@@ -378,6 +378,13 @@ int vp_adaln_modulate_bf16(const void* x, void* y, int64_t ldy, int32_t B, int32
 int vp_adaln_modulate_mx_fp8(const void* x, void* q, void* scales, int32_t B, int32_t Ntok, int32_t D,
                              int32_t text_len, const void* ln_w, const void* ln_b, float eps, const void* mod,
                              int64_t mod_bstride, void* stream);
+/* both at once, from one read of x (ABI 32): y receives the bytes vp_adaln_modulate_bf16 writes (rows at stride ldy)
+ * and q / scales the bytes vp_adaln_modulate_mx_fp8 writes, bit for bit — the MX quantiser reads the bf16-rounded row
+ * in either kernel.  For the fp8 QKV projection under unfused LoRA: the MX rows are the base GEMM's operand, the bf16
+ * rows the adapters' (T = x A^T, and in training dA = dT^T x).  D % 128 == 0. */
+int vp_adaln_modulate_bf16_mx_fp8(const void* x, void* y, int64_t ldy, void* q, void* scales, int32_t B, int32_t Ntok,
+                                  int32_t D, int32_t text_len, const void* ln_w, const void* ln_b, float eps,
+                                  const void* mod, int64_t mod_bstride, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Per-head LayerNorm(64) + interleaved-pair RoPE — attn.norm_q / norm_k (attention_processor.py:2143-2146) and

@@ -11,6 +11,11 @@ events, every shape warmed up first.  Three measurements:
   accuracy  the full-width resample block of tests/golden/block_resample.safetensors (r0, r1) on the fp8 resample
             path against the reference's fp32 slice, beside fp8_block_gate(ref_bf16_rel) of tests/test_model_gpu.py.
 
+  lora      (only when named) the same chain with enable_fp8(resample_attention=True) and a rank-256 adapter on
+            to_q / to_k / to_v / to_out.0 of every block (bench.py --lora-rank's synthetic factors): loaded as the
+            reference loads it — unfused, the adapters as low-rank bf16 launches beside the MX-FP8 projections —
+            against fuse_lora() (folded, the folded weights re-quantised), interleaved.
+
     python tools/bench_resample_fp8.py [--rounds 5] [--iters 3] [--only stage,chain,accuracy]
 """
 import argparse
@@ -142,7 +147,9 @@ def stage(rounds, iters):
     print("stage " + json.dumps(out), flush=True)
 
 
-def chain(rounds):
+def _chain_models():
+    """(transformer, branch, run): bench.py's config-4 models on the fp8 path and a call that runs the chain's 2
+    windows x 1 step."""
     import bench
     from videopainter_amd import CogVideoXTransformer3DModel, CogvideoXBranchModel, device_scope
     from videopainter_amd.config import COGVIDEOX_5B_I2V
@@ -170,6 +177,11 @@ def chain(rounds):
 
     def run():
         return harness(wins, pe, npe, num_inference_steps=1, generator=torch.Generator().manual_seed(0), **kw)
+    return tr, br, run
+
+
+def chain(rounds):
+    tr, br, run = _chain_models()
     res = {"resample_attention=False": [], "resample_attention=True": []}
     outs = {}
     with torch.no_grad():
@@ -188,6 +200,49 @@ def chain(rounds):
     f, t = (out["arms"][k]["median_ms"] for k in res)
     out["true_over_false_median"] = round(t / f, 4)
     print("chain " + json.dumps(out), flush=True)
+
+
+def lora(rounds, rank=256):
+    from videopainter_amd.lora import attach_lora_
+    tr, br, run = _chain_models()
+    tr.enable_fp8_attention(True, resample=True)
+    gl = torch.Generator(device=dev).manual_seed(91)
+    lsd = {}
+    for i, blk in enumerate(tr.transformer_blocks):  # (bench.py --lora-rank's adapter)
+        for t, lin in (("to_q", blk.attn1.to_q), ("to_k", blk.attn1.to_k), ("to_v", blk.attn1.to_v),
+                       ("to_out.0", blk.attn1.to_out[0])):
+            o_f, i_f = lin.weight.shape
+            lsd[f"transformer_blocks.{i}.attn1.{t}.lora_A.weight"] = (
+                torch.randn(rank, i_f, device=dev, generator=gl) * i_f ** -0.5).to(BF16)
+            lsd[f"transformer_blocks.{i}.attn1.{t}.lora_B.weight"] = (
+                torch.randn(o_f, rank, device=dev, generator=gl) * 0.01).to(BF16)
+    with torch.no_grad():
+        none = run().float()
+    attach_lora_(tr, lsd, 1.0, "vpid")
+    del lsd
+
+    def arm(fused):
+        tr.fuse_lora() if fused else tr.unfuse_lora()
+    res, outs = {"unfused": [], "fused": []}, {}
+    with torch.no_grad():
+        for a in res:  # warm-up of both forms
+            arm(a == "fused")
+            outs[a] = run().float()
+        torch.cuda.synchronize()
+        for _ in range(rounds):
+            for a in res:
+                arm(a == "fused")
+                torch.cuda.synchronize()
+                res[a].append(timeit(run, 1) * 1e3 / 2)  # per step: 2 windows x 1 step
+    u, f = outs["unfused"], outs["fused"]
+    out = {"what": f"config-4 chain on the fp8 path (QKV, resample attention, out, FFN), rank-{rank} adapter on every "
+                   "block's q / k / v / out, 2 windows x 1 step, ms per denoising step",
+           "arms": {k: summary(v) for k, v in res.items()},
+           "latents_rel_unfused_vs_fused": float((u - f).norm() / (f.norm() + 1e-30)),
+           "latents_rel_adapter_effect": float((f - none).norm() / (none.norm() + 1e-30))}
+    um, fm = (out["arms"][k]["median_ms"] for k in res)
+    out["unfused_over_fused_median"] = round(um / fm, 4)
+    print("lora " + json.dumps(out), flush=True)
 
 
 def accuracy():
@@ -247,6 +302,8 @@ def main():
         accuracy()
     if "chain" in only:
         chain(a.rounds)
+    if "lora" in only:
+        lora(a.rounds)
 
 
 if __name__ == "__main__":

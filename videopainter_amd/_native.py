@@ -11,7 +11,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VP_HIP_LIB", os.path.join(_HERE, "_lib", "libvp_hip.so"))
-ABI_VERSION = 31
+ABI_VERSION = 32
 
 vp = C.c_void_p
 i32 = C.c_int32
@@ -162,6 +162,7 @@ _SIGS = {
     "vp_qkv_heads_pack_fp8": (i32, [vp, i64, i64, vp, i32, i32, i32, i32, i32, vp, vp, f32, vp, vp, f32, vp, vp, f32,
                                     f32, vp]),
     "vp_adaln_modulate_mx_fp8": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, f32, vp, i64, vp]),
+    "vp_adaln_modulate_bf16_mx_fp8": (i32, [vp, vp, i64, vp, vp, i32, i32, i32, i32, vp, vp, f32, vp, i64, vp]),
     "vp_attention_fwd_bf16": (i32, [C.POINTER(AttnDesc), vp]),
     "vp_attention_fwd_fp8": (i32, [C.POINTER(AttnFp8Desc), vp]),
     "vp_attention_fp8_workspace_bytes": (i64, [C.POINTER(AttnFp8Desc)]),

@@ -464,13 +464,15 @@ class CogVideoXAttnProcessor2_0_resample(CogVideoXAttnProcessor2_0):
                qkv: Optional[torch.Tensor] = None, keep: Optional[dict] = None) -> torch.Tensor:
         """keep: a training forward's dict (autograd._BlockFn with the closed-form resample backward on): receives
         the attention output "o" and the statistics "lse" of the two-segment launch (the null-key mass included) —
-        the same launches as without it; window 0's bf16 closed-form plan only."""
+        the same launches as without it; window 0's bf16 closed-form plan only (the projection may be a handed-over
+        `qkv`, the block's fp8 one: the backward recomputes the pre-norm "qpre" / "kpre" / "v" and the normed "q" /
+        "k" from the same stages, autograd._TwoSegment)."""
         B, Ntok, D = x.shape
         rope = _rope_dev(image_rotary_emb, x.device)
         prev = prev_hidden_states is not None and prev_clip_weight is not None and prev_clip_weight > 0.0
         m, plan, fused = self.head_plan(attn, text_len, rope, prev, resample_mask, prev_resample_mask)
         fp8 = self.fp8_exponents(attn, plan)
-        if keep is not None and (prev or qkv is not None or fp8 is not None or plan[3] is None):
+        if keep is not None and (prev or fp8 is not None or plan[3] is None):
             raise ValueError("keep: window 0's bf16 attention with the null keys in closed form only")
         # (the block may hand over an fp8 projection; the fp8 form quantises from the pre-norm q / k: no fused
         # epilogue in either case)

@@ -54,8 +54,11 @@ aux output z the one addition), and the four dgrad GEMMs — the same projection
 vp_gemm_mx_fp8 too, against transposed weights quantised along the forward's output dimension (`_wt_mx`, `_qkv_t_mx`:
 built at the first backward), each dY quantised after its gate row-scale (kernels.rowscale_mx), the FF2 dgrad handing
 dz to the FF1 dgrad in MX (EPI_GELU_BWD_MXFP8).  FP8_DGRAD names the dgrads that do; the attention stays bf16 both ways.
-Such a block is refused with a trainable parameter or a wanted temb gradient (weight gradients and the modulation path
-are bf16-only), and qkv / out fp8 with the resample forms.
+Such a block is refused with a trainable base parameter or a wanted temb gradient (weight gradients and the modulation
+path are bf16-only); LoRA factors on to_q / to_k / to_v / to_out.0 train on it: their forward delta runs beside the
+fp8 base as low-rank bf16 launches (transformer.py), `_aug_dgrad` follows each base dgrad on the bf16 GEMM, and a
+block that trains q / k / v factors keeps the to_out dgrad in bf16 (FP8_DGRAD_LORA_OFF).  All three attention forms
+take the fp8 QKV / out projections of a block with adapters: their recompute reads the handed-over pre-norm qkv.
 Out of scope for the backward (NotImplementedError): the fp8 attention, the previous-clip blend (windows > 0) and
 `return_hidden_states` — inference-only in the reference.
 """
@@ -69,7 +72,7 @@ from . import _native as NAT
 from . import kernels as K
 from .attention_processor import (CogVideoXAttnProcessor2_0, CogVideoXAttnProcessor2_0_resample, _qkv,
                                   bounded_scores, keep_handed_qkv, keeps_all, project_out)
-from .lora import AugmentedProjection, augmented_rows
+from .lora import AugmentedProjection, augmented_rows, module_pairs
 
 BF16 = torch.bfloat16
 F32 = torch.float32
@@ -108,6 +111,19 @@ def _qkv_t(attn) -> torch.Tensor:
 # "qkv".  A name taken out keeps that dgrad on the bf16 GEMM against the bf16 transposed weight, while the forward
 # stays fp8 (the A/B arm, and the fallback should one GEMM's e4m3 dgrad cost too much accuracy).
 FP8_DGRAD = {"ff2", "ff1", "out", "qkv"}
+# A block that trains LoRA factors on q / k / v keeps the to_out dgrad on the bf16 GEMM whatever FP8_DGRAD says: its
+# e4m3 cost goes through the attention's backward into d(q | k | v), which those factors' gradients are sums of, and
+# alone pushes them outside the 5x band of one block (5.5 - 6.4x with it, <= 4.9x without; dx, which
+# averages over 3D columns more, stays inside either way).
+FP8_DGRAD_LORA_OFF = {"out"}
+
+
+def _out_dgrad_mx(block, train: bool) -> bool:
+    """The to_out dgrad of this backward runs on the fp8 GEMM."""
+    a = block.attn1
+    if block.out_mx is None or "out" not in FP8_DGRAD:
+        return False
+    return not (train and "out" in FP8_DGRAD_LORA_OFF and AugmentedProjection.of((a.to_q, a.to_k, a.to_v)) is not None)
 
 
 def _wt_mx(w: torch.Tensor) -> "K.MXTensor":
@@ -136,11 +152,12 @@ def _qkv_t_mx(attn) -> "K.MXTensor":
     return c[1]
 
 
-def _aug_tail_t(aug: AugmentedProjection) -> torch.Tensor:
+def _aug_tail_t(aug: AugmentedProjection, side: bool = False) -> torch.Tensor:
     """[R, sum out_i]: the transposed block-diagonal tail of the augmented weights — rows i r .. of projection i's
-    columns hold W_aug_i[:, K:]^T = (s B_i)^T, zero elsewhere (cached on the first Linear, keyed like them)."""
-    ws = aug.weights()
-    key = tuple(id(l) for l in aug.lins) + aug._key()
+    columns hold W_aug_i[:, K:]^T = (s B_i)^T, zero elsewhere (cached on the first Linear, keyed like them).  side:
+    built from the rank blocks alone (aug.tails(): the adapters beside an MX-FP8 base, which build no W_aug)."""
+    ws = aug.tails() if side else aug.weights()
+    key = tuple(id(l) for l in aug.lins) + aug._key() + (side,)
     owner = aug.lins[0]
     c = owner.__dict__.get("_vp_aug_tail_t")
     if c is None or c[0] != key:
@@ -148,7 +165,7 @@ def _aug_tail_t(aug: AugmentedProjection) -> torch.Tensor:
         wt = torch.zeros(aug.R, n, device=ws[0].device, dtype=BF16)
         off = 0
         for i, w in enumerate(ws):
-            c0 = aug.block_col(i)
+            c0 = 0 if side else aug.block_col(i)
             K.transpose(w[:, c0:c0 + aug.r], out=wt[i * aug.r:(i + 1) * aug.r, off:off + w.shape[0]])
             off += w.shape[0]
         c = (key, wt)
@@ -157,15 +174,16 @@ def _aug_tail_t(aug: AugmentedProjection) -> torch.Tensor:
 
 
 def _aug_dgrad(aug: AugmentedProjection, dy2: torch.Tensor, x2: Optional[torch.Tensor], out2: torch.Tensor, train: bool,
-               G: "_Grads", x_aug: Optional[torch.Tensor] = None) -> None:
+               G: "_Grads", x_aug: Optional[torch.Tensor] = None, side: bool = False) -> None:
     """Backward of the unfused-LoRA projections y_i = x_aug W_aug_i^T (lora.AugmentedProjection; segment i reads
     rank block i of T = x A_cat^T), given out2 = dy W0 (the base dgrad): out2 += dT A_cat with dT = dy W_tail
     (block i = s dy_i B_i).  With train: W0_i's gradient only when it trains (dy_i^T x), dB = s (dy_i^T T_i) from
-    the GEMM over rank block i of x_aug alone, dA = dT^T x — no full [N, K + R] weight gradient for frozen bases."""
+    the GEMM over rank block i of x_aug alone, dA = dT^T x — no full [N, K + R] weight gradient for frozen bases.
+    side: the adapters ran beside an MX-FP8 base projection (`_aug_tail_t`); the same launches on the same operands."""
     Kd, r = aug.K, aug.r
     M = dy2.shape[0]
     dT = torch.empty(M, aug.R, device=dy2.device, dtype=BF16)
-    K.gemm(dy2, [_aug_tail_t(aug)], [None], dT)
+    K.gemm(dy2, [_aug_tail_t(aug, side)], [None], dT)
     dxl = torch.empty(M, Kd, device=dy2.device, dtype=BF16)
     K.gemm(dT, [aug.a_cat_t()], [None], dxl)  # dT A_cat
     K.axpy(out2, dxl, out=out2)
@@ -354,14 +372,18 @@ class _TwoSegment(_AttentionForm):
     """The resample processor (window 0) as the backward differentiates it: keys / values as ONE buffer each,
     [B, 2N, D] — K / V in rows [0, N), the second segment behind them — so one flash backward covers both."""
 
-    def _recompute_operands(self, xn: torch.Tensor, T: int, rope, keep: dict, second=None):
-        """What both forms recompute alike: the pre-norm projections ("qpre" / "kpre"; `_qkv`), the buffers "q" [B, N,
-        D] and "k" / "v" [B, 2N, D], and the q and K norm launches into them — after `second(k, v, kc, vc)`, the
-        launches of a second segment built from the pre-norm projections.  Returns (v, kc, vc)."""
+    def _recompute_operands(self, xn: torch.Tensor, T: int, rope, keep: dict, second=None, qkv=None):
+        """What both forms recompute alike: the pre-norm projections ("qpre" / "kpre"; `_qkv`, or the columns of a
+        handed-over `qkv`, the block's fp8 projection), the buffers "q" [B, N, D] and "k" / "v" [B, 2N, D], and the q
+        and K norm launches into them — after `second(k, v, kc, vc)`, the launches of a second segment built from the
+        pre-norm projections.  Returns (v, kc, vc)."""
         a = self.a
         B, Ntok, D = xn.shape
         H, dev, nq, nk = a.heads, xn.device, a.norm_q, a.norm_k
-        qkv = _qkv(a, xn, None, keep)
+        if qkv is None:
+            qkv = _qkv(a, xn, None, keep)
+        else:
+            keep.update(qpre=qkv[..., :D], kpre=qkv[..., D:2 * D])
         q, k, v = qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:]
         qn = torch.empty(B, Ntok, D, device=dev, dtype=BF16)
         kc = torch.empty(B, 2 * Ntok, D, device=dev, dtype=BF16)
@@ -390,7 +412,7 @@ class _Explicit2N(_TwoSegment):
                              pre_scale=1.0)
             vc[:, :Ntok].copy_(v)
             K.mask_scale_rows(v, vc[:, Ntok:], self.mask, 1.0)
-        self._recompute_operands(xn, T, rope, keep, second)
+        self._recompute_operands(xn, T, rope, keep, second, qkv)
         o = augmented_rows((a.to_out[0],), *xn.shape, xn.device)
         lse = torch.empty(xn.shape[0], a.heads, Ntok, device=xn.device, dtype=F32)
         K.attention(keep["q"], keep["k"], keep["v"], o, a.heads, scale=a.scale, bounded_scores=bounded_scores(a),
@@ -443,7 +465,7 @@ class _ClosedForm(_TwoSegment):
         """No attention launch (the forward kept "o" / "lse"): compact copies, as the fused forward makes them."""
         Ntok = xn.shape[1]
         keep["plan"] = m, dst, _, _, _, _ = _closed_form_plan(self.a, T, rope, self.mask)
-        v, kc, vc = self._recompute_operands(xn, T, rope, keep)
+        v, kc, vc = self._recompute_operands(xn, T, rope, keep, qkv=qkv)
         # LN(1 . k) + RoPE of a masked row is K's row, and V2 = v there
         K.mask_scale_rows(kc[:, :Ntok], kc[:, Ntok:], m, 1.0, dst_rows=dst)
         vc[:, :Ntok].copy_(v)
@@ -484,6 +506,11 @@ def _mx_gemms(block) -> bool:
     return block.ff_mx is not None or block.qkv_mx is not None or getattr(block, "out_mx", None) is not None
 
 
+def _lora_factors(a) -> set:
+    """ids of the unfused LoRA factors on to_q / to_k / to_v / to_out.0: what a block on the MX-FP8 GEMMs may train."""
+    return {id(p) for lin in (a.to_q, a.to_k, a.to_v, a.to_out[0]) for A, B, _ in module_pairs(lin) for p in (A, B)}
+
+
 def _trainable_form(block, resample_mask=None, rope=None, temb=None):
     """The attention form of a block call the backward can run; raises what it refuses.  temb: the call's time
     embedding (whether its gradient is wanted)."""
@@ -492,16 +519,22 @@ def _trainable_form(block, resample_mask=None, rope=None, temb=None):
         raise NotImplementedError("the backward runs the bf16 path: disable the fp8 modes for training")
     form = _attention_form(a, resample_mask)
     if _mx_gemms(block):
-        # the dgrad GEMMs run against constant weights; weight gradients and the modulation path are bf16-only
-        if any(p.requires_grad for p in block.parameters()):
+        # the dgrad GEMMs run against constant weights; weight gradients and the modulation path are bf16-only.  The
+        # LoRA factors on the attention projections train: their low-rank backward runs on the bf16 GEMM (_aug_dgrad)
+        lora = _lora_factors(a)
+        if any(p.requires_grad and id(p) not in lora for p in block.parameters()):
             raise NotImplementedError("a block on the fp8 GEMMs trains no parameter of its own (its weight gradients "
-                                      "are bf16-only): freeze the block, or disable enable_fp8_ffn / _qkv / _out on it")
+                                      "are bf16-only) but LoRA factors on to_q / to_k / to_v / to_out.0: freeze the "
+                                      "rest, or disable enable_fp8_ffn / _qkv / _out on it")
         if temb is not None and temb.requires_grad and torch.is_grad_enabled():
             raise NotImplementedError("a block on the fp8 GEMMs builds no time-embedding gradient (the modulation "
                                       "path is bf16-only): detach temb, or disable enable_fp8_ffn / _qkv / _out on it")
-        if (block.qkv_mx is not None or block.out_mx is not None) and not isinstance(form, _SingleSegment):
+        if ((block.qkv_mx is not None or block.out_mx is not None) and not isinstance(form, _SingleSegment)
+                and not lora and AugmentedProjection.of((a.to_q, a.to_k, a.to_v, a.to_out[0])) is None):
+            # (as before the LoRA side path: lifted for the blocks that carry adapters, the ID training's)
             raise NotImplementedError("the fp8 QKV / output projections have no backward with the resample "
-                                      "processor: enable_fp8_ffn alone trains with it")
+                                      "processor on a block without LoRA adapters: enable_fp8_ffn alone trains "
+                                      "with it")
     form.check(rope)
     return form
 
@@ -623,10 +656,19 @@ def _attn_output_bwd(block, s: dict, g: torch.Tensor, T: int, mod1: torch.Tensor
     to_out = block.attn1.to_out[0]
     oaug = AugmentedProjection.of((to_out,))
     o2 = s["o"].view(M, D)
-    if block.out_mx is not None and "out" in FP8_DGRAD:
-        # (a frozen block without adapters — `_trainable_form`, enable_fp8_out: nothing below but the dgrad)
+    side = block.out_mx is not None and oaug is not None  # (the adapter ran beside the fp8 projection)
+    if _out_dgrad_mx(block, train):
+        # (`_trainable_form`: the base is frozen — the dgrad, and under an adapter its low-rank backward in bf16)
         s["do"] = do = torch.empty(B, Ntok, D, device=g.device, dtype=BF16)
-        K.gemm_mx(K.rowscale_mx(g.view(M, D), Ntok, T, mod1, 2, 5), [_wt_mx(to_out.weight)], [None], do.view(M, D))
+        if oaug is None:
+            K.gemm_mx(K.rowscale_mx(g.view(M, D), Ntok, T, mod1, 2, 5), [_wt_mx(to_out.weight)], [None], do.view(M, D))
+            return None
+        # the gate row-scale in bf16 (the adapter's dy), quantised from there: rowscale_mx's bytes
+        dao = torch.empty(M, D, device=g.device, dtype=BF16)
+        K.rowscale(g.view(M, D), dao, Ntok, T, mod1, 2, 5)
+        K.gemm_mx(K.mx_quantize(dao, out=K.MXTensor(M, D, g.device, zero=False)), [_wt_mx(to_out.weight)], [None],
+                  do.view(M, D))
+        _aug_dgrad(oaug, dao, o2, do.view(M, D), train, G, oaug.input(o2) if train else None, side=True)
         return None
     dao = torch.empty(M, D, device=g.device, dtype=BF16)
     K.rowscale(g.view(M, D), dao, Ntok, T, mod1, 2, 5)
@@ -642,17 +684,19 @@ def _attn_output_bwd(block, s: dict, g: torch.Tensor, T: int, mod1: torch.Tensor
             elif to_out.weight.requires_grad:
                 G.put(to_out.weight, K.wgrad(dao, o2))
             G.put(to_out.bias, _total(dao))
+    if train and oaug is not None and o_aug is None:  # (a block whose modulation path is off: need_dmod False)
+        o_aug = oaug.input(o2)
     do = torch.empty(B, Ntok, D, device=g.device, dtype=BF16)
     _dgrad(dao, to_out.weight, do.view(M, D))
     if oaug is not None:
-        _aug_dgrad(oaug, dao, o2, do.view(M, D), train and need_dmod, G, o_aug)
+        _aug_dgrad(oaug, dao, o2, do.view(M, D), train, G, o_aug, side=side)
     s["do"] = do
     return gate1
 
 
-def _qkv_bwd(a, s: dict, train: bool, G: _Grads, mx: bool = False) -> torch.Tensor:
+def _qkv_bwd(a, s: dict, train: bool, G: _Grads, mx: bool = False, side: bool = False) -> torch.Tensor:
     """The fused QKV projection: "dqkv" -> d xn [B, N, D], and the weight / bias / LoRA gradients.  mx: the dgrad on
-    the fp8 GEMM (a frozen block without adapters: the dgrad alone)."""
+    the fp8 GEMM (the base is frozen: the dgrad alone, and under adapters their low-rank backward in bf16)."""
     dqkv, xn, xq = s.pop("dqkv"), s.pop("xn", None), s.pop("xq", None)
     B, Ntok, D3 = dqkv.shape
     D, M = D3 // 3, B * Ntok
@@ -662,8 +706,14 @@ def _qkv_bwd(a, s: dict, train: bool, G: _Grads, mx: bool = False) -> torch.Tens
     if mx:
         dq8 = K.mx_quantize(dqkv.view(M, D3), out=K.MXTensor(M, D3, dqkv.device, zero=False))
         K.gemm_mx(dq8, [_qkv_t_mx(a)], [None], dxn.view(M, D))
+        if qaug is not None:
+            _aug_dgrad(qaug, dqkv.view(M, D3), xn.view(M, D) if train else None, dxn.view(M, D), train, G, xq, side=True)
         return dxn
+    side = side and qaug is not None  # (fp8 forward, this dgrad on the bf16 GEMM: the adapters ran beside the base)
     K.gemm(dqkv.view(M, D3), [_qkv_t(a)], [None], dxn.view(M, D))
+    if side:
+        _aug_dgrad(qaug, dqkv.view(M, D3), xn.view(M, D) if train else None, dxn.view(M, D), train, G, xq, side=True)
+        return dxn
     if train:
         db = _total(dqkv.view(M, D3))
         if qaug is None and any(l.weight.requires_grad for l in lins):
@@ -705,7 +755,9 @@ def block_backward(block, form, x: torch.Tensor, T: int, temb: torch.Tensor, rop
     then the attention is not recomputed; front: the training forward's keep-all dict (_BlockFn.forward) — then
     nothing is recomputed."""
     B, Ntok, D = x.shape
-    need_dmod = train or want_dtemb
+    # (a block on the MX-FP8 GEMMs trains LoRA factors at most and builds no temb gradient, `_trainable_form`: its
+    # modulation path — the gate sums, h, the AdaLN affine sums — is off)
+    need_dmod = (train or want_dtemb) and not _mx_gemms(block)
     G = _Grads()
     # the forward's intermediates: kept by the training forward (the `keep` level "all") or recomputed here by
     # forward_joint's own stages; the stages below pop them, and hand "do" / "dqkv" on, through this dict
@@ -726,7 +778,8 @@ def block_backward(block, form, x: torch.Tensor, T: int, temb: torch.Tensor, rop
     dmod2 = _ff_bwd(block, s, dout, g, T, mod2, need_dmod, train, G)
     gate1 = _attn_output_bwd(block, s, g, T, mod1, need_dmod, train, G)
     s["dqkv"] = form.backward(s, T, rope, train, G)
-    dxn = _qkv_bwd(block.attn1, s, train, G, block.qkv_mx is not None and "qkv" in FP8_DGRAD)
+    dxn = _qkv_bwd(block.attn1, s, train, G, block.qkv_mx is not None and "qkv" in FP8_DGRAD,
+                   block.qkv_mx is not None)
     dtemb = _attn_input_bwd(block, x, dxn, g, T, temb, mod1, gate1, dmod2, need_dmod, want_dtemb, train, G)
     return g, dtemb, dinj, G
 

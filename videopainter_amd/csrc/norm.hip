@@ -47,11 +47,13 @@ VP_DEV void row_stats(const RowRegs& r, int nch, int lane, int D, float& mean, f
 
 // AdaLN row body: x (this wave's row as NCH bf16 chunks per lane) -> normalised, modulated row (same arithmetic,
 // in the same order, as the reference chain: LayerNorm in fp32 from bf16, bf16 rounding after the affine, after
-// (1 + scale), after the product and after + shift)
-template <bool MX, int NCH>
+// (1 + scale), after the product and after + shift).  DUAL (with MX): the same rounded row is also stored as bf16 at
+// y16 (row stride ld16) — the values the MX quantiser reads, so both outputs equal the single-output kernels' bytes.
+template <bool MX, int NCH, bool DUAL = false>
 VP_DEV void adaln_row(bf16x8 (&xr)[NCH], int row, int lane, int Ntok, int D, int text_len, const bf16* __restrict__ lw,
                       const bf16* __restrict__ lb, float eps, const bf16* __restrict__ mod, int64_t mod_bs,
-                      void* __restrict__ y, uint8_t* __restrict__ yscale, int64_t ldy) {
+                      void* __restrict__ y, uint8_t* __restrict__ yscale, int64_t ldy, bf16* __restrict__ y16 = nullptr,
+                      int64_t ld16 = 0) {
   const int b = row / Ntok;
   const int tok = row - b * Ntok;
   const int nch = D / 8;
@@ -94,6 +96,12 @@ VP_DEV void adaln_row(bf16x8 (&xr)[NCH], int row, int lane, int Ntok, int D, int
         const float n = rbf((bf2f(xr[i][e]) - mean) * rstd * bf2f(w[e]) + bf2f(bb[e]));
         const float s1 = rbf(1.f + bf2f(sc[e]));
         f[e] = rbf(rbf_prod(n * s1) + bf2f(sh[e]));
+      }
+      if constexpr (DUAL) {
+        bf16x8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = f2bf(f[e]);
+        *(bf16x8*)(y16 + (int64_t)row * ld16 + c * 8) = o;
       }
       if constexpr (MX) {
         uint8_t sb;
@@ -161,6 +169,21 @@ void launch_adaln(int rows, hipStream_t s, const bf16* x, void* y, uint8_t* ys, 
   else if (nch <= 6) VP_ADALN(6);
   else VP_ADALN(8);
 #undef VP_ADALN
+}
+
+// Both forms of the modulated row from one read of x (the fp8 QKV projection under unfused LoRA: the MX rows feed the
+// base GEMM, the bf16 rows the adapters' low-rank GEMMs and, in training, dA = dT^T x).
+template <int NCH>
+__global__ __launch_bounds__(ROW_THREADS) void adaln_modulate_dual_kernel(
+    const bf16* __restrict__ x, bf16* __restrict__ y16, int64_t ld16, void* __restrict__ q, uint8_t* __restrict__ qscale,
+    int rows, int Ntok, int D, int text_len, const bf16* __restrict__ lw, const bf16* __restrict__ lb, float eps,
+    const bf16* __restrict__ mod, int64_t mod_bs) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * (ROW_THREADS / 64) + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  bf16x8 xr[NCH];
+  load_row_bf16<NCH>(xr, x + (int64_t)row * D, lane, D / 8);
+  adaln_row<true, NCH, true>(xr, row, lane, Ntok, D, text_len, lw, lb, eps, mod, mod_bs, q, qscale, D, y16, ld16);
 }
 
 // ---- final norm_final + norm_out (cogvideox_transformer_3d.py:617-624; normalization.py:73-85) ----
@@ -532,6 +555,31 @@ extern "C" int vp_adaln_modulate_mx_fp8(const void* x, void* q, void* scales, in
   const int rows = B * Ntok;
   launch_adaln<true>(rows, (hipStream_t)stream, (const bf16*)x, q, (uint8_t*)scales, Ntok, D, text_len,
                      (const bf16*)ln_w, (const bf16*)ln_b, eps, (const bf16*)mod, mod_bstride, D);
+  VP_CHECK_LAUNCH();
+  return VP_OK;
+}
+
+extern "C" int vp_adaln_modulate_bf16_mx_fp8(const void* x, void* y, int64_t ldy, void* q, void* scales, int32_t B,
+                                             int32_t Ntok, int32_t D, int32_t text_len, const void* ln_w,
+                                             const void* ln_b, float eps, const void* mod, int64_t mod_bstride,
+                                             void* stream) {
+  if (!x || !y || !q || !scales || !ln_w || !ln_b || !mod || B <= 0 || Ntok <= 0 || D <= 0 || (D % 128) ||
+      D > MAXC * 512)
+    return VP_ERR_ARG;
+  if ((mod_bstride % 8) || ldy < D || (ldy % 8)) return VP_ERR_ARG;
+  const int rows = B * Ntok;
+  const int nch = (D / 8 + 63) / 64;
+  const int grid = (rows + 3) / 4;
+#define VP_ADALN2(N) hipLaunchKernelGGL((adaln_modulate_dual_kernel<N>), dim3(grid), dim3(ROW_THREADS), 0, \
+                                        (hipStream_t)stream, (const bf16*)x, (bf16*)y, ldy, q, (uint8_t*)scales, rows, \
+                                        Ntok, D, text_len, (const bf16*)ln_w, (const bf16*)ln_b, eps, (const bf16*)mod, \
+                                        mod_bstride)
+  if (nch <= 1) VP_ADALN2(1);
+  else if (nch <= 2) VP_ADALN2(2);
+  else if (nch <= 4) VP_ADALN2(4);
+  else if (nch <= 6) VP_ADALN2(6);
+  else VP_ADALN2(8);
+#undef VP_ADALN2
   VP_CHECK_LAUNCH();
   return VP_OK;
 }

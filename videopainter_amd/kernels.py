@@ -360,6 +360,27 @@ def adaln_modulate_mx(x: torch.Tensor, ln_w: torch.Tensor, ln_b: torch.Tensor, m
     return out
 
 
+def adaln_modulate_dual(x: torch.Tensor, ln_w: torch.Tensor, ln_b: torch.Tensor, mod: torch.Tensor, text_len: int,
+                        eps: float, out: Optional[torch.Tensor] = None, out_mx: Optional["MXTensor"] = None):
+    """AdaLN-Zero modulate writing the row both ways from one read of x -> (bf16 rows, MXTensor): `adaln_modulate`'s
+    and `adaln_modulate_mx`'s bytes (the fp8 QKV projection under unfused LoRA).  out: as `adaln_modulate`'s."""
+    _chk(x, "x")
+    if not x.is_contiguous():
+        raise ValueError("x must be contiguous [B, N, D]")
+    B, Ntok, D = x.shape
+    out = torch.empty_like(x) if out is None else out
+    _chk(out, "out")
+    ldy = out.stride(-2)
+    if (out.shape[-1] != D or out.stride(-1) != 1 or out.numel() != B * Ntok * D
+            or (out.dim() == 3 and out.stride(0) != Ntok * ldy)):
+        raise ValueError("adaln out must be [B, N, D] / [B*N, D] rows with a contiguous last dim")
+    out_mx = MXTensor(B * Ntok, D, x.device, zero=False) if out_mx is None else out_mx
+    N.check(N.lib().vp_adaln_modulate_bf16_mx_fp8(_p(x), _p(out), ldy, _p(out_mx.q), _p(out_mx.scales), B, Ntok, D,
+                                                  text_len, _p(ln_w), _p(ln_b), eps, _p(mod), mod.stride(0),
+                                                  _stream()), "vp_adaln_modulate_bf16_mx_fp8")
+    return out, out_mx
+
+
 def mx_mfma_probe(A: torch.Tensor, B: torch.Tensor, sa: torch.Tensor, sb: torch.Tensor) -> torch.Tensor:
     """One block-scaled MFMA (layout self-test): A, B uint8 e4m3 [16, 128]; sa, sb uint8 [64] (lane scales)."""
     Cm = torch.empty(16, 16, device=A.device, dtype=torch.float32)

@@ -19,7 +19,9 @@ Here every adapted projection runs ONE GEMM on K-augmented operands (`AugmentedP
 and the GEMM's per-segment A tail (include/vp_hip.h vp_gemm_desc.a_tail_k / a_tail_off) lets segment i of the fused
 QKV read only its own rank block: the extra work is PEFT's (2 r (K + N) per row and projection), the delta enters
 in the fp32 accumulator before the fused epilogues (qk-norm + RoPE, the gated residual), and W0 is never modified —
-the reference's arithmetic up to PEFT's extra bf16 roundings of x A^T and of the delta.
+the reference's arithmetic up to PEFT's extra bf16 roundings of x A^T and of the delta.  Beside a base projection on
+the MX-FP8 GEMM (enable_fp8_qkv / _out) the same T feeds low-rank bf16 launches of their own instead (`tails`,
+`side_delta`: PEFT's base(x) + lora_B(lora_A(x)) * scaling as launches; CogVideoXBlock._attn_input / _attn_output).
 
 Loaded adapters (`attach_lora_`, `load_lora_weights`) and trainable ones (`add_trainable_adapter_`, PEFT's
 `add_adapter`) take the same path.  `fuse_lora` is the explicit fold (W = W0 + s B A in fp32, rounded once; the base
@@ -178,7 +180,7 @@ def _requant_fp8(model) -> None:
 @torch.no_grad()
 def refold_lora_(model: torch.nn.Module, scale: Optional[float] = None) -> int:
     """Set the per-call scale and rebuild every weight that holds a fold from its kept base (exact).  Unfused
-    projections need nothing: their augmented operands follow the scale.  Re-quantises an enabled fp8 QKV."""
+    projections need nothing: their augmented operands follow the scale.  Re-quantises an enabled fp8 QKV / out."""
     st = lora_state(model)
     if st is None:
         return 0
@@ -194,21 +196,6 @@ def refold_lora_(model: torch.nn.Module, scale: Optional[float] = None) -> int:
 
 def _mark(lin, st: LoraState, mod: str) -> None:
     lin.__dict__["_vp_lora_mod"] = (st, mod)
-
-
-def _check_fp8_free(model, mods_of_blocks) -> None:
-    """Unfused adapters cannot ride the MX-FP8 QKV / output-projection GEMMs: raise BEFORE anything is attached
-    (fuse_lora folds them)."""
-    mods = dict(model.named_modules())
-    for name, _ in mods_of_blocks:
-        blk = name.rsplit(".attn1.", 1)[0]
-        b = mods.get(blk)
-        if b is not None and getattr(b, "qkv_mx", None) is not None and re.search(r"\.to_[qkv]$", name):
-            raise NotImplementedError(f"{name}: the fp8 QKV projection is enabled; unfused LoRA runs on the bf16 "
-                                      "GEMM (disable fp8 QKV, or fuse_lora())")
-        if b is not None and getattr(b, "out_mx", None) is not None and re.search(r"\.to_out\.0$", name):
-            raise NotImplementedError(f"{name}: the fp8 output projection is enabled; unfused LoRA runs on the bf16 "
-                                      "GEMM (disable it, or fuse_lora())")
 
 
 @torch.no_grad()
@@ -232,8 +219,6 @@ def attach_lora_(model: torch.nn.Module, sd: Dict[str, torch.Tensor], lora_scale
     name = adapter_name or f"default_{len(st.adapters)}"
     if any(n == name for n, _ in st.adapters):
         raise ValueError(f"adapter {name!r} is already loaded")
-    if not st.fused:
-        _check_fp8_free(model, [(m, mods[m]) for m in pairs if covered(m)])
     for mod in pairs:
         if _folded_here(st, mod) and mod not in st.base:
             st.base[mod] = mods[mod].weight.detach().clone()
@@ -289,8 +274,6 @@ def unfuse_lora_(model: torch.nn.Module) -> None:
     if st is None or not st.fused:
         return
     mods = dict(model.named_modules())
-    # (unfused adapters cannot ride an enabled fp8 QKV — raise before anything changes, not half-way)
-    _check_fp8_free(model, [(m, mods[m]) for m in st.base if covered(m)])
     for mod in [m for m in st.base if covered(m)]:
         mods[mod].weight.copy_(st.base.pop(mod))
     st.fused = False
@@ -334,7 +317,14 @@ def add_trainable_adapter_(model: torch.nn.Module, r: int, lora_alpha: float, ta
     for name, lin in matched:
         if hasattr(lin, "lora_A"):
             raise ValueError(f"{name} already carries a trainable adapter (one trainable adapter per model)")
-    _check_fp8_free(model, matched)
+    # TRAINABLE factors on q / k / v go on before the fp8 QKV projection is enabled (add_adapter, then enable_fp8:
+    # the launches are those of the other order, which loaded adapters may take): raise before anything is attached
+    mods = dict(model.named_modules())
+    for name, _ in matched:
+        b = mods.get(name.rsplit("attn1.", 1)[0].rstrip("."), model)
+        if getattr(b, "qkv_mx", None) is not None and re.search(r"(^|\.)to_[qkv]$", name):
+            raise NotImplementedError(f"{name}: the fp8 QKV projection is enabled already; add the trainable adapter "
+                                      "first, then enable_fp8_qkv / enable_fp8")
     model.requires_grad_(False)
     pairs = {}
     for name, lin in matched:
@@ -484,6 +474,46 @@ class AugmentedProjection:
                 l.__dict__["_vp_aug_W"] = c
             out.append(c[1])
         return out
+
+    def tails(self):
+        """[s B_i] bf16 [out_i, r] (zero columns for the padding), one per Linear and cached on it: W_aug_i's rank
+        block alone — the weights of the low-rank launches that run beside an MX-FP8 base projection (`side_delta`),
+        where no W_aug is built."""
+        out = []
+        for l, ps in zip(self.lins, self.pairs):
+            k = (self._pkey(ps), self.r)
+            c = l.__dict__.get("_vp_aug_tail")
+            if c is None or c[0] != k:
+                w = torch.zeros(l.weight.shape[0], self.r, device=l.weight.device, dtype=torch.bfloat16)
+                o = 0
+                for A, B, s in ps:
+                    w[:, o:o + A.shape[0]].copy_(B.detach().float() * s)
+                    o += A.shape[0]
+                c = (k, w)
+                l.__dict__["_vp_aug_tail"] = c
+            out.append(c[1])
+        return out
+
+    def side_delta(self, x_aug: torch.Tensor, out2d: torch.Tensor, **kw) -> torch.Tensor:
+        """The adapters' deltas beside a base projection that runs elsewhere (the MX-FP8 GEMM): one bf16 GEMM per
+        projection that carries an adapter, rank block i of T (x_aug's columns K + i r ..) against s B_i, into
+        projection i's columns of out2d.  Without kw the delta is added IN PLACE onto the base output out2d holds
+        (EPI_BIAS_ADDROWS with addrows = C: out = rnd(rnd(acc) + out), each element read and written by one thread);
+        with kw (the gated epilogue's) it is the caller's epilogue, a single projection."""
+        from . import _native as NAT
+        from . import kernels as K
+        col = 0
+        for i, (l, ps, w) in enumerate(zip(self.lins, self.pairs, self.tails())):
+            n = l.weight.shape[0]
+            if ps:
+                t = x_aug[:, self.K + i * self.r:self.K + (i + 1) * self.r]
+                c = out2d[:, col:col + n]
+                if kw:
+                    K.gemm(t, [w], [None], c, **kw)
+                else:
+                    K.gemm(t, [w], [None], c, epilogue=NAT.EPI_BIAS_ADDROWS, addrows=c)
+            col += n
+        return out2d
 
     def input(self, x2d: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """x_aug [M, K + R] = [x | x A_cat^T] (one GEMM for T).  `out`: a buffer whose first K columns already

@@ -241,15 +241,12 @@ class CogVideoXBlock(nn.Module):
 
     def enable_fp8_qkv(self, enabled: bool = True) -> None:
         """Fused QKV projection on the block-scaled fp8 MFMA: the three weights quantised once to MX-FP8, the norm1
-        AdaLN writing MX-FP8 directly, bf16 q/k/v out (the prev-clip K/V projection stays bf16)."""
+        AdaLN writing MX-FP8 directly, bf16 q/k/v out (the prev-clip K/V projection stays bf16).  Unfused LoRA adapters
+        on q / k / v (loaded ones attached before or after this call, trainable ones before it) run beside it as low-rank bf16 launches (`_attn_input`)."""
         if not enabled:
             self.qkv_mx = None
             return
         a = self.attn1
-        from .lora import module_pairs
-        if any(module_pairs(l) for l in (a.to_q, a.to_k, a.to_v)):
-            raise NotImplementedError("fp8 QKV with unfused LoRA adapters on q / k / v: fuse_lora() (loaded adapters) "
-                                      "or drop the adapter first")
         ws = (a.to_q.weight, a.to_k.weight, a.to_v.weight)
         if any(w.shape[0] % 256 or w.shape[1] % 128 for w in ws):
             raise ValueError("fp8 QKV needs widths that are multiples of 256")
@@ -258,15 +255,12 @@ class CogVideoXBlock(nn.Module):
     def enable_fp8_out(self, enabled: bool = True) -> None:
         """The attention's output projection (to_out[0], attention_processor.py:2202) on the block-scaled fp8 MFMA:
         the weight quantised once to MX-FP8, the attention output quantised per call (vp_mx_quantize_bf16), the gated
-        residual in the fp8 GEMM's epilogue as in the bf16 path."""
+        residual in the fp8 GEMM's epilogue as in the bf16 path.  An unfused LoRA adapter on to_out (attached before
+        or after this call) runs beside it as low-rank bf16 launches (`_attn_output`)."""
         if not enabled:
             self.out_mx = None
             return
         lin = self.attn1.to_out[0]
-        from .lora import module_pairs
-        if module_pairs(lin):
-            raise NotImplementedError("fp8 output projection with an unfused LoRA adapter on to_out: fuse_lora() "
-                                      "(loaded adapters) or drop the adapter first")
         if lin.weight.shape[0] % 256 or lin.weight.shape[1] % 128:
             raise ValueError("fp8 output projection needs widths that are multiples of 256")
         self.out_mx = K.mx_quantize(lin.weight)
@@ -350,14 +344,31 @@ class CogVideoXBlock(nn.Module):
         """norm1 AdaLN -> (xn, qkv, pn): the attention's bf16 operand xn (written straight into the projection's
         K-augmented operand under unfused LoRA, unless an `attend` hook takes it: augment=False), or with the fp8 QKV
         projection the MX-FP8 modulate + GEMM's output qkv; pn: the previous window's states through the same norm1
-        (reference :141-146), the prev-clip K / V operand."""
+        (reference :141-146), the prev-clip K / V operand.
+
+        The fp8 QKV projection under unfused LoRA on q / k / v is PEFT's base(x) + lora_B(lora_A(x)) * scaling as
+        launches: the dual modulate writes the MX rows and, into the K-augmented operand, the bf16 rows; the MX GEMM
+        writes the base qkv; T = x A_cat^T (lora.AugmentedProjection.input) and one low-rank bf16 GEMM per adapted
+        projection add the delta onto it in place, qkv = rnd(rnd(T_i (s B_i)^T) + qkv) (`side_delta`).  xn is then
+        returned beside qkv, and a keep-all training forward keeps it and the operand ("xn", "xq")."""
         B, Ntok, D = x.shape
         a, n1 = self.attn1, self.norm1.norm
         xn = qkv = pn = None
         if self.qkv_mx is not None:
-            xq = K.adaln_modulate_mx(x, n1.weight, n1.bias, mod1, text_len, n1.eps)
+            lins = (a.to_q, a.to_k, a.to_v)
+            qaug = AugmentedProjection.of(lins)
+            if qaug is None:
+                xq = K.adaln_modulate_mx(x, n1.weight, n1.bias, mod1, text_len, n1.eps)
+            else:
+                xn, xq = K.adaln_modulate_dual(x, n1.weight, n1.bias, mod1, text_len, n1.eps,
+                                               out=augmented_rows(lins, B, Ntok, D, x.device))
             qkv = torch.empty(B, Ntok, 3 * D, device=x.device, dtype=x.dtype)
             K.gemm_mx(xq, list(self.qkv_mx), [a.to_q.bias, a.to_k.bias, a.to_v.bias], qkv.view(B * Ntok, 3 * D))
+            if qaug is not None:
+                x_aug = qaug.input(xn.reshape(-1, D))
+                qaug.side_delta(x_aug, qkv.view(B * Ntok, 3 * D))
+                if keeps_all(keep) and keep["train"]:
+                    keep["xn"], keep["xq"] = xn, x_aug
         else:
             xn = self._norm1(x, mod1, text_len,
                              augmented_rows((a.to_q, a.to_k, a.to_v), B, Ntok, D, x.device) if augment else None)
@@ -378,8 +389,9 @@ class CogVideoXBlock(nn.Module):
         rule of its attention's backward form (autograd: `keep_level`)."""
         a = self.attn1
         if attend is not None:
+            # (an unfused adapter on to_out reads the bf16 o: the hook then hands that back, not the MX operand)
             return attend(a, x, text_len, rope, pn, prev_clip_weight, resample_mask, prev_resample_mask, qkv,
-                          self.out_mx is not None)
+                          self.out_mx is not None and AugmentedProjection.of((a.to_out[0],)) is None)
         return a.processor.attend(a, x, text_len, rope, pn, prev_clip_weight, resample_mask, prev_resample_mask,
                                   qkv=qkv, keep=keep)
 
@@ -387,12 +399,22 @@ class CogVideoXBlock(nn.Module):
                      keep: Optional[dict] = None) -> torch.Tensor:
         """to_out (bf16, or the fp8 projection of the re-quantised o) with the gated residual on x -> x_mid.  o: bf16
         [B, N, D], or with the fp8 projection its MX-FP8 operand already (an MXTensor [B N, D]: the head-parallel
-        split quantises while it gathers the heads, kernels.mx_quantize_heads)."""
+        split quantises while it gathers the heads, kernels.mx_quantize_heads).
+
+        The fp8 projection under an unfused LoRA adapter on to_out: the adapter's low-rank bf16 GEMM runs first, under
+        the gated epilogue without a bias onto the residual, R' = rnd(x + rnd(gate rnd(T (s B)^T))) into a buffer of
+        its own, and the MX GEMM then takes R' as its residual: x + gate (base + bias + delta) up to those roundings."""
         B, Ntok, D = x.shape
         M = B * Ntok
         x_mid = torch.empty_like(x)
         kw = dict(epilogue=NAT.EPI_GATED, resid=x.view(M, D), mod=mod1, tokens_per_batch=Ntok, text_len=text_len)
         if self.out_mx is not None:
+            oaug = AugmentedProjection.of((self.attn1.to_out[0],))
+            if oaug is not None:
+                if isinstance(o, K.MXTensor):
+                    raise ValueError("an unfused LoRA adapter on to_out reads the bf16 attention output")
+                kw["resid"] = oaug.side_delta(oaug.input(o.view(M, D)), torch.empty(M, D, device=x.device, dtype=BF16),
+                                              gate_chunk=2, gate_text_chunk=5, **kw)
             om = o if isinstance(o, K.MXTensor) else \
                 K.mx_quantize(o.view(M, D), out=K.MXTensor(M, D, x.device, zero=False))
             K.gemm_mx(om, [self.out_mx], [self.attn1.to_out[0].bias], x_mid.view(M, D), **kw)
@@ -408,14 +430,14 @@ class CogVideoXBlock(nn.Module):
         keep, at the level "all", receives the pre-activation "z" — the epilogue's aux output (of either GEMM),
         requested then only; a backward that needs no h passes activate=False: FF1 then stores z alone (the fp8 FF1
         under EPI_BIAS: the same bits), nothing is returned — and, for trainable parameters, "xn2" and "h" (bf16
-        FeedForward only: a block on the fp8 GEMMs trains none, autograd._trainable_form)."""
+        FeedForward only: a block on the fp8 GEMMs trains LoRA factors at most, autograd._trainable_form)."""
         B, Ntok, D = x_mid.shape
         M = B * Ntok
         n2, ff0 = self.norm2.norm, self.ff.net[0].proj
         if self.ff_mx is not None:
             w1 = self.ff_mx[0]
             xq = K.adaln_modulate_mx(x_mid, n2.weight, n2.bias, mod2, text_len, n2.eps)
-            # a frozen block (autograd refuses trainable parameters beside the MX GEMMs): z is all its backward reads
+            # (autograd refuses trainable FeedForward parameters beside the MX GEMMs): z is all its backward reads
             z = None
             if keeps_all(keep):
                 keep["z"] = z = torch.empty(M, w1.rows, device=x_mid.device, dtype=BF16)
